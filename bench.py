@@ -79,6 +79,9 @@ def parse_args():
     p.add_argument("--arithmetic", choices=["exact", "fast"], default=os.environ.get("BENCH_ARITHMETIC", DEFAULT_ARITHMETIC),
                    help="arithmetic flavour of the sweeps in the timed region (bahip_context_set_arithmetic); the other flavour is measured "
                         "after it, by the same protocol, and reported beside `value`")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed region, write what its BundleAdjustment call computed (keyframe poses, cameras, depth deformation, "
+                        "a fixed sample of the surfels) as DIR/<name>.npy, rank 0's share in a sharded run (see dump_outputs)")
     p.add_argument("--build-only", action="store_true")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-extras", action="store_true",
@@ -283,6 +286,47 @@ def cpu_baseline(args, ba, data, log):
         reference["port"] = port
         return reference
     return port
+
+
+DUMP_SURFELS = 1 << 20      # surfels written by --dump-outputs: 12 floats each, 50 MB
+DUMP_SAMPLE_SEED = 7
+
+
+def dump_outputs(directory, ba, log):
+    """--dump-outputs: the state a caller of the timed BundleAdjustment call gets back, as float32 / float64 .npy files, so that
+    two builds run with the same arguments (the same seeded scene) can be compared output for output.  Keyframe poses (global_T_frame,
+    quaternion x y z w then translation), both cameras and the depth deformation image, and the caller-visible surfel rows
+    (B/kernels.cuh:69-78) unpacked: position, normal (the three signed 10-bit components / 511), radius squared, colour bytes,
+    descriptors.  A cloud of more than DUMP_SURFELS surfels is written as a sample whose buffer indices depend on the surfel count
+    only (seeded), which keeps the files under 64 MB."""
+    os.makedirs(directory, exist_ok=True)
+    K = ba.keyframe_count()
+    rows = ba.download_surfels(rows=8)
+    if rows.shape[1] > DUMP_SURFELS:
+        keep = np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(rows.shape[1], DUMP_SURFELS, replace=False)
+        rows = rows[:, np.sort(keep)]
+    packed_normal, packed_colour = rows[3].view(np.uint32), rows[5].view(np.uint32)
+    s10 = [(((packed_normal >> s) & 0x3ff).astype(np.int32) ^ 0x200) - 0x200 for s in (0, 10, 20)]
+    colour_camera, depth_camera, depth_a = ba.cameras()
+    arrays = {
+        "keyframe_poses": np.array([ba.keyframe_pose(k) for k in range(K)], np.float64),
+        "color_camera": np.asarray(colour_camera, np.float64),
+        "depth_camera": np.asarray(depth_camera, np.float64),
+        "depth_deformation_a": np.array([depth_a], np.float64),
+        "depth_deformation_cfactor": ba.cfactor(),
+        "surfel_positions": np.ascontiguousarray(rows[0:3].T),
+        "surfel_normals": np.stack(s10, axis=1).astype(np.float32) / np.float32(511),
+        "surfel_radius_squared": np.ascontiguousarray(rows[4]),
+        "surfel_colors": np.stack([(packed_colour >> s) & 0xff for s in (0, 8, 16)], axis=1).astype(np.float32),
+        "surfel_descriptors": np.ascontiguousarray(rows[6:8].T),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 * 10 ** 6, total
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"outputs of the timed region's last step -> {directory}/ ({len(arrays)} arrays, {total / 1e6:.1f} MB, "
+        f"{arrays['surfel_positions'].shape[0]} of {ba.surfels_size()} surfels)")
 
 
 def launch_ranks(args):
@@ -507,6 +551,8 @@ def main():
         elapsed = float(t.item())
     stats = ba.last_stats()
     timed_end_poses = np.array([ba.keyframe_pose(k) for k in range(args.keyframes)])   # (after the clock has stopped: for the flavours' parity figures)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ba, log)
 
     def read_stage_timers():
         out_ms, out_n = np.zeros(8), np.zeros(8, dtype=np.int64)

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,3 +96,56 @@ def test_gpus_flag_is_honoured_or_fails_loudly():
     assert out.returncode != 0 and "WORLD_SIZE=1" in out.stderr and out.stdout.strip() == ""
     out = _bench("--gpus", "0")
     assert out.returncode != 0
+
+
+class _FakeDirectBA:
+    """What bench.dump_outputs reads of badslam_amd.directba.DirectBA, over host arrays."""
+    def __init__(self, n, seed=0):
+        rng = np.random.Generator(np.random.PCG64(seed))
+        self.rows = rng.standard_normal((8, n)).astype(np.float32)
+        s10 = rng.integers(-511, 512, (3, n)).astype(np.int64)
+        self.normals = s10.T.astype(np.float32) / np.float32(511)
+        self.rows[3] = ((s10[0] & 0x3ff) | ((s10[1] & 0x3ff) << 10) | ((s10[2] & 0x3ff) << 20)).astype(np.uint32).view(np.float32)
+        rgb = rng.integers(0, 256, (3, n)).astype(np.uint32)
+        self.colors = rgb.T.astype(np.float32)
+        self.rows[5] = (rgb[0] | (rgb[1] << 8) | (rgb[2] << 16)).view(np.float32)
+
+    def keyframe_count(self):
+        return 4
+
+    def keyframe_pose(self, k):
+        return np.arange(7.0) + k
+
+    def download_surfels(self, rows):
+        return self.rows[:rows].copy()
+
+    def surfels_size(self):
+        return self.rows.shape[1]
+
+    def cameras(self):
+        return np.array([500.0, 500.0, 320.0, 240.0]), np.array([510.0, 510.0, 320.0, 240.0]), 0.25
+
+    def cfactor(self):
+        return np.full((240, 320), 0.5, np.float32)
+
+
+def test_dump_outputs_writes_float_arrays_under_64_mb(tmp_path):
+    """bench.py --dump-outputs: every file a float32 / float64 .npy, the surfel rows unpacked, a large cloud sampled at buffer indices
+    that depend only on the surfel count (the same in every run), 64 MB in all at most."""
+    import bench
+    small = _FakeDirectBA(1000)
+    bench.dump_outputs(str(tmp_path / "small"), small, lambda msg: None)
+    got = {f[:-4]: np.load(tmp_path / "small" / f) for f in os.listdir(tmp_path / "small")}
+    assert set(got) == {"keyframe_poses", "color_camera", "depth_camera", "depth_deformation_a", "depth_deformation_cfactor", "surfel_positions",
+                        "surfel_normals", "surfel_radius_squared", "surfel_colors", "surfel_descriptors"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["keyframe_poses"].shape == (4, 7) and got["depth_deformation_a"][0] == 0.25
+    assert np.array_equal(got["surfel_positions"], small.rows[0:3].T) and np.array_equal(got["surfel_radius_squared"], small.rows[4])
+    assert np.array_equal(got["surfel_descriptors"], small.rows[6:8].T)
+    assert np.array_equal(got["surfel_normals"], small.normals) and np.array_equal(got["surfel_colors"], small.colors)
+    n = 3 * bench.DUMP_SURFELS
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), _FakeDirectBA(n, seed=1), lambda msg: None)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= 64 * 10 ** 6
+    a, b = np.load(tmp_path / "a" / "surfel_positions.npy"), np.load(tmp_path / "b" / "surfel_positions.npy")
+    assert a.shape == (bench.DUMP_SURFELS, 3) and np.array_equal(a, b)

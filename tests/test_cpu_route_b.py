@@ -1,5 +1,7 @@
 """Route B of INTEGRATION.md without a GPU: the shim (badslam_amd/host/route_b/kernels_hip.cc) must implement every function its
 stand-in for the reference's B/kernels.h declares, with the reference's argument lists, and link against the two libraries."""
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -37,19 +39,19 @@ def _declarations(text):
 
 
 def test_signatures_follow_the_reference_header():
-    """Where the reference tree is at hand (the build container), every declaration of the stand-in is held against the text of
-    the real B/kernels.h: the whole parameter list -- types, names, order, default values -- token for token, and the line range
-    the stand-in cites for it (the citations had drifted; the claim "same interface" rested on a hand copy
-    nobody diffed).  Elsewhere the committed stand-in is what documents the signatures."""
-    ref = "/root/reference/applications/badslam/src/badslam/kernels.h"
-    if not os.path.exists(ref):
-        import pytest
-        pytest.skip("reference tree not present")
+    """Every declaration of the stand-in is held against the real B/kernels.h: the whole parameter list -- types, names, order,
+    default values -- token for token, and the line range the stand-in cites for it (VERDICT r2 weak 10: the citations had drifted;
+    the claim "same interface" rested on a hand copy nobody diffed).  The real header's declarations are committed as
+    tests/golden/route_b_reference_declarations.json (sha256 of each normalised parameter list, line range; written by
+    scripts/make_golden_route_b.py from the reference tree)."""
+    with open(os.path.join(ROOT, "tests", "golden", "route_b_reference_declarations.json")) as f:
+        golden = json.load(f)["declarations"]
+    theirs = {name: (d["params_sha256"], *d["lines"]) for name, d in golden.items()}
     mine_text = open(os.path.join(RB, "badslam", "kernels.h")).read()
-    theirs, mine = _declarations(open(ref).read()), _declarations(mine_text)
+    mine = _declarations(mine_text)
     assert len(mine) >= 18 and set(mine) <= set(theirs), set(mine) - set(theirs)
     for name, (params, _, _) in sorted(mine.items()):
-        assert params == theirs[name][0], (name, params, theirs[name][0])
+        assert hashlib.sha256(params.encode()).hexdigest() == theirs[name][0], (name, params)
     # the PCG entry points and everything DirectBA's two schemes call are covered
     for needed in ("PCGInitCUDA", "PCGInit2CUDA", "PCGStep1CUDA", "PCGStep2CUDA", "PCGStep3CUDA", "UpdateSurfelsFromPCGDeltaCUDA",
                    "UpdateCFactorsFromPCGDeltaCUDA", "OptimizeGeometryIterationCUDA", "AccumulatePoseEstimationCoeffsCUDA", "OptimizeIntrinsicsCUDA"):
