@@ -89,6 +89,7 @@ SIGNATURES = {
     "bahip_context_set_allreduce": (C.c_int, [C.c_void_p, ALLREDUCE_FN, C.c_void_p]),
     "bahip_context_set_keyframe_sharding": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "bahip_context_set_sum_classes": (C.c_int, [C.c_void_p, C.c_int]),
+    "bahip_context_set_intrinsics_sum_classes": (C.c_int, [C.c_void_p, C.c_int]),
     "bahip_context_set_creation_order": (C.c_int, [C.c_void_p, C.c_int]),
     "bahip_host_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "bahip_host_free": (C.c_int, [C.c_void_p]),
@@ -186,6 +187,7 @@ SIGNATURES = {
     "bahip_debug_set_intrinsics_bin_capacity": (C.c_int, [C.c_void_p, C.c_int]),
     "bahip_debug_intrinsics_bin_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "bahip_debug_set_intrinsics_slices": (C.c_int, [C.c_void_p, C.c_int]),
+    "bahip_debug_read_intrinsics_sums": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bahip_exchange_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_int]),
     "bahip_debug_exact_sum": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "bahip_debug_count_pairs": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.POINTER(C.c_uint64)]),

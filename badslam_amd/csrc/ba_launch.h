@@ -174,7 +174,9 @@ int intrinsics_bin_count(const Intrinsics& in, int* bins_x_out);
 size_t intrinsics_bin_record_bytes();
 void launch_intrinsics_accumulate(hipStream_t st, bool depth, bool color, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                                   const SurfelsView& s, double* glob, double* cells, const IntrBins& bins, const uint32_t* sched,
-                                  uint32_t position_begin = 0, uint32_t position_count = 0 /* 0: all positions of the schedule */);
+                                  uint32_t position_begin = 0, uint32_t position_count = 0 /* 0: all positions of the schedule */,
+                                  int classes = 1 /* the global sums' keyframe classes (bahip_context_set_intrinsics_sum_classes) */,
+                                  int kf_rank = 0, int kf_world = 1 /* keyframe sharding: the sweep visits this rank's classes only */);
 uint32_t intrinsics_sweep_positions(uint32_t surfels, const uint32_t* sched);   // positions of a full sweep (what the slices cut)
 void launch_intrinsics_bin_reduce(hipStream_t st, bool depth, const Intrinsics& in, const SurfelsView& s, double* cells, const IntrBins& bins);
 void set_intrinsics_reduce_form(int form);   // 0: LDS table of ds_add_f64, 1: records sorted by cell in LDS, sums in registers
@@ -342,7 +344,7 @@ hipError_t launch_compact(hipStream_t st, const SurfelsView& s, uint32_t* invali
   /* kernels_intrinsics.hip */                                                                                                                \
   void launch_intrinsics_accumulate(hipStream_t st, bool depth, bool color, const Intrinsics& in, const KfEntry* kfs, int num_kfs,            \
                                     const SurfelsView& s, double* glob, double* cells, const IntrBins& bins, const uint32_t* sched,           \
-                                    uint32_t position_begin, uint32_t position_count);                                                        \
+                                    uint32_t position_begin, uint32_t position_count, int classes, int kf_rank, int kf_world);                \
   /* kernels_pcg.hip */                                                                                                                       \
   void launch_pcg_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,         \
                        const SurfelsView& s, float* r, float* M, uint32_t* tile_cost, const uint32_t* sched);                                 \

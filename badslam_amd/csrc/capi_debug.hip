@@ -233,6 +233,21 @@ int bahip_debug_set_intrinsics_slices(bahip_context* ctx, int slices) {
   ctx->intr_slices_forced = slices > 0 ? std::min(slices, kIntrMaxSlices) : 0;
   return 0;
 }
+int bahip_debug_read_intrinsics_sums(bahip_context* ctx, float out[34], float* cells_out) {
+  REQUIRE(out != nullptr, "bahip_debug_read_intrinsics_sums: NULL argument");
+  REQUIRE(ctx->intr_sums_cells >= 0 && ctx->intr_scratch, "bahip_debug_read_intrinsics_sums: no intrinsics step has left its sums");
+  // the binary64 accumulators after the exchange (capi_solvers.hip: glob_d, cells_d), rounded like intrinsics_finish_kernel /
+  // intrinsics_schur_kernel round them (round to nearest even)
+  const size_t cells = 8 * (size_t)ctx->intr_sums_cells;
+  std::vector<double> host(64 + (cells_out ? cells : 0));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipMemcpy(host.data(), ctx->intr_scratch, sizeof(double) * host.size(), hipMemcpyDeviceToHost));
+  for (int q = 0; q < 34; ++q) out[q] = (float)host[q];
+  if (cells_out)
+    for (size_t e = 0; e < cells; ++e) cells_out[e] = (float)host[64 + e];
+  return 0;
+}
+
 int bahip_debug_intrinsics_bin_stats(bahip_context* ctx, uint32_t* capacity_out, uint32_t* most_out, uint64_t* total_out) {
   uint32_t most = 0; uint64_t total = 0;
   for (size_t b = 0; b < (size_t)ctx->intr_bin_count * (size_t)std::max(ctx->intr_bin_rows, 0) && ctx->intr_bin_counts_host; ++b) {

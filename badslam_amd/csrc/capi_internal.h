@@ -199,6 +199,8 @@ struct bahip_context {
   int kf_rank = 0, kf_world = 1;   // keyframe sharding (bahip_context_set_keyframe_sharding): keyframe k lives on rank k % kf_world (1, 2, 4 or 8)
   int arithmetic = 0;              // BAHIP_ARITHMETIC_EXACT / _FAST: flavour of the sweeps (bahip_context_set_arithmetic), mirrored in in.fast_math
   int sum_classes = 4;             // interleaved partial sums per surfel of the normals / geometry passes: 4 or 8 (bahip_context_set_sum_classes)
+  int intrinsics_sum_classes = 1;  // keyframe classes of the intrinsics step's global sums: 1, 2, 4 or 8 (bahip_context_set_intrinsics_sum_classes)
+  int intr_sums_cells = -1;        // sparse cells of the accumulators the last intrinsics step left in intr_scratch (-1: none; bahip_debug_read_intrinsics_sums)
   float* kf_partials = nullptr;    // class partials of the geometry step (normals, then position) / hit words of the activation
   size_t kf_partials_capacity = 0; // floats
   long long exchange_calls = 0;    // sums over the ranks requested since the last reset (bahip_exchange_stats), and their bytes

@@ -8,12 +8,20 @@ using namespace bahip_capi;
 extern "C" {
 int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimize_color, const bahip_surfels* surfels,
                               bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a) {
-  REQUIRE_NO_KF_SHARDING("bahip_optimize_intrinsics");
+  if (kf_sharded(ctx)) {
+    // a rank sweeps whole classes of the global sums (kernels_intrinsics.hip: "DEFINITION"); the per-cell sums need nothing
+    REQUIRE(is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator");
+    REQUIRE(ctx->kf_world <= ctx->intrinsics_sum_classes,
+            "keyframe sharding of the intrinsics step needs at least as many keyframe classes of its global sums as ranks: "
+            "bahip_context_set_intrinsics_sum_classes (on the single-GPU run it is compared with as well: the class count is part of the "
+            "sums' definition)");
+  }
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
   REQUIRE(optimize_depth || optimize_color, "at least one of depth / colour intrinsics must be optimised");  // :55
   *out_color_camera = ctx->color_cam;
   *out_depth_camera = ctx->depth_cam;
   *out_a = ctx->dp.a;
+  ctx->intr_sums_cells = -1;
   if (surfels->surfels_size == 0 && !is_sharded(ctx)) return 0;   // a rank with an empty shard still takes part in the exchange
   const int S = ctx->in.cf_width * ctx->in.cf_height;
   if (S > ctx->intr_capacity) {
@@ -91,7 +99,8 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
   if (slices == 1) {
     if (bins.capacity) HIP_TRY(hipMemsetAsync(bins.cursors, 0, sizeof(uint32_t) * (size_t)num_bins, st));
     timer_begin(ctx, 6, true);
-    launch_intrinsics_accumulate(st, optimize_depth != 0, optimize_color != 0, ctx->in, ctx->dev_kfs, ctx->num_kfs, sv, glob_d, cells_d, bins, sched);
+    launch_intrinsics_accumulate(st, optimize_depth != 0, optimize_color != 0, ctx->in, ctx->dev_kfs, ctx->num_kfs, sv, glob_d, cells_d, bins, sched,
+                                 0, 0, ctx->intrinsics_sum_classes, ctx->kf_rank, ctx->kf_world);
     timer_end(ctx, 6);
     timer_begin(ctx, 7, true);
     launch_intrinsics_bin_reduce(st, optimize_depth != 0, ctx->in, sv, cells_d, bins);
@@ -121,7 +130,7 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
       if (p >= 2) HIP_TRY(hipStreamWaitEvent(st, reduced[set], 0));
       if (mine.capacity) HIP_TRY(hipMemsetAsync(mine.cursors, 0, sizeof(uint32_t) * (size_t)num_bins, st));
       launch_intrinsics_accumulate(st, true, optimize_color != 0, ctx->in, ctx->dev_kfs, ctx->num_kfs, sv, glob_d, cells_d, mine, sched,
-                                   (uint32_t)p * per_slice, per_slice);
+                                   (uint32_t)p * per_slice, per_slice, ctx->intrinsics_sum_classes, ctx->kf_rank, ctx->kf_world);
       CHECK_LAUNCH();
       HIP_TRY(hipEventRecord(swept[set], st));
       HIP_TRY(hipStreamWaitEvent(aux, swept[set], 0));
@@ -136,6 +145,7 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
     timer_end(ctx, 6);   // (sweeps and reductions together: the reductions have no events of their own on this stream)
   }
   if (reduce_over_ranks(ctx, glob_d, 64 + 8 * (size_t)S, BAHIP_SUM_F64)) return 1;
+  ctx->intr_sums_cells = S;
   launch_intrinsics_finish(ctx->stream, optimize_depth != 0, S, glob_d, cells_d, glob, cells, partials);
   CHECK_LAUNCH();
   timer_end(ctx, 4);   // the sweep and the Schur complement; the 5x5 / 4x4 solves and the cfactor update that follow are tiny

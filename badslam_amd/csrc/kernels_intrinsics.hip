@@ -94,12 +94,15 @@ constexpr int kIntrRegSums = 34 - kIntrLdsSums;
 
 // ---- the sweep: compiled once per arithmetic flavour (ba_launch.h) ----------------------------------------------------------------
 BAHIP_FLAVOURED_BEGIN
-template <bool kDepth, bool kColor>
+// kClassed: the global sums over `classes` interleaved keyframe classes (see "DEFINITION" above), of which this rank visits those with
+// bit c of `owned` set; !kClassed: one class, every keyframe -- the kernel as it is without the class loop (classes / owned unused).
+template <bool kDepth, bool kColor, bool kClassed>
 __global__ void __launch_bounds__(kIntrSweepBlock) __attribute__((amdgpu_waves_per_eu(BAHIP_INTR_WAVES_PER_EU)))
 intrinsics_accumulate_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s,
                              double* __restrict__ glob /* 34 */, double* __restrict__ cells /* S records of kCellFloats */, IntrBins bins,
                              const uint32_t* __restrict__ sched, uint32_t padded_tiles, uint32_t position_begin /* the launch covers the
-                             positions [position_begin, position_begin + gridDim.x) of the schedule: a slice of the sweep */) {
+                             positions [position_begin, position_begin + gridDim.x) of the schedule: a slice of the sweep */,
+                             int classes, uint32_t owned) {
   __shared__ float xpose[64 * (kCellFloats + 1)];   // lane-major: 8 values + the cell index, stride 9 (conflict-free both ways)
   uint32_t tile;   // heavy work first (wave_cull.h: scheduled_tile)
   if (!scheduled_tile(blockIdx.x + position_begin, padded_tiles, sched, &tile)) return;
@@ -204,9 +207,8 @@ intrinsics_accumulate_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int
     }
   };
 
-  for_each_candidate(
-      num_kfs, [&](int k) { return sphere_may_project_item(in, kfs[k].pose.F, wb); },
-      [&](int k) {
+  const auto visible = [&](int k) { return sphere_may_project_item(in, kfs[k].pose.F, wb); };
+  const auto candidate = [&](int k) {
         const KfEntry& kf = kfs[k];
         const float* F = kf.pose.F;
         const Projected p = project_surfel(in, F, gp);
@@ -278,30 +280,65 @@ intrinsics_accumulate_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int
           }
         }
         reserve_pending();
-      });
-  flush_pending();
-
-  float mine = 0.f;
+      };
+  // the tile's xor butterfly of every sum, added to the binary64 totals
+  const auto fold_sums = [&]() {
+    float mine = 0.f;
 #pragma unroll
-  for (int q = 0; q < 34; ++q) {
-    const float v = wave_sum(sum_value(q));
-    if (lane == q) mine = v;
+    for (int q = 0; q < 34; ++q) {
+      const float v = wave_sum(sum_value(q));
+      if (lane == q) mine = v;
+    }
+    if (lane < 34 && mine != 0.f) unsafeAtomicAdd(&glob[lane], (double)mine);
+  };
+  if constexpr (!kClassed) {
+    for_each_candidate(num_kfs, visible, candidate);
+    flush_pending();
+    fold_sums();
+    return;
   }
-  if (lane < 34 && mine != 0.f) unsafeAtomicAdd(&glob[lane], (double)mine);
+  // class by class (wave-uniform): a binary32 chain per surfel over the class's keyframes, the butterfly, the per-lane sums reset
+  // (the per-cell records of the class's last candidate go out first: nothing of the sweep but the sums is live in the butterfly)
+  for (int c = 0; c < classes; ++c) {
+    if (!((owned >> c) & 1u)) continue;   // another rank holds this class's images
+    for_each_candidate(num_kfs, visible, candidate, classes, c);
+    flush_pending();
+    fold_sums();
+#pragma unroll
+    for (int q = 0; q < kIntrRegSums; ++q) reg_sums[q] = 0.f;
+#pragma unroll
+    for (int q = 0; q < kIntrLdsSums; ++q) lds_sums[q * 64 + lane] = 0.f;
+  }
 }
 
 // positions [position_begin, position_begin + position_count) of the sweep's schedule (position_count == 0: all of them)
+template <bool kClassed>
+static void launch_intrinsics_sweep(hipStream_t st, bool depth, bool color, dim3 grid, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
+                                    const SurfelsView& s, double* glob, double* cells, const IntrBins& bins, const uint32_t* sched,
+                                    uint32_t padded, uint32_t position_begin, int classes, uint32_t owned) {
+  const dim3 block(kIntrSweepBlock);
+  if (depth && color)
+    hipLaunchKernelGGL((intrinsics_accumulate_kernel<true, true, kClassed>), grid, block, 0, st, in, kfs, num_kfs, s, glob, cells, bins, sched, padded,
+                       position_begin, classes, owned);
+  else if (depth)
+    hipLaunchKernelGGL((intrinsics_accumulate_kernel<true, false, kClassed>), grid, block, 0, st, in, kfs, num_kfs, s, glob, cells, bins, sched, padded,
+                       position_begin, classes, owned);
+  else
+    hipLaunchKernelGGL((intrinsics_accumulate_kernel<false, true, kClassed>), grid, block, 0, st, in, kfs, num_kfs, s, glob, cells, bins, sched, padded,
+                       position_begin, classes, owned);
+}
 void launch_intrinsics_accumulate(hipStream_t st, bool depth, bool color, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                                   const SurfelsView& s, double* glob, double* cells, const IntrBins& bins, const uint32_t* sched,
-                                  uint32_t position_begin, uint32_t position_count) {
+                                  uint32_t position_begin, uint32_t position_count, int classes, int kf_rank, int kf_world) {
   if (!s.size) return;
   const uint32_t padded = xcd_padded_tiles((s.size + kIntrSweepBlock - 1) / kIntrSweepBlock), positions = sched_positions(padded, sched);
   if (position_begin >= positions) return;
   const uint32_t count = position_count ? std::min(position_count, positions - position_begin) : positions - position_begin;
-  const dim3 grid(count), block(kIntrSweepBlock);
-  if (depth && color) hipLaunchKernelGGL((intrinsics_accumulate_kernel<true, true>), grid, block, 0, st, in, kfs, num_kfs, s, glob, cells, bins, sched, padded, position_begin);
-  else if (depth) hipLaunchKernelGGL((intrinsics_accumulate_kernel<true, false>), grid, block, 0, st, in, kfs, num_kfs, s, glob, cells, bins, sched, padded, position_begin);
-  else hipLaunchKernelGGL((intrinsics_accumulate_kernel<false, true>), grid, block, 0, st, in, kfs, num_kfs, s, glob, cells, bins, sched, padded, position_begin);
+  // class c lives on rank c % kf_world (both counts powers of two, kf_world <= classes: the caller checks)
+  uint32_t owned = 0;
+  for (int c = 0; c < classes; ++c) if ((c & (kf_world - 1)) == kf_rank) owned |= 1u << c;
+  if (classes == 1) launch_intrinsics_sweep<false>(st, depth, color, dim3(count), in, kfs, num_kfs, s, glob, cells, bins, sched, padded, position_begin, 1, owned);
+  else launch_intrinsics_sweep<true>(st, depth, color, dim3(count), in, kfs, num_kfs, s, glob, cells, bins, sched, padded, position_begin, classes, owned);
 }
 BAHIP_FLAVOURED_END
 
@@ -310,8 +347,9 @@ BAHIP_FLAVOURED_END
 namespace bahip {
 void launch_intrinsics_accumulate(hipStream_t st, bool depth, bool color, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                                   const SurfelsView& s, double* glob, double* cells, const IntrBins& bins, const uint32_t* sched,
-                                  uint32_t position_begin, uint32_t position_count) {
-  BAHIP_PICK(in, launch_intrinsics_accumulate(st, depth, color, in, kfs, num_kfs, s, glob, cells, bins, sched, position_begin, position_count));
+                                  uint32_t position_begin, uint32_t position_count, int classes, int kf_rank, int kf_world) {
+  BAHIP_PICK(in, launch_intrinsics_accumulate(st, depth, color, in, kfs, num_kfs, s, glob, cells, bins, sched, position_begin, position_count, classes,
+                                              kf_rank, kf_world));
 }
 
 // The records of one slice of one block's append buffer, added into a table in LDS and from there into the global per-cell

@@ -218,6 +218,7 @@ void DirectBA::SetSurfelSharding(int rank, int world, u32 chunk) {
 }
 
 void DirectBA::SetSumClasses(int classes) { BAHIP_CHECKED_CALL(bahip_context_set_sum_classes(ctx_, classes)); }
+void DirectBA::SetIntrinsicsSumClasses(int classes) { BAHIP_CHECKED_CALL(bahip_context_set_intrinsics_sum_classes(ctx_, classes)); }
 void DirectBA::SetFastArithmetic(bool enabled) { BAHIP_CHECKED_CALL(bahip_context_set_arithmetic(ctx_, enabled ? BAHIP_ARITHMETIC_FAST : BAHIP_ARITHMETIC_EXACT)); }
 void DirectBA::SetRowMajorCreation(bool enabled) { BAHIP_CHECKED_CALL(bahip_context_set_creation_order(ctx_, enabled ? 1 : 0)); }
 
@@ -411,8 +412,8 @@ void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsi
   }
   last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = 0;
   if (keyframe_shard_world_ > 1)
-    CHECK(!use_pcg && !optimize_depth_intrinsics && !optimize_color_intrinsics && !do_surfel_updates && !increase_ba_iteration_count)
-        << "keyframe sharding covers the alternating scheme over poses and geometry without surfel updates and end tasks "
+    CHECK(!use_pcg && !do_surfel_updates && !increase_ba_iteration_count)
+        << "keyframe sharding covers the alternating scheme over poses, geometry and intrinsics without surfel updates and end tasks "
            "(their per-surfel sums run over all keyframes in order): use surfel sharding for the rest";
   if (use_pcg) {
     BundleAdjustmentPCG(stream, optimize_depth_intrinsics, optimize_color_intrinsics, do_surfel_updates, optimize_poses,

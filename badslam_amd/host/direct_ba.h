@@ -148,14 +148,18 @@ class DirectBA {
   // Multi-GPU KEYFRAME sharding (bahip_context_set_keyframe_sharding): this object holds ALL surfels; of the keyframes it needs
   // the images of those with (index among the non-deleted keyframes) % world == rank only (world = 1, 2, 4, or 8 after
   // SetSumClasses(8)).  Covers the
-  // alternating scheme over poses and geometry -- BundleAdjustment(stream, false, false, /*do_surfel_updates*/ false, ...,
-  // /*use_pcg*/ false, ..., /*increase_ba_iteration_count*/ false) -- and ends with the unsharded run's bits on every rank; the
-  // intrinsics step, the PCG scheme and the surfel lifecycle (end tasks included) are refused.  Needs SetAllReduce or an RCCL
-  // communicator when world > 1.
+  // alternating scheme over poses, geometry and the depth / colour intrinsics -- BundleAdjustment(stream, ..., /*do_surfel_updates*/
+  // false, ..., /*use_pcg*/ false, ..., /*increase_ba_iteration_count*/ false), the intrinsics after SetIntrinsicsSumClasses(c) with
+  // c >= world -- and ends with the unsharded run's bits (same class counts) on every rank; the PCG scheme and the surfel lifecycle
+  // (end tasks included) are refused.  Needs SetAllReduce or an RCCL communicator when world > 1.
   void SetKeyframeSharding(int rank, int world);
   // The per-surfel sums of the normals / geometry passes are defined over 4 (default) or 8 interleaved keyframe classes
   // (bahip_context_set_sum_classes); keyframe sharding over 8 ranks needs 8 -- and so does the single-GPU run it is compared with.
   void SetSumClasses(int classes);
+  // The global sums of the intrinsics step are defined over 1 (default), 2, 4 or 8 keyframe classes
+  // (bahip_context_set_intrinsics_sum_classes); keyframe sharding of that step over `world` ranks needs at least `world` -- and the
+  // single-GPU run it is compared with the same count.
+  void SetIntrinsicsSumClasses(int classes);
   // Ours: new surfels of a keyframe in the reference's row-major append order (B/kernel_create_surfels.cu:357-390) instead of this
   // backend's tile-major one (bahip_context_set_creation_order): the same surfels, the reference's indices -- and therefore the
   // reference's survivors when surfels merge.  Slower sweeps until the next spatial reorder (SetSpatialSortCellSize).

@@ -156,6 +156,18 @@ class Scene:
         """4 (default) or 8 interleaved keyframe classes in the per-surfel sums (bahip_context_set_sum_classes)."""
         capi.check(self.lib.bahip_context_set_sum_classes(self.ctx.handle, int(classes)))
 
+    def set_intrinsics_sum_classes(self, classes):
+        """1 (default), 2, 4 or 8 keyframe classes in the global sums of the intrinsics step (bahip_context_set_intrinsics_sum_classes)."""
+        capi.check(self.lib.bahip_context_set_intrinsics_sum_classes(self.ctx.handle, int(classes)))
+
+    def read_intrinsics_sums(self, with_cells=True):
+        """The last intrinsics step's sums rounded to binary32 (bahip_debug_read_intrinsics_sums): (glob[34], cells[S, 8] or None)."""
+        glob = np.zeros(34, np.float32)
+        cells = np.zeros((self.cf_w * self.cf_h, 8), np.float32) if with_cells else None
+        capi.check(self.lib.bahip_debug_read_intrinsics_sums(self.ctx.handle, glob.ctypes.data_as(C.POINTER(C.c_float)),
+                                                              cells.ctypes.data_as(C.POINTER(C.c_float)) if with_cells else None))
+        return glob, cells
+
     def set_keyframe_sharding(self, rank, world):
         """Keyframe k lives on rank k % world (bahip_context_set_keyframe_sharding); bind_keyframes then hands over the
         images of this rank's keyframes only (null pointers for the others: the backend must not look at them)."""

@@ -123,16 +123,25 @@ int bahip_context_set_allreduce(bahip_context* ctx, bahip_allreduce_fn fn, void*
  *     exchanges of the class partials (bit patterns as BAHIP_SUM_I64: 4 x 5 and 4 x 8 binary32 values per surfel);
  *   - bahip_estimate_keyframe_poses* sweep this rank's keyframes, sum the fixed-point normal equations over the ranks
  *     (K x 56 int64 per Gauss-Newton round, the exchange surfel sharding makes too) and solve every pose on every rank;
- *   - everything ends with the bits of the unsharded run on every rank.
- * The intrinsics step, the PCG scheme and the surfel lifecycle are refused in this mode (their per-surfel chains run over all
- * keyframes in order; use surfel sharding).  A hook or an RCCL communicator must be installed when world > 1.  Surfel and
- * keyframe sharding exclude each other on one context. */
+ *   - bahip_optimize_intrinsics sweeps this rank's classes of the global sums' keyframe classes (world must not exceed the count
+ *     of bahip_context_set_intrinsics_sum_classes) and sums the binary64 accumulators over the ranks (BAHIP_SUM_F64, 64 + 8 S
+ *     doubles, the exchange surfel sharding makes too); every rank solves the same 5 x 5 / 4 x 4 systems and cfactor cells;
+ *   - everything ends with the bits of the unsharded run (with the same class counts) on every rank.
+ * The PCG scheme and the surfel lifecycle are refused in this mode (their per-surfel chains run over all keyframes in order; use
+ * surfel sharding).  A hook or an RCCL communicator must be installed when world > 1.  Surfel and keyframe sharding exclude each
+ * other on one context. */
 int bahip_context_set_keyframe_sharding(bahip_context* ctx, int rank, int world);
 /* The number of interleaved partial sums (keyframe classes) the per-surfel sums of the normals and geometry passes are DEFINED
  * over: 4 (default) or 8.  In exact arithmetic both are the reference's sum (B/kernel_opt_geometry.cu: keyframe after keyframe);
  * in binary32 they differ in the last bits like any reordering.  The oracle takes the same parameter (orc_set_sum_classes), and
  * both class counts are held against it bit for bit.  Takes effect at once (no re-binding needed). */
 int bahip_context_set_sum_classes(bahip_context* ctx, int classes);
+/* The number of keyframe classes C the 34 global sums of the intrinsics step (A, b1, colour H, colour b) are DEFINED over: 1
+ * (default), 2, 4 or 8.  Keyframe k (bound index) belongs to class k % C; per surfel and class a binary32 chain over the class's
+ * keyframes in ascending order, per 64-surfel tile and class the xor butterfly, then binary64 over all (tile, class) values
+ * (kernels_intrinsics.hip).  C = 1 is the one chain over all keyframes.  Keyframe sharding over `world` ranks needs C >= world, and
+ * the single-GPU run it is compared with the same C.  The per-cell sums do not depend on it.  Takes effect with the next step. */
+int bahip_context_set_intrinsics_sum_classes(bahip_context* ctx, int classes);
 /* Order in which the surfels a keyframe creates are appended: 0 (default) = by tiles of 8 x 8 sparse cells of the creating
  * keyframe, row-major inside a tile -- the 64 surfels of a wavefront form a compact patch, which is what the sweeps' culling wants;
  * 1 = row-major over the whole image, the reference's order (B/kernel_create_surfels.cu:357-390).  The same surfels either way;
@@ -538,6 +547,11 @@ int bahip_debug_read_tile_schedule(bahip_context* ctx, uint32_t* padded_tiles_ou
  * largest / total demand of the last call. */
 int bahip_debug_set_intrinsics_bin_capacity(bahip_context* ctx, int records_per_block);
 int bahip_debug_intrinsics_bin_stats(bahip_context* ctx, uint32_t* capacity_out, uint32_t* most_out, uint64_t* total_out);
+/* The sums of the last bahip_optimize_intrinsics call, after the exchange over the ranks, rounded to binary32 as the step rounds
+ * them before it forms the Schur complement: out[34] the global sums (A 0..14, b1 15..19, colour H 20..29, colour b 30..33),
+ * cells_out (NULL or 8 S floats) the per-cell table {B0..B4, D, b2, observation count} per sparse cell.  These are the sums the
+ * oracle's orc_intrinsics_accumulate defines (the 5 x 5 system adds the Schur complement to the first 20). */
+int bahip_debug_read_intrinsics_sums(bahip_context* ctx, float out[34], float* cells_out);
 /* The intrinsics step's sweep runs in slices of its schedule when the cloud is large (the per-pair records of a slice are reduced on a
  * second stream while the next slice sweeps; two buffer sets of one slice's records each): 1 .. 16 fixes the number of slices (tests on
  * small scenes), 0 = by the size of the sweep (default).  The sums do not depend on it. */
