@@ -90,6 +90,7 @@ SIGNATURES = {
     "bahip_context_set_keyframe_sharding": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "bahip_context_set_sum_classes": (C.c_int, [C.c_void_p, C.c_int]),
     "bahip_context_set_intrinsics_sum_classes": (C.c_int, [C.c_void_p, C.c_int]),
+    "bahip_context_set_pcg_sum_classes": (C.c_int, [C.c_void_p, C.c_int]),
     "bahip_context_set_creation_order": (C.c_int, [C.c_void_p, C.c_int]),
     "bahip_host_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "bahip_host_free": (C.c_int, [C.c_void_p]),

@@ -351,6 +351,14 @@ struct ClassPartials {
   uint32_t stride;   // floats per plane (>= surfels, even: the planes travel as 64-bit integer words)
   uint32_t owned;
 };
+// The keyframe classes of the PCG sweeps' per-surfel chains (bahip_context_set_pcg_sum_classes; kernels_pcg.hip: "DEFINITION of the
+// surfel block"): `classes` of them, the partials of those in cp.owned stored to cp.data with `entries` planes per class -- 2 x
+// geom_stride after PCGInit (r, then M), geom_stride after PCGStep1 (g).
+struct PcgClasses {
+  ClassPartials cp;
+  int classes;
+  int entries;
+};
 
 // A pointer read from a device table (KfEntry::geom, ...) is a generic pointer to the compiler, which then emits flat_load
 // (checked against the LDS / scratch apertures, counted on vmcnt AND lgkmcnt).  Every such pointer here is a hipMalloc

@@ -76,6 +76,10 @@ void launch_geometry_phase(hipStream_t stream, int phase, bool use_depth, bool u
                            const SurfelsView& s, long long activate_count, const ClassPartials& cpn, const ClassPartials& cpp);
 void launch_activation_hits(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, uint32_t surfels_size,
                             int kf_rank, int kf_world, uint32_t* hits);
+// ... and the normals update on its own (bahip_update_surfel_normals): phase 1 stores this rank's class partials (kNormalsSums per class and
+// surfel) to cp, phase 2 takes the normals from the exchanged partials
+constexpr int kNormalsSums = 4;
+void launch_normals_phase(hipStream_t stream, int phase, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, const ClassPartials& cp);
 void launch_activation_from_hits(hipStream_t stream, const SurfelsView& s, uint32_t surfels_size, const uint32_t* hits);
 
 void launch_count_pairs(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,
@@ -202,7 +206,8 @@ PcgExact pcg_exact_view(void* buffer, uint32_t head_count);
 size_t pcg_control_bytes();
 void launch_pcg_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                      const SurfelsView& s, float* r, float* M,
-                     uint32_t* tile_cost = nullptr /* census for the schedule, as in launch_pose_accumulate */, const uint32_t* sched = nullptr);
+                     uint32_t* tile_cost = nullptr /* census for the schedule, as in launch_pose_accumulate */, const uint32_t* sched = nullptr,
+                     const PcgClasses* classes = nullptr /* C > 1 (bahip_context_set_pcg_sum_classes): the surfel entries go to class partials */);
 void launch_pcg_resolve_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, float* r, float* M);
 void launch_pcg_init2(hipStream_t st, const PcgLayout& L, const PcgExact& ex, float a, const float* r, const float* M, float* delta, float* g,
                       float* p);
@@ -210,7 +215,10 @@ void launch_pcg_control_init(hipStream_t st, const PcgExact& ex, void* ctl, floa
 void launch_pcg_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                       const SurfelsView& s, const float* p, float* g, const void* ctl, const uint32_t* sched = nullptr,
                       uint32_t* tile_counters = nullptr /* the context's two sets of eight tile counters: allows the persistent LDS form */,
-                      int* parity_inout = nullptr);
+                      int* parity_inout = nullptr, const PcgClasses* classes = nullptr /* as launch_pcg_init */);
+// the surfel block of r and M (va, vb; ctl NULL: after PCGInit) or of g (va; after PCGStep1, stopped by ctl like the other kernels of a
+// step) from the class partials of `classes`, summed in the defined order (kernels_pcg.hip: "DEFINITION of the surfel block")
+void launch_pcg_class_combine(hipStream_t st, const PcgLayout& L, const PcgClasses& classes, uint32_t surfels, float* va, float* vb, const void* ctl);
 void set_pcg_lds_form(int mode);   // test hook: 0 = always the one-tile-per-wavefront form of the step-1 sweep, 1 = automatic, 2 = the LDS form whenever the table fits
 void launch_pcg_eps_terms(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const float* p);
 void launch_pcg_resolve_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, float* g, float* alpha_d, double eps_repeat, const void* ctl);
@@ -324,6 +332,8 @@ hipError_t launch_compact(hipStream_t st, const SurfelsView& s, uint32_t* invali
                              int num_kfs, const SurfelsView& s, long long activate_count, const ClassPartials& cpn, const ClassPartials& cpp); \
   void launch_activation_hits(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,                \
                               uint32_t surfels_size, int kf_rank, int kf_world, uint32_t* hits);                                              \
+  void launch_normals_phase(hipStream_t stream, int phase, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,      \
+                            const ClassPartials& cp);                                                                                         \
   void set_tile_waves(int waves);                                                                                                             \
   long long geometry_hybrid_launches();                                                                                                       \
   /* kernels_pose.hip */                                                                                                                      \
@@ -347,10 +357,10 @@ hipError_t launch_compact(hipStream_t st, const SurfelsView& s, uint32_t* invali
                                     uint32_t position_begin, uint32_t position_count, int classes, int kf_rank, int kf_world);                \
   /* kernels_pcg.hip */                                                                                                                       \
   void launch_pcg_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,         \
-                       const SurfelsView& s, float* r, float* M, uint32_t* tile_cost, const uint32_t* sched);                                 \
+                       const SurfelsView& s, float* r, float* M, uint32_t* tile_cost, const uint32_t* sched, const PcgClasses* classes);      \
   void launch_pcg_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,        \
                         const SurfelsView& s, const float* p, float* g, const void* ctl, const uint32_t* sched, uint32_t* tile_counters,      \
-                        int* parity_inout);                                                                                                   \
+                        int* parity_inout, const PcgClasses* classes);                                                                        \
   void set_pcg_lds_form(int mode);                                                                                                            \
   void pcg_step1_form_launches(long long out[2]);
 namespace exact { BAHIP_FLAVOURED_DECLARATIONS }

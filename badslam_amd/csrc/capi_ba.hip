@@ -214,7 +214,26 @@ int bahip_assign_colors(bahip_context* ctx, const bahip_surfels* surfels) {
 int bahip_update_surfel_normals(bahip_context* ctx, const bahip_surfels* surfels) {
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
   REQUIRE(surfels->active != nullptr, "normals update needs the active-surfel buffer");
-  REQUIRE_NO_KF_SHARDING("bahip_update_surfel_normals (a stage of the PCG scheme)");
+  if (kf_sharded(ctx)) {
+    // as the normals pass of the keyframe-sharded geometry step: this rank's class partials, summed over the ranks, combined
+    REQUIRE(is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator");
+    REQUIRE(ctx->kf_world <= ctx->sum_classes, "keyframe sharding of the normals update needs at least as many classes of the per-surfel sums as "
+                                               "ranks: bahip_context_set_sum_classes");
+    const SurfelsView v = make_view(surfels);
+    if (v.size == 0) return 0;
+    const size_t stride = ((size_t)v.size + 63) & ~(size_t)63, floats = (size_t)ctx->sum_classes * kNormalsSums * stride;
+    if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, floats, 0, "the class partials of the normals update")) return 1;
+    const ClassPartials cp{ctx->kf_partials, (uint32_t)stride, owned_classes(ctx, ctx->sum_classes)};
+    HIP_TRY(hipMemsetAsync(ctx->kf_partials, 0, sizeof(float) * floats, ctx->stream));
+    launch_normals_phase(ctx->stream, 1, ctx->in, ctx->dev_kfs, ctx->num_kfs, v, cp);
+    CHECK_LAUNCH();
+    if (reduce_over_ranks(ctx, cp.data, floats / 2, BAHIP_SUM_I64))
+      return fail((std::string("keyframe sharding: the exchange of the normals update's class partials failed: ") + g_last_error).c_str(),
+                  __FILE__, __LINE__);
+    launch_normals_phase(ctx->stream, 2, ctx->in, ctx->dev_kfs, ctx->num_kfs, v, cp);
+    CHECK_LAUNCH();
+    return 0;
+  }
   launch_normals(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels));
   CHECK_LAUNCH();
   return 0;

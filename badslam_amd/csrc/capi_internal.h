@@ -200,6 +200,7 @@ struct bahip_context {
   int arithmetic = 0;              // BAHIP_ARITHMETIC_EXACT / _FAST: flavour of the sweeps (bahip_context_set_arithmetic), mirrored in in.fast_math
   int sum_classes = 4;             // interleaved partial sums per surfel of the normals / geometry passes: 4 or 8 (bahip_context_set_sum_classes)
   int intrinsics_sum_classes = 1;  // keyframe classes of the intrinsics step's global sums: 1, 2, 4 or 8 (bahip_context_set_intrinsics_sum_classes)
+  int pcg_sum_classes = 1;         // keyframe classes of the surfel block of the PCG scheme's r, M and g: 1, 2, 4 or 8 (bahip_context_set_pcg_sum_classes)
   int intr_sums_cells = -1;        // sparse cells of the accumulators the last intrinsics step left in intr_scratch (-1: none; bahip_debug_read_intrinsics_sums)
   float* kf_partials = nullptr;    // class partials of the geometry step (normals, then position) / hit words of the activation
   size_t kf_partials_capacity = 0; // floats
@@ -274,6 +275,12 @@ int reduce_over_ranks(bahip_context* ctx, void* buffer, size_t count, int dtype)
 void rccl_destroy_communicator(bahip_context* ctx);   // (context destruction)
 inline bool is_sharded(const bahip_context* ctx) { return ctx->allreduce != nullptr || ctx->rccl_comm != nullptr; }
 inline bool kf_owned(const bahip_context* ctx, int k) { return (k & (ctx->kf_world - 1)) == ctx->kf_rank; }
+// owned[c]: this rank sweeps keyframe class c of `classes` -- class c lives on rank c % kf_world (both powers of two, kf_world <= classes)
+inline uint32_t owned_classes(const bahip_context* ctx, int classes) {
+  uint32_t owned = 0;
+  for (int c = 0; c < classes; ++c) if ((c & (ctx->kf_world - 1)) == ctx->kf_rank) owned |= 1u << c;
+  return owned;
+}
 #define REQUIRE_NO_KF_SHARDING(what) \
   REQUIRE(!kf_sharded(ctx), what " is not available under keyframe sharding (its per-surfel sums run over all keyframes in order): use surfel sharding")
 

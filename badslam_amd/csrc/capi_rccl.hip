@@ -95,6 +95,13 @@ int bahip_context_set_intrinsics_sum_classes(bahip_context* ctx, int classes) {
   return 0;
 }
 
+int bahip_context_set_pcg_sum_classes(bahip_context* ctx, int classes) {
+  REQUIRE(classes == 1 || classes == 2 || classes == 4 || classes == 8,
+          "the surfel block of the PCG scheme's r, M and g is defined over 1, 2, 4 or 8 keyframe classes");
+  ctx->pcg_sum_classes = classes;
+  return 0;
+}
+
 int bahip_context_set_keyframe_sharding(bahip_context* ctx, int rank, int world) {
   REQUIRE(world == 1 || world == 2 || world == 4 || world == 8, "keyframe sharding: world must be 1, 2, 4 or 8 (a rank holds whole keyframe classes)");
   REQUIRE(world <= ctx->sum_classes, "keyframe sharding over 8 ranks needs the 8-class definition of the per-surfel sums: bahip_context_set_sum_classes(ctx, 8) "

@@ -219,7 +219,16 @@ static int ensure_pcg_exact(bahip_context* ctx, uint32_t head_count) {
 int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const bahip_surfels* surfels,
                         bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a, int* inner_steps_out,
                         int* num_converged_out) {
-  REQUIRE_NO_KF_SHARDING("bahip_pcg_iteration");
+  const bool kf = kf_sharded(ctx);
+  if (kf) {
+    // a rank sweeps whole keyframe classes of the surfel block's chains (kernels_pcg.hip: "DEFINITION of the surfel block"); the dense
+    // head is exact and splits over the ranks as it does under surfel sharding
+    REQUIRE(is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator");
+    REQUIRE(ctx->kf_world <= ctx->pcg_sum_classes,
+            "keyframe sharding of the PCG scheme needs at least as many keyframe classes of its surfel block as ranks: "
+            "bahip_context_set_pcg_sum_classes (on the single-GPU run it is compared with as well: the class count is part of the "
+            "definition)");
+  }
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
   const bool sharded = is_sharded(ctx);   // (exact sums need no rank count: every rank adds its terms, the limbs are summed)
   ctx->pcg_stage_head = 0xffffffffu;      // the accumulators are re-used: a stage-by-stage caller has to call bahip_pcg_begin again
@@ -252,7 +261,9 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
   if (inner_steps_out) *inner_steps_out = 0;
   if (num_converged_out) *num_converged_out = 0;
 
-  if (U == 0 && !sharded) {   // nothing to solve for (e.g. one keyframe = the gauge, no surfels): every pose counts as converged
+  // nothing to solve for (e.g. one keyframe = the gauge, no surfels): every pose counts as converged (under keyframe sharding every rank
+  // has the whole unknown vector, so all return here alike)
+  if (U == 0 && (!sharded || kf)) {
     if (num_converged_out) *num_converged_out = K;
     return 0;
   }
@@ -280,12 +291,52 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
   const size_t x1_step = ((size_t)kHotExchanged1 * kHotReplicas + (size_t)head_count) * kExactLimbs;
   const size_t x2 = ((size_t)kHotReplicas + 1) * kExactLimbs;   // the sticky flag's cell + slot 20, from ex.invalid on
   void* const x2_from = ex.invalid;
+  // Keyframe sharding: the unknown vectors are replicated, not sharded -- every rank holds all of r, M, delta, g and p, and the
+  // per-unknown kernels add the same surfel-block terms on every rank.  Those (the epsilon terms of alpha_d over the local unknowns,
+  // slot kHotEpsLocal, which exchange 1 carries, and the dot products over them, slot kHotDotLocal, which exchange 2 carries) must
+  // count once: the ranks other than 0 clear their copy before the exchange.  The sticky flag still travels in exchange 2.
+  ExactCell* const eps_local = ex.hot + (size_t)kHotEpsLocal * kHotReplicas;
+  ExactCell* const dot_local = ex.hot_tail;   // (slot kHotDotLocal = kHotExchanged1: the first of the tail)
+  const bool count_replicated = !kf || ctx->kf_rank == 0;
+  // C > 1 (and always under keyframe sharding): the sweeps visit this rank's classes and store the chains of the surfel entries to
+  // class partials -- [class][entry][surfel], 2 x geom_stride entries after PCGInit, geom_stride after PCGStep1 --, zero for the
+  // classes of other ranks; they are summed over the ranks as 64-bit integers (bit patterns: x + 0 keeps every bit) and combined
+  const int classes = ctx->pcg_sum_classes;
+  const bool classed = classes > 1;
+  PcgClasses pc{};
+  size_t class_floats = 0;
+  if (classed) {
+    const size_t stride = ((size_t)N + 63) & ~(size_t)63;
+    pc.classes = classes;
+    pc.cp.stride = (uint32_t)stride;
+    pc.cp.owned = owned_classes(ctx, classes);
+    if (L.optimize_geometry && N > 0) {
+      class_floats = (size_t)classes * 2 * L.geom_stride * stride;
+      if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, class_floats, 0, "the class partials of the PCG scheme")) return 1;
+      pc.cp.data = ctx->kf_partials;
+    }
+  }
+  // the partials of one sweep: cleared before it, summed over the ranks and combined after it
+  auto class_sweep_begin = [&](int entries) -> int {
+    pc.entries = entries;
+    if (class_floats) HIP_TRY(hipMemsetAsync(pc.cp.data, 0, sizeof(float) * (size_t)classes * entries * pc.cp.stride, st));
+    return 0;
+  };
+  auto class_sweep_end = [&](float* va, float* vb, const void* ctl_) -> int {
+    if (!class_floats) return 0;
+    if (kf && reduce_over_ranks(ctx, pc.cp.data, (size_t)classes * pc.entries * pc.cp.stride / 2, BAHIP_SUM_I64)) return 1;
+    launch_pcg_class_combine(st, L, pc, N, va, vb, ctl_);
+    CHECK_LAUNCH();
+    return 0;
+  };
   // heavy work first (wave_cull.h): the init sweep takes the census when there is no schedule for this grid yet (a PCG-only
   // caller never runs the pose sweep that usually provides it), the inner steps use it
   const uint32_t padded_tiles = pose_padded_tiles(sv.size);
   const bool census = g_tile_order_enabled && sv.size > 0 && ctx->tile_order_tiles != padded_tiles && !ctx->tile_order_unavailable_for(padded_tiles);
   if (census && ensure_tile_schedule(ctx, padded_tiles)) return 1;
-  launch_pcg_init(st, L, ex, ctx->in, ctx->dev_kfs, K, sv, r_, M_, census ? ctx->dev_tile_cost : nullptr, tile_order_for(ctx, sv.size));
+  if (classed && class_sweep_begin(2 * L.geom_stride)) return 1;
+  launch_pcg_init(st, L, ex, ctx->in, ctx->dev_kfs, K, sv, r_, M_, census ? ctx->dev_tile_cost : nullptr, tile_order_for(ctx, sv.size),
+                  classed ? &pc : nullptr);
   CHECK_LAUNCH();
   if (census) {
     if (launch_tile_order(st, ctx->dev_tile_cost, padded_tiles, ctx->dev_tile_order)) {
@@ -298,11 +349,13 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
     }
   }
   const uint32_t* sched = tile_order_for(ctx, sv.size);
-  if (sharded && reduce_over_ranks(ctx, ex.hot, x1_init, BAHIP_SUM_I64)) return 1;
+  if (classed && class_sweep_end(r_, M_, nullptr)) return 1;
+  if (sharded && reduce_over_ranks(ctx, ex.hot, x1_init, BAHIP_SUM_I64)) return 1;   // (slot kHotEpsLocal is still zero here)
   launch_pcg_resolve_init(st, L, ex, r_, M_);
   CHECK_LAUNCH();
   launch_pcg_init2(st, L, ex, ctx->dp.a, r_, M_, delta, g_, p_);
   CHECK_LAUNCH();
+  if (!count_replicated) HIP_TRY(hipMemsetAsync(dot_local, 0, sizeof(ExactCell) * kHotReplicas, st));
   if (sharded && reduce_over_ranks(ctx, x2_from, x2, BAHIP_SUM_I64)) return 1;
 
   // Inner loop: the stopping rule runs on the device (pcg_control_kernel), so steps are queued in groups without a host
@@ -312,20 +365,25 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
   launch_pcg_control_init(st, ex, ctl, sc + i_an);
   CHECK_LAUNCH();
   // AddAlphaDEpsilonTerms runs once per keyframe in the reference (B/kernel_pcg.cu:1102-1112), and not at all without surfels
-  const double eps_repeat = (N > 0 || sharded) ? (double)K : 0.0;
+  // (a surfel shard may be empty where the whole cloud is not; under keyframe sharding N is the whole cloud)
+  const double eps_repeat = (N > 0 || (sharded && !kf)) ? (double)K : 0.0;
   constexpr int kStepsPerGroup = 6;
   int steps = 0;
   for (int step = 0; step < opt->max_inner_iterations; ++step) {
     if (step > 0) { const int t = i_an; i_an = i_bn; i_bn = t; }
+    if (classed && class_sweep_begin(L.geom_stride)) return 1;
     timer_begin(ctx, 5, step == 0);
-    launch_pcg_step1(st, L, ex, ctx->in, ctx->dev_kfs, K, sv, p_, g_, ctl, sched, ctx->dev_tile_counters, &ctx->pose_parity);
+    launch_pcg_step1(st, L, ex, ctx->in, ctx->dev_kfs, K, sv, p_, g_, ctl, sched, ctx->dev_tile_counters, &ctx->pose_parity, classed ? &pc : nullptr);
     timer_end(ctx, 5);
     CHECK_LAUNCH();
+    if (classed && class_sweep_end(g_, nullptr, ctl)) return 1;
+    if (!count_replicated) HIP_TRY(hipMemsetAsync(eps_local, 0, sizeof(ExactCell) * kHotReplicas, st));
     if (sharded && reduce_over_ranks(ctx, ex.hot, x1_step, BAHIP_SUM_I64)) return 1;   // g head, intrinsics entries, alpha_d terms
     launch_pcg_resolve_step1(st, L, ex, g_, sc + 1, eps_repeat, ctl);
     CHECK_LAUNCH();
     launch_pcg_step2(st, L, ex, r_, M_, delta, g_, p_, sc + i_an, sc + 1, ctl);
     CHECK_LAUNCH();
+    if (!count_replicated) HIP_TRY(hipMemsetAsync(dot_local, 0, sizeof(ExactCell) * kHotReplicas, st));
     if (sharded && reduce_over_ranks(ctx, x2_from, x2, BAHIP_SUM_I64)) return 1;
     launch_pcg_control(st, ex, ctl, sc + i_bn);
     CHECK_LAUNCH();
@@ -434,6 +492,8 @@ int stage_keyframe(bahip_context* ctx, const bahip_frame* frame, const float fra
   return 0;
 }
 int stage_ready(bahip_context* ctx, const PcgLayout& L) {
+  REQUIRE(!kf_sharded(ctx), "the PCG stage entry points are not available under keyframe sharding (a caller's per-keyframe calls would chain "
+                            "the surfel entries over one rank's keyframes): use bahip_pcg_iteration");
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
   REQUIRE(ctx->pcg_exact != nullptr && ctx->pcg_stage_head == head_count_of(L), "bahip_pcg_begin was not called for this layout");
   return 0;
@@ -442,7 +502,8 @@ int stage_ready(bahip_context* ctx, const PcgLayout& L) {
 extern "C" {
 
 int bahip_pcg_begin(bahip_context* ctx, const bahip_pcg_layout* layout, uint32_t surfels_size) {
-  REQUIRE_NO_KF_SHARDING("bahip_pcg_begin");
+  REQUIRE(!kf_sharded(ctx), "bahip_pcg_begin: the PCG stage entry points are not available under keyframe sharding (a caller's per-keyframe "
+                            "calls would chain the surfel entries over one rank's keyframes): use bahip_pcg_iteration");
   const PcgLayout L = stage_layout(layout, surfels_size);
   const uint32_t head = head_count_of(L);
   if (ensure_pcg_exact(ctx, head)) return 1;

@@ -22,6 +22,14 @@
 //   - dot products over the unknowns (alpha_n, beta_n, the epsilon terms of alpha_d): the binary32 products, exact.
 // So the conjugate gradient is deterministic, bit-identical to the oracle (inner step count included), independent of the
 // launch shape, and a surfel-sharded run -- limbs exchanged with an int64 all-reduce -- equals the unsharded one bit for bit.
+//
+// DEFINITION of the surfel block of r, M (PCGInit) and g (PCGStep1) over C keyframe classes (bahip_context_set_pcg_sum_classes: 1, 2,
+// 4 or 8; keyframe k of the bound table belongs to class k % C): per surfel entry and class a binary32 chain over the class's keyframes
+// in ascending order, p_c, and the entry is ((p0 + p1) + p2) + ... -- the combination rule of tile_sums in kernels_surfel.hip.  C = 1
+// is the one chain over all keyframes, written by the sweep itself (the kernels without the class loop, kClassed off).  With C > 1 the
+// sweeps (kClassed on) visit the classes a rank owns and store their chains to class partials ([class][entry][surfel], zero for the
+// classes of other ranks); under keyframe sharding the ranks sum the partials as 64-bit integers (x + 0 keeps every bit) and
+// pcg_class_combine_kernel adds them up as defined.  A single GPU with C > 1 takes the same route without the exchange.
 #include "ba_device.h"
 #include "ba_launch.h"
 #include "exact_sum.h"
@@ -54,6 +62,14 @@ __device__ __forceinline__ int intrinsics_slot(const PcgLayout& L, uint32_t u) {
   if (L.optimize_depth_intrinsics && u >= L.depth_intr_start && u < L.depth_intr_start + 5u) return (int)(u - L.depth_intr_start);
   if (L.optimize_color_intrinsics && u >= L.color_intr_start && u < L.color_intr_start + 4u) return 5 + (int)(u - L.color_intr_start);
   return -1;
+}
+// The classes of a kClassed sweep come as its last kernel argument; a sweep without the class loop has no such argument, so its code
+// (kernel arguments included) is that of the one-class definition alone.
+__device__ __forceinline__ PcgClasses pcg_classes_of() { return PcgClasses{}; }
+__device__ __forceinline__ PcgClasses pcg_classes_of(const PcgClasses& c) { return c; }
+// Plane q of class c's partials (kClassed sweeps: the entries of this rank's classes; pcg_class_combine_kernel: all of them).
+__device__ __forceinline__ float* pcg_class_plane(const PcgClasses& pc, int c, int q) {
+  return pc.cp.data + (size_t)(c * pc.entries + q) * pc.cp.stride;
 }
 
 // ---- the exact accumulators of one PCG solve ------------------------------------------------------------------------------
@@ -179,10 +195,15 @@ __device__ __forceinline__ bool gather_and_associate(const PcgLayout& L, const I
 }
 
 // ---- PCGInit: r -= J^T W F, M += diag(J^T W J)  (B/kernel_pcg.cu:179-541) -----------------------------
-template <bool kDepthIntr, bool kColorIntr>
+// kClassed: the surfel entries over the keyframe classes of `classes_arg` (one PcgClasses, see "DEFINITION of the surfel block"),
+// of which the sweep visits the owned ones and stores their chains to the partials (r_ / M_ are not written); !kClassed: one class,
+// every keyframe, the chains written to r_ / M_ -- the kernel as it is without the class loop (no further argument).
+template <bool kDepthIntr, bool kColorIntr, bool kClassed, typename... Classes>
 __global__ void __launch_bounds__(kPcgSweepBlock) BAHIP_PCG_SWEEP_ATTR
 pcg_init_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s,
-                float* __restrict__ r_, float* __restrict__ M_, uint32_t* __restrict__ tile_cost, const uint32_t* __restrict__ sched) {
+                float* __restrict__ r_, float* __restrict__ M_, uint32_t* __restrict__ tile_cost, const uint32_t* __restrict__ sched,
+                Classes... classes_arg) {
+  static_assert(sizeof...(Classes) == (kClassed ? 1 : 0), "a kClassed sweep takes one PcgClasses, the other none");
   uint32_t tile;   // heavy work first (wave_cull.h: scheduled_tile); tile_cost: the census the schedule is built from
   if (!scheduled_tile(blockIdx.x, gridDim.x - (sched ? kHeavySlots : 0u), sched, &tile)) return;
   uint32_t visited = 0;
@@ -199,7 +220,7 @@ pcg_init_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restri
   const int replica = (int)(tile & (kHotReplicas - 1));
   const uint32_t gi = L.optimize_geometry ? (L.surfel_start + (uint32_t)L.geom_stride * ii) : 0u;
   float gr[3] = {0, 0, 0}, gM[3] = {0, 0, 0};     // surfel entries
-  if (L.accumulate && in_range && L.optimize_geometry) {   // per-keyframe calls continue the chain the earlier calls left
+  if (!kClassed && L.accumulate && in_range && L.optimize_geometry) {   // per-keyframe calls continue the chain the earlier calls left
     gr[0] = r_[gi]; gM[0] = M_[gi];
     if (L.geom_stride == 3) { gr[1] = r_[gi + 1]; gM[1] = M_[gi + 1]; gr[2] = r_[gi + 2]; gM[2] = M_[gi + 2]; }
   }
@@ -242,9 +263,8 @@ pcg_init_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restri
       pending_cf = 0xffffffffu;
     }
   };
-  for_each_candidate(
-      num_kfs, [&](int k) { return sphere_may_project_item(in, kfs[k].pose.F, wb); },
-      [&](int k) {
+  const auto may_project = [&](int k) { return sphere_may_project_item(in, kfs[k].pose.F, wb); };
+  const auto candidate = [&](int k) {
         const KfEntry& kf = kfs[k];
         ++visited;
         PairGather pg;
@@ -317,14 +337,38 @@ pcg_init_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restri
           pending_pose = pose_kf;
           pending_base = pose_kf ? kf_pose_index(L, k) : 0u;   // pose unknowns come first: head index == unknown index
         }
-      });
+      };
+  if constexpr (!kClassed) {
+    for_each_candidate(num_kfs, may_project, candidate);
+    flush_pending();
+    if (tile_cost && lane == 0 && visited) atomicAdd(&tile_cost[tile], visited);
+
+    if (in_range && L.optimize_geometry) {
+      r_[gi] = gr[0]; M_[gi] = gM[0];
+      if (L.geom_stride == 3) { r_[gi + 1] = gr[1]; M_[gi + 1] = gM[1]; r_[gi + 2] = gr[2]; M_[gi + 2] = gM[2]; }
+    }
+    return;
+  }
+  // class by class (wave-uniform): the chains of the surfel entries start from zero per class and go to the partials; the dense
+  // head's (tile, keyframe) totals go to the exact accumulators as above (any order: integer sums)
+  const PcgClasses pc = pcg_classes_of(classes_arg...);
+  const int gs = L.geom_stride;
+#pragma nounroll
+  for (int c = 0; c < pc.classes; ++c) {
+    if (!((pc.cp.owned >> c) & 1u)) continue;   // another rank holds this class's images
+    for_each_candidate(num_kfs, may_project, candidate, pc.classes, c);
+    if (in_range && L.optimize_geometry) {
+      pcg_class_plane(pc, c, 0)[i] = gr[0]; pcg_class_plane(pc, c, gs)[i] = gM[0];
+      if (gs == 3) {
+        pcg_class_plane(pc, c, 1)[i] = gr[1]; pcg_class_plane(pc, c, 4)[i] = gM[1];
+        pcg_class_plane(pc, c, 2)[i] = gr[2]; pcg_class_plane(pc, c, 5)[i] = gM[2];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { gr[q] = 0.f; gM[q] = 0.f; }
+  }
   flush_pending();
   if (tile_cost && lane == 0 && visited) atomicAdd(&tile_cost[tile], visited);
-
-  if (in_range && L.optimize_geometry) {
-    r_[gi] = gr[0]; M_[gi] = gM[0];
-    if (L.geom_stride == 3) { r_[gi + 1] = gr[1]; M_[gi + 1] = gM[1]; r_[gi + 2] = gr[2]; M_[gi + 2] = gM[2]; }
-  }
 }
 
 BAHIP_FLAVOURED_END
@@ -427,6 +471,23 @@ pcg_resolve_kernel(PcgLayout L, PcgExact ex, float* __restrict__ va, float* __re
   }
 }
 
+// ---- the surfel block from the class partials (C > 1, see "DEFINITION of the surfel block") ----------------------------------
+// One thread per surfel: entry q = ((p0 + p1) + p2) + ..., classes ascending; entries [0, geom_stride) go to va (r / g), the others
+// to vb (M).  After PCGStep1 it runs only while the inner loop has not stopped, like the resolve kernel.
+__global__ void __launch_bounds__(kPcgBlock)
+pcg_class_combine_kernel(PcgLayout L, PcgClasses pc, uint32_t surfels, float* __restrict__ va, float* __restrict__ vb, const PcgControl* ctl) {
+  if (ctl && ctl->stop) return;
+  const uint32_t i = blockIdx.x * kPcgBlock + threadIdx.x;
+  if (i >= surfels) return;
+  const uint32_t gs = (uint32_t)L.geom_stride, gi = L.surfel_start + gs * i;
+  for (int q = 0; q < pc.entries; ++q) {
+    float t = pcg_class_plane(pc, 0, q)[i];
+    for (int c = 1; c < pc.classes; ++c) t += pcg_class_plane(pc, c, q)[i];
+    if ((uint32_t)q < gs) va[gi + q] = t;
+    else vb[gi + q - gs] = t;
+  }
+}
+
 // ---- exact dot products in the per-unknown kernels -----------------------------------------------------------------------------
 // A thread's terms over the local (surfel) unknowns go into a private column of limbs in workgroup memory (the limb index is
 // data dependent); terms of dense-head unknowns -- few -- go straight to the head's replicated slot with atomics.  At the end
@@ -521,9 +582,11 @@ struct PcgLdsSink {
   __device__ __forceinline__ void add_pose(uint32_t head_index, float v, int part) const { add_cell(head_index, v, part); }
   __device__ __forceinline__ void add_hot(int slot, float v, int part) const { add_cell(pose_cells + pcg_lds_hot_index(slot), v, part); }
 };
-template <bool kDepthIntr, bool kColorIntr, typename Sink>
+// kClassed: as pcg_init_kernel -- the owned classes' chains of the surfel entries of g to the partials of `pc`, g_'s surfel block not written
+template <bool kDepthIntr, bool kColorIntr, bool kClassed, typename Sink>
 __device__ __forceinline__ void pcg_step1_tile(const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* __restrict__ kfs, int num_kfs,
-                                               const SurfelsView& s, const float* __restrict__ p_, float* __restrict__ g_, uint32_t tile, const Sink& sink) {
+                                               const SurfelsView& s, const float* __restrict__ p_, float* __restrict__ g_, uint32_t tile, const Sink& sink,
+                                               const PcgClasses& pc) {
   const uint32_t i = tile * kPcgSweepBlock + (threadIdx.x & 63);
   const bool in_range = i < s.size;
   const uint32_t ii = in_range ? i : 0;
@@ -544,7 +607,7 @@ __device__ __forceinline__ void pcg_step1_tile(const PcgLayout& L, const PcgExac
   if (kDepthIntr) for (int c = 0; c < 5; ++c) pdi[c] = p_[L.depth_intr_start + c];
   if (kColorIntr) for (int c = 0; c < 4; ++c) pci[c] = p_[L.color_intr_start + c];
   float gs[3] = {0, 0, 0};
-  if (L.accumulate && in_range && L.optimize_geometry) {
+  if (!kClassed && L.accumulate && in_range && L.optimize_geometry) {
     gs[0] = g_[gi];
     if (L.geom_stride == 3) { gs[1] = g_[gi + 1]; gs[2] = g_[gi + 2]; }
   }
@@ -574,9 +637,8 @@ __device__ __forceinline__ void pcg_step1_tile(const PcgLayout& L, const PcgExac
       pending_cf = 0xffffffffu;
     }
   };
-  for_each_candidate(
-      num_kfs, [&](int k) { return sphere_may_project_item(in, kfs[k].pose.F, wb); },
-      [&](int k) {
+  const auto may_project = [&](int k) { return sphere_may_project_item(in, kfs[k].pose.F, wb); };
+  const auto candidate = [&](int k) {
         const KfEntry& kf = kfs[k];
         PairGather pg;
         const bool visible = gather_and_associate(L, in, kf, gp, gn, tp, in_range, &pg);
@@ -667,24 +729,42 @@ __device__ __forceinline__ void pcg_step1_tile(const PcgLayout& L, const PcgExac
         pending_any = true;
         pending_pose = pose_kf;
         pending_base = pose_kf ? base : 0u;
-      });
-  flush_pending();
+      };
+  if constexpr (!kClassed) {
+    for_each_candidate(num_kfs, may_project, candidate);
+    flush_pending();
 
-  if (in_range && L.optimize_geometry) {
-    g_[gi] = gs[0];
-    if (L.geom_stride == 3) { g_[gi + 1] = gs[1]; g_[gi + 2] = gs[2]; }
+    if (in_range && L.optimize_geometry) {
+      g_[gi] = gs[0];
+      if (L.geom_stride == 3) { g_[gi + 1] = gs[1]; g_[gi + 2] = gs[2]; }
+    }
+    return;
   }
+#pragma nounroll
+  for (int c = 0; c < pc.classes; ++c) {
+    if (!((pc.cp.owned >> c) & 1u)) continue;   // another rank holds this class's images
+    for_each_candidate(num_kfs, may_project, candidate, pc.classes, c);
+    if (in_range && L.optimize_geometry) {
+      pcg_class_plane(pc, c, 0)[i] = gs[0];
+      if (L.geom_stride == 3) { pcg_class_plane(pc, c, 1)[i] = gs[1]; pcg_class_plane(pc, c, 2)[i] = gs[2]; }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) gs[q] = 0.f;
+  }
+  flush_pending();
 }
 
-template <bool kDepthIntr, bool kColorIntr>
+template <bool kDepthIntr, bool kColorIntr, bool kClassed, typename... Classes>   // (kClassed, Classes: as pcg_init_kernel)
 __global__ void __launch_bounds__(kPcgSweepBlock) BAHIP_PCG_SWEEP_ATTR
 pcg_step1_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s,
-                 const float* __restrict__ p_, float* __restrict__ g_, const PcgControl* ctl, const uint32_t* __restrict__ sched) {
+                 const float* __restrict__ p_, float* __restrict__ g_, const PcgControl* ctl, const uint32_t* __restrict__ sched,
+                 Classes... classes_arg) {
+  static_assert(sizeof...(Classes) == (kClassed ? 1 : 0), "a kClassed sweep takes one PcgClasses, the other none");
   if (ctl->stop) return;
   uint32_t tile;   // heavy work first (wave_cull.h: scheduled_tile)
   if (!scheduled_tile(blockIdx.x, gridDim.x - (sched ? kHeavySlots : 0u), sched, &tile)) return;
   const PcgGlobalSink sink{ex, (int)(tile & (kHotReplicas - 1))};
-  pcg_step1_tile<kDepthIntr, kColorIntr>(L, ex, in, kfs, num_kfs, s, p_, g_, tile, sink);
+  pcg_step1_tile<kDepthIntr, kColorIntr, kClassed>(L, ex, in, kfs, num_kfs, s, p_, g_, tile, sink, pcg_classes_of(classes_arg...));
 }
 
 // Persistent form (round 4), like pose_accumulate_lds_kernel: one workgroup of 16 wavefronts per compute unit keeps the pose
@@ -695,11 +775,12 @@ pcg_step1_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restr
 // millisecond of the memory side's 23.6 G atomic requests per second behind a 0.8 ms sweep.  Integer sums: the same bits.
 constexpr int kPcgLdsWaves = 16;
 constexpr uint32_t kPcgLdsBatch = 32;
-template <bool kDepthIntr, bool kColorIntr>
+template <bool kDepthIntr, bool kColorIntr, bool kClassed, typename... Classes>   // (kClassed, Classes: as pcg_init_kernel)
 __global__ void __launch_bounds__(64 * kPcgLdsWaves) BAHIP_PCG_SWEEP_ATTR
 pcg_step1_lds_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s,
                      const float* __restrict__ p_, float* __restrict__ g_, const PcgControl* ctl, const uint32_t* __restrict__ sched,
-                     uint32_t padded_tiles, uint32_t* __restrict__ tile_counters, int parity, uint32_t pose_cells) {
+                     uint32_t padded_tiles, uint32_t* __restrict__ tile_counters, int parity, uint32_t pose_cells, Classes... classes_arg) {
+  static_assert(sizeof...(Classes) == (kClassed ? 1 : 0), "a kClassed sweep takes one PcgClasses, the other none");
   extern __shared__ long long pcg_table[];   // ExactCell[pose_cells + kPcgLdsHotCells], then the batch word
   if (blockIdx.x == 0 && threadIdx.x < 8) tile_counters[(parity ^ 1) * 8 + threadIdx.x] = 0;
   if (ctl->stop) return;
@@ -722,7 +803,7 @@ pcg_step1_lds_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __r
     if (index < size) {
       uint32_t tile;
       if (first + index < per_xcd && scheduled_tile((first + index) * 8u + xcd, padded_tiles, sched, &tile))
-        pcg_step1_tile<kDepthIntr, kColorIntr>(L, ex, in, kfs, num_kfs, s, p_, g_, tile, sink);
+        pcg_step1_tile<kDepthIntr, kColorIntr, kClassed>(L, ex, in, kfs, num_kfs, s, p_, g_, tile, sink, pcg_classes_of(classes_arg...));
     } else if (index == size) {
       if (lane == 0) {
         const uint32_t left = per_xcd > first + size ? per_xcd - (first + size) : 0u;
@@ -896,15 +977,21 @@ PcgExact pcg_exact_view(void* buffer, uint32_t head_count) {
 }  // namespace bahip
 #endif
 BAHIP_FLAVOURED_BEGIN
-void launch_pcg_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
-                     const SurfelsView& s, float* r, float* M, uint32_t* tile_cost, const uint32_t* sched) {
-  if (!s.size) return;
+template <bool kClassed, typename... Classes>
+static void launch_pcg_init_sweep(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
+                                  const SurfelsView& s, float* r, float* M, uint32_t* tile_cost, const uint32_t* sched, Classes... cls) {
   const dim3 grid(sched_positions(gS(s.size), sched)), block(kPcgSweepBlock);
   const bool di = L.optimize_depth_intrinsics, ci = L.optimize_color_intrinsics;
-  if (di && ci) hipLaunchKernelGGL((pcg_init_kernel<true, true>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched);
-  else if (di) hipLaunchKernelGGL((pcg_init_kernel<true, false>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched);
-  else if (ci) hipLaunchKernelGGL((pcg_init_kernel<false, true>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched);
-  else hipLaunchKernelGGL((pcg_init_kernel<false, false>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched);
+  if (di && ci) hipLaunchKernelGGL((pcg_init_kernel<true, true, kClassed, Classes...>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched, cls...);
+  else if (di) hipLaunchKernelGGL((pcg_init_kernel<true, false, kClassed, Classes...>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched, cls...);
+  else if (ci) hipLaunchKernelGGL((pcg_init_kernel<false, true, kClassed, Classes...>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched, cls...);
+  else hipLaunchKernelGGL((pcg_init_kernel<false, false, kClassed, Classes...>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched, cls...);
+}
+void launch_pcg_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
+                     const SurfelsView& s, float* r, float* M, uint32_t* tile_cost, const uint32_t* sched, const PcgClasses* classes) {
+  if (!s.size) return;
+  if (!classes) launch_pcg_init_sweep<false>(st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched);
+  else launch_pcg_init_sweep<true>(st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched, *classes);
 }
 BAHIP_FLAVOURED_END
 #ifndef BAHIP_FAST_MATH   // exists once (the exact unit)
@@ -921,6 +1008,10 @@ void launch_pcg_init2(hipStream_t st, const PcgLayout& L, const PcgExact& ex, fl
                       float* p) {
   if (L.unknown_count) hipLaunchKernelGGL(pcg_init2_kernel, dim3(gR(L.unknown_count)), dim3(kPcgBlock), 0, st, L, ex, a, r, M, delta, g, p);
 }
+void launch_pcg_class_combine(hipStream_t st, const PcgLayout& L, const PcgClasses& classes, uint32_t surfels, float* va, float* vb, const void* ctl) {
+  if (surfels) hipLaunchKernelGGL(pcg_class_combine_kernel, dim3(gU(surfels)), dim3(kPcgBlock), 0, st, L, classes, surfels, va, vb,
+                                  static_cast<const PcgControl*>(ctl));
+}
 void launch_pcg_control_init(hipStream_t st, const PcgExact& ex, void* ctl, float* alpha_n) {
   hipLaunchKernelGGL(pcg_control_init_kernel, dim3(1), dim3(64), 0, st, ex, static_cast<PcgControl*>(ctl), alpha_n);
 }
@@ -935,10 +1026,10 @@ BAHIP_FLAVOURED_BEGIN
 static int g_pcg_lds_form = bahip_env_int("BAHIP_PCG_LDS", 1);   // 0: always the one-tile-per-wavefront form
 void set_pcg_lds_form(int mode) { g_pcg_lds_form = (mode >= 0 && mode <= 2) ? mode : 1; }   // 2: also on grids that do not fill the chip (tests)
 constexpr size_t kPcgLdsTableLimit = 128 * 1024;
-template <bool kDepthIntr, bool kColorIntr>
+template <bool kDepthIntr, bool kColorIntr, bool kClassed, typename... Classes>
 static bool launch_pcg_step1_lds(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                                  const SurfelsView& s, const float* p, float* g, const PcgControl* ctl, const uint32_t* sched,
-                                 uint32_t* tile_counters, int* parity_inout) {
+                                 uint32_t* tile_counters, int* parity_inout, Classes... cls) {
   // the pose block of the unknown vector (and of the dense head: head index = unknown index there) ends where the next block begins
   uint32_t pose_end = L.unknown_count;
   if (L.optimize_geometry) pose_end = std::min(pose_end, L.surfel_start);
@@ -951,7 +1042,7 @@ static bool launch_pcg_step1_lds(hipStream_t st, const PcgLayout& L, const PcgEx
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   if (!raised[dev] && !failed[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pcg_step1_lds_kernel<kDepthIntr, kColorIntr>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pcg_step1_lds_kernel<kDepthIntr, kColorIntr, kClassed, Classes...>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)kPcgLdsTableLimit) == hipSuccess) raised[dev] = true;
     else { failed[dev] = true; (void)hipGetLastError(); }
   }
@@ -962,36 +1053,43 @@ static bool launch_pcg_step1_lds(hipStream_t st, const PcgLayout& L, const PcgEx
   const unsigned grid = std::max(8u, std::min((unsigned)cus, ((sched_positions(tiles, sched) + kPcgLdsWaves - 1) / kPcgLdsWaves + 7u) & ~7u));
   const int parity = *parity_inout;
   *parity_inout = parity ^ 1;
-  hipLaunchKernelGGL((pcg_step1_lds_kernel<kDepthIntr, kColorIntr>), dim3(grid), dim3(64 * kPcgLdsWaves), bytes, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched,
-                     tiles, tile_counters, parity, pose_cells);
+  hipLaunchKernelGGL((pcg_step1_lds_kernel<kDepthIntr, kColorIntr, kClassed, Classes...>), dim3(grid), dim3(64 * kPcgLdsWaves), bytes, st, L, ex, in, kfs, num_kfs,
+                     s, p, g, ctl, sched, tiles, tile_counters, parity, pose_cells, cls...);
   return true;
 }
 
 // launches of the step-1 sweep by form since the process started: [0] one tile per wavefront, [1] persistent with the pose block in LDS
 static long long g_pcg_step1_form_launches[2] = {0, 0};
 void pcg_step1_form_launches(long long out[2]) { out[0] = g_pcg_step1_form_launches[0]; out[1] = g_pcg_step1_form_launches[1]; }
-void launch_pcg_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
-                      const SurfelsView& s, const float* p, float* g, const void* ctl_, const uint32_t* sched, uint32_t* tile_counters,
-                      int* parity_inout) {
-  const PcgControl* ctl = static_cast<const PcgControl*>(ctl_);
-  if (!s.size) return;
+template <bool kClassed, typename... Classes>
+static void launch_pcg_step1_sweep(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
+                                   const SurfelsView& s, const float* p, float* g, const PcgControl* ctl, const uint32_t* sched, uint32_t* tile_counters,
+                                   int* parity_inout, Classes... cls) {
   const bool di = L.optimize_depth_intrinsics, ci = L.optimize_color_intrinsics;
   // the persistent LDS form when the grid fills the chip, the per-keyframe entry points (Route B) are not in play and the pose
   // block of the head fits the table
   if (tile_counters && parity_inout && L.single_keyframe < 0 && (g_pcg_lds_form == 2 || (g_pcg_lds_form == 1 && gS(s.size) >= 8192))) {
     bool launched;
-    if (di && ci) launched = launch_pcg_step1_lds<true, true>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout);
-    else if (di) launched = launch_pcg_step1_lds<true, false>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout);
-    else if (ci) launched = launch_pcg_step1_lds<false, true>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout);
-    else launched = launch_pcg_step1_lds<false, false>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout);
+    if (di && ci) launched = launch_pcg_step1_lds<true, true, kClassed>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout, cls...);
+    else if (di) launched = launch_pcg_step1_lds<true, false, kClassed>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout, cls...);
+    else if (ci) launched = launch_pcg_step1_lds<false, true, kClassed>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout, cls...);
+    else launched = launch_pcg_step1_lds<false, false, kClassed>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout, cls...);
     if (launched) { ++g_pcg_step1_form_launches[1]; return; }
   }
   ++g_pcg_step1_form_launches[0];
   const dim3 grid(sched_positions(gS(s.size), sched)), block(kPcgSweepBlock);
-  if (di && ci) hipLaunchKernelGGL((pcg_step1_kernel<true, true>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched);
-  else if (di) hipLaunchKernelGGL((pcg_step1_kernel<true, false>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched);
-  else if (ci) hipLaunchKernelGGL((pcg_step1_kernel<false, true>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched);
-  else hipLaunchKernelGGL((pcg_step1_kernel<false, false>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched);
+  if (di && ci) hipLaunchKernelGGL((pcg_step1_kernel<true, true, kClassed, Classes...>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, cls...);
+  else if (di) hipLaunchKernelGGL((pcg_step1_kernel<true, false, kClassed, Classes...>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, cls...);
+  else if (ci) hipLaunchKernelGGL((pcg_step1_kernel<false, true, kClassed, Classes...>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, cls...);
+  else hipLaunchKernelGGL((pcg_step1_kernel<false, false, kClassed, Classes...>), grid, block, 0, st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, cls...);
+}
+void launch_pcg_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
+                      const SurfelsView& s, const float* p, float* g, const void* ctl_, const uint32_t* sched, uint32_t* tile_counters,
+                      int* parity_inout, const PcgClasses* classes) {
+  const PcgControl* ctl = static_cast<const PcgControl*>(ctl_);
+  if (!s.size) return;
+  if (!classes) launch_pcg_step1_sweep<false>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout);
+  else launch_pcg_step1_sweep<true>(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout, *classes);
 }
 BAHIP_FLAVOURED_END
 #ifndef BAHIP_FAST_MATH   // exists once (the exact unit)
@@ -1019,13 +1117,13 @@ void launch_pcg_update_cfactors(hipStream_t st, const Intrinsics& in, uint32_t s
 
 // dispatchers (ba_launch.h: "Two arithmetic flavours")
 void launch_pcg_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
-                     const SurfelsView& s, float* r, float* M, uint32_t* tile_cost, const uint32_t* sched) {
-  BAHIP_PICK(in, launch_pcg_init(st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched));
+                     const SurfelsView& s, float* r, float* M, uint32_t* tile_cost, const uint32_t* sched, const PcgClasses* classes) {
+  BAHIP_PICK(in, launch_pcg_init(st, L, ex, in, kfs, num_kfs, s, r, M, tile_cost, sched, classes));
 }
 void launch_pcg_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                       const SurfelsView& s, const float* p, float* g, const void* ctl, const uint32_t* sched, uint32_t* tile_counters,
-                      int* parity_inout) {
-  BAHIP_PICK(in, launch_pcg_step1(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout));
+                      int* parity_inout, const PcgClasses* classes) {
+  BAHIP_PICK(in, launch_pcg_step1(st, L, ex, in, kfs, num_kfs, s, p, g, ctl, sched, tile_counters, parity_inout, classes));
 }
 void set_pcg_lds_form(int mode) { exact::set_pcg_lds_form(mode); fast::set_pcg_lds_form(mode); }
 void pcg_step1_form_launches(long long out[2]) {

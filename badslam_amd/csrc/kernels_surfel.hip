@@ -457,6 +457,22 @@ geometry_phase_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kf
   geometry_step<kUseDepth, kUseDesc, 1, kActivate, kPhase>(in, kfs, num_kfs, s, activate_count, nullptr, cpn, cpp, xcd_run_tile(blockIdx.x, gridDim.x), nullptr);   // (buffer order)
 }
 
+// One phase of the keyframe-sharded normals update (bahip_update_surfel_normals, before each outer iteration of the PCG scheme): kPhase 1
+// stores this rank's class partials (normals_pass: kSumsProduce), kPhase 2 takes the normals from the exchanged ones (kSumsConsume).
+template <int kPhase>
+__global__ void __launch_bounds__(kSurfelBlock) BAHIP_WAVES_ATTR
+normals_phase_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s, ClassPartials cp) {
+  const uint32_t i = xcd_chunked_tile(blockIdx.x) * kSurfelBlock + threadIdx.x;
+  const bool in_range = i < s.size;
+  const uint32_t ii = in_range ? i : 0;
+  bool live = in_range && (s.active[ii] & kSurfelActiveFlag);
+  const Vec3 gp = surfel_position(s, ii);
+  Vec3 gn = surfel_normal(s, ii);
+  const WaveBounds wb = wave_bounds(gp, live && position_valid(gp));
+  static_assert(kNormalsSums == 4, "normals_pass without activation: x, y, z, count");
+  normals_pass<1, false, kPhase == 1 ? kSumsProduce : kSumsConsume>(in, kfs, num_kfs, wb, s, ii, &live, false, gp, &gn, nullptr, cp, in_range);
+}
+
 // Surfel activation under keyframe sharding: this rank's kActive keyframes only; hits[i] = 1 where one of them sees surfel i
 // (the words are summed over the ranks as integers, then activation_from_hits_kernel sets the flags).
 __global__ void __launch_bounds__(kSurfelBlock) BAHIP_WAVES_ATTR
@@ -585,6 +601,14 @@ void launch_geometry_phase(hipStream_t stream, int phase, bool use_depth, bool u
   }
 }
 
+// (the caller clears the partials phase 1 produces beforehand and sums them over the ranks afterwards)
+void launch_normals_phase(hipStream_t stream, int phase, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, const ClassPartials& cp) {
+  if (s.size == 0) return;
+  const dim3 grid(grid_for(s.size)), block(kSurfelBlock);
+  if (phase == 1) hipLaunchKernelGGL(normals_phase_kernel<1>, grid, block, 0, stream, in, kfs, num_kfs, s, cp);
+  else hipLaunchKernelGGL(normals_phase_kernel<2>, grid, block, 0, stream, in, kfs, num_kfs, s, cp);
+}
+
 void launch_activation_hits(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, uint32_t surfels_size,
                             int kf_rank, int kf_world, uint32_t* hits) {
   if (surfels_size == 0) return;
@@ -692,6 +716,9 @@ void launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const In
 void launch_geometry_phase(hipStream_t stream, int phase, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                            const SurfelsView& s, long long activate_count, const ClassPartials& cpn, const ClassPartials& cpp) {
   BAHIP_PICK(in, launch_geometry_phase(stream, phase, use_depth, use_desc, in, kfs, num_kfs, s, activate_count, cpn, cpp));
+}
+void launch_normals_phase(hipStream_t stream, int phase, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, const ClassPartials& cp) {
+  BAHIP_PICK(in, launch_normals_phase(stream, phase, in, kfs, num_kfs, s, cp));
 }
 void launch_activation_hits(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, uint32_t surfels_size,
                             int kf_rank, int kf_world, uint32_t* hits) {

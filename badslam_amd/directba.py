@@ -284,8 +284,13 @@ class DirectBA:
         self.L.dba_set_intrinsics_sum_classes.argtypes = [C.c_void_p, C.c_int]
         assert self.L.dba_set_intrinsics_sum_classes(self.h, int(classes)) == 0
 
+    def SetPCGSumClasses(self, classes):
+        """1 (default), 2, 4 or 8 keyframe classes in the surfel block of the PCG scheme's r, M and g (keyframe sharding of it over world ranks needs >= world)."""
+        self.L.dba_set_pcg_sum_classes.argtypes = [C.c_void_p, C.c_int]
+        assert self.L.dba_set_pcg_sum_classes(self.h, int(classes)) == 0
+
     def SetKeyframeSharding(self, rank, world):
-        """This object holds all surfels and sweeps the keyframes k with k % world == rank (world = 2, 4 or 8: whole keyframe classes of the per-surfel sums; alternating scheme only, the intrinsics after SetIntrinsicsSumClasses(>= world))."""
+        """This object holds all surfels and sweeps the keyframes k with k % world == rank (world = 2, 4 or 8: whole keyframe classes of the per-surfel sums; the intrinsics after SetIntrinsicsSumClasses(>= world), the PCG scheme after SetPCGSumClasses(>= world), without surfel updates)."""
         assert self.L.dba_set_keyframe_sharding(self.h, int(rank), int(world)) == 0
 
     def set_pcg_gauge_keyframe(self, k):

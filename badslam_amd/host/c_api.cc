@@ -223,6 +223,10 @@ int dba_set_intrinsics_sum_classes(dba_handle* h, int classes) {
   h->ba->SetIntrinsicsSumClasses(classes);
   return 0;
 }
+int dba_set_pcg_sum_classes(dba_handle* h, int classes) {
+  h->ba->SetPCGSumClasses(classes);
+  return 0;
+}
 int dba_set_keyframe_sharding(dba_handle* h, int rank, int world) {
   h->ba->SetKeyframeSharding(rank, world);
   return 0;

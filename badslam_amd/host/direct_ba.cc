@@ -219,6 +219,7 @@ void DirectBA::SetSurfelSharding(int rank, int world, u32 chunk) {
 
 void DirectBA::SetSumClasses(int classes) { BAHIP_CHECKED_CALL(bahip_context_set_sum_classes(ctx_, classes)); }
 void DirectBA::SetIntrinsicsSumClasses(int classes) { BAHIP_CHECKED_CALL(bahip_context_set_intrinsics_sum_classes(ctx_, classes)); }
+void DirectBA::SetPCGSumClasses(int classes) { BAHIP_CHECKED_CALL(bahip_context_set_pcg_sum_classes(ctx_, classes)); }
 void DirectBA::SetFastArithmetic(bool enabled) { BAHIP_CHECKED_CALL(bahip_context_set_arithmetic(ctx_, enabled ? BAHIP_ARITHMETIC_FAST : BAHIP_ARITHMETIC_EXACT)); }
 void DirectBA::SetRowMajorCreation(bool enabled) { BAHIP_CHECKED_CALL(bahip_context_set_creation_order(ctx_, enabled ? 1 : 0)); }
 
@@ -412,9 +413,9 @@ void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsi
   }
   last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = 0;
   if (keyframe_shard_world_ > 1)
-    CHECK(!use_pcg && !do_surfel_updates && !increase_ba_iteration_count)
-        << "keyframe sharding covers the alternating scheme over poses, geometry and intrinsics without surfel updates and end tasks "
-           "(their per-surfel sums run over all keyframes in order): use surfel sharding for the rest";
+    CHECK(!do_surfel_updates && !increase_ba_iteration_count)
+        << "keyframe sharding covers the alternating scheme over poses, geometry and intrinsics and the PCG scheme (SetPCGSumClasses), "
+           "without surfel updates and end tasks (their per-surfel sums run over all keyframes in order): use surfel sharding for the rest";
   if (use_pcg) {
     BundleAdjustmentPCG(stream, optimize_depth_intrinsics, optimize_color_intrinsics, do_surfel_updates, optimize_poses,
                         optimize_geometry, min_iterations, max_iterations, pcg_max_inner_iterations, pcg_max_keyframes,
@@ -859,7 +860,9 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
     opt.optimize_depth_intrinsics = optimize_depth_intrinsics; opt.optimize_color_intrinsics = optimize_color_intrinsics;
     opt.use_depth_residuals = use_depth_residuals_; opt.use_descriptor_residuals = use_descriptor_residuals_;
     opt.max_inner_iterations = max_inner_iterations;
-    opt.gauge_keyframe = (pcg_gauge_keyframe_ >= 0) ? pcg_gauge_keyframe_ : (rand() % (int)keyframes_.size());   // B/direct_ba_pcg.cc:328
+    // B/direct_ba_pcg.cc:328 draws rand() % K; under keyframe sharding every rank must hold the same gauge, and a rand() stream is
+    // neither shared by the instances of one process nor by those of several: there the default is keyframe 0
+    opt.gauge_keyframe = (pcg_gauge_keyframe_ >= 0) ? pcg_gauge_keyframe_ : keyframe_shard_world_ > 1 ? 0 : (rand() % (int)keyframes_.size());
     bahip_camera out_color, out_depth;
     float out_a = depth_params_.a;
     int inner_steps = 0, num_converged = 0;

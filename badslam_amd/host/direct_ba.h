@@ -134,7 +134,8 @@ class DirectBA {
 
   // --- additions of this backend ---
   // The gauge keyframe of the PCG scheme; the reference draws rand() % K per outer iteration
-  // (B/direct_ba_pcg.cc:328).  < 0 (default) = same rand() stream.
+  // (B/direct_ba_pcg.cc:328).  < 0 (default) = same rand() stream; under keyframe sharding keyframe 0 (every rank must hold the
+  // same gauge).
   void SetPCGGaugeKeyframe(int keyframe_id) { pcg_gauge_keyframe_ = keyframe_id; }
   // Multi-GPU surfel sharding: sums of the per-keyframe normal equations go through this hook
   // (see include/badslam_hip.h, bahip_allreduce_fn).
@@ -149,9 +150,10 @@ class DirectBA {
   // the images of those with (index among the non-deleted keyframes) % world == rank only (world = 1, 2, 4, or 8 after
   // SetSumClasses(8)).  Covers the
   // alternating scheme over poses, geometry and the depth / colour intrinsics -- BundleAdjustment(stream, ..., /*do_surfel_updates*/
-  // false, ..., /*use_pcg*/ false, ..., /*increase_ba_iteration_count*/ false), the intrinsics after SetIntrinsicsSumClasses(c) with
-  // c >= world -- and ends with the unsharded run's bits (same class counts) on every rank; the PCG scheme and the surfel lifecycle
-  // (end tasks included) are refused.  Needs SetAllReduce or an RCCL communicator when world > 1.
+  // false, ..., /*increase_ba_iteration_count*/ false), the intrinsics after SetIntrinsicsSumClasses(c) with
+  // c >= world, the PCG scheme (use_pcg, after SetPCGSumClasses(c) with c >= world) -- and ends with the unsharded run's bits (same class
+  // counts) on every rank; the surfel lifecycle (end tasks included) is refused.  Needs SetAllReduce or an RCCL communicator when
+  // world > 1.
   void SetKeyframeSharding(int rank, int world);
   // The per-surfel sums of the normals / geometry passes are defined over 4 (default) or 8 interleaved keyframe classes
   // (bahip_context_set_sum_classes); keyframe sharding over 8 ranks needs 8 -- and so does the single-GPU run it is compared with.
@@ -160,6 +162,10 @@ class DirectBA {
   // (bahip_context_set_intrinsics_sum_classes); keyframe sharding of that step over `world` ranks needs at least `world` -- and the
   // single-GPU run it is compared with the same count.
   void SetIntrinsicsSumClasses(int classes);
+  // The surfel block of the PCG scheme's r, M and g is defined over 1 (default), 2, 4 or 8 keyframe classes
+  // (bahip_context_set_pcg_sum_classes); keyframe sharding of the PCG scheme over `world` ranks needs at least `world` -- and the
+  // single-GPU run it is compared with the same count.
+  void SetPCGSumClasses(int classes);
   // Ours: new surfels of a keyframe in the reference's row-major append order (B/kernel_create_surfels.cu:357-390) instead of this
   // backend's tile-major one (bahip_context_set_creation_order): the same surfels, the reference's indices -- and therefore the
   // reference's survivors when surfels merge.  Slower sweeps until the next spatial reorder (SetSpatialSortCellSize).

@@ -160,6 +160,10 @@ class Scene:
         """1 (default), 2, 4 or 8 keyframe classes in the global sums of the intrinsics step (bahip_context_set_intrinsics_sum_classes)."""
         capi.check(self.lib.bahip_context_set_intrinsics_sum_classes(self.ctx.handle, int(classes)))
 
+    def set_pcg_sum_classes(self, classes):
+        """1 (default), 2, 4 or 8 keyframe classes in the surfel block of the PCG scheme's r, M and g (bahip_context_set_pcg_sum_classes)."""
+        capi.check(self.lib.bahip_context_set_pcg_sum_classes(self.ctx.handle, int(classes)))
+
     def read_intrinsics_sums(self, with_cells=True):
         """The last intrinsics step's sums rounded to binary32 (bahip_debug_read_intrinsics_sums): (glob[34], cells[S, 8] or None)."""
         glob = np.zeros(34, np.float32)

@@ -90,6 +90,9 @@ int dba_set_sum_classes(dba_handle* h, int classes);
 /* DirectBA::SetIntrinsicsSumClasses: 1 (default), 2, 4 or 8 keyframe classes in the definition of the intrinsics step's global sums
  * (bahip_context_set_intrinsics_sum_classes; keyframe sharding of that step over world ranks needs >= world) */
 int dba_set_intrinsics_sum_classes(dba_handle* h, int classes);
+/* DirectBA::SetPCGSumClasses: 1 (default), 2, 4 or 8 keyframe classes in the definition of the surfel block of the PCG scheme's r, M and g
+ * (bahip_context_set_pcg_sum_classes; keyframe sharding of the PCG scheme over world ranks needs >= world) */
+int dba_set_pcg_sum_classes(dba_handle* h, int classes);
 /* DirectBA::SetRowMajorCreation (ours): 1 = the surfels a keyframe creates are appended in the reference's row-major pixel order
  * (B/kernel_create_surfels.cu:357-390), 0 (default) = tile-major (bahip_context_set_creation_order) */
 int dba_set_row_major_creation(dba_handle* h, int enabled);
@@ -97,7 +100,8 @@ int dba_set_row_major_creation(dba_handle* h, int enabled);
 int dba_set_fast_arithmetic(dba_handle* h, int enabled);
 /* DirectBA::SetKeyframeSharding: this object holds all surfels and the images of the keyframes k with k % world == rank
  * (bahip_context_set_keyframe_sharding; world = 1, 2, 4, or 8 after dba_set_sum_classes(h, 8)); the alternating scheme over poses,
- * geometry and -- after dba_set_intrinsics_sum_classes(h, c), c >= world -- the intrinsics, without surfel updates, PCG or end tasks */
+ * geometry and -- after dba_set_intrinsics_sum_classes(h, c), c >= world -- the intrinsics, and the PCG scheme after
+ * dba_set_pcg_sum_classes(h, c), c >= world; without surfel updates or end tasks */
 int dba_set_keyframe_sharding(dba_handle* h, int rank, int world);
 /* DirectBA::SetBAIterationCount / SetLastBAIterationCount (direct_ba.h:362-366) */
 int dba_set_ba_iteration_counts(dba_handle* h, int ba_iteration_count, int last_ba_iteration_count);

@@ -126,10 +126,15 @@ int bahip_context_set_allreduce(bahip_context* ctx, bahip_allreduce_fn fn, void*
  *   - bahip_optimize_intrinsics sweeps this rank's classes of the global sums' keyframe classes (world must not exceed the count
  *     of bahip_context_set_intrinsics_sum_classes) and sums the binary64 accumulators over the ranks (BAHIP_SUM_F64, 64 + 8 S
  *     doubles, the exchange surfel sharding makes too); every rank solves the same 5 x 5 / 4 x 4 systems and cfactor cells;
+ *   - bahip_pcg_iteration sweeps this rank's classes of the PCG surfel block's keyframe classes (world must not exceed the count of
+ *     bahip_context_set_pcg_sum_classes); the class partials of r and M after the init sweep and of g after every step-1 sweep are
+ *     summed over the ranks as BAHIP_SUM_I64 over their bit patterns (C x 2 x (1 or 3) and C x (1 or 3) binary32 values per surfel),
+ *     the exact accumulators as under surfel sharding; the normals update before it (bahip_update_surfel_normals) exchanges its
+ *     class partials like the geometry step's normals pass (world must not exceed bahip_context_set_sum_classes);
  *   - everything ends with the bits of the unsharded run (with the same class counts) on every rank.
- * The PCG scheme and the surfel lifecycle are refused in this mode (their per-surfel chains run over all keyframes in order; use
- * surfel sharding).  A hook or an RCCL communicator must be installed when world > 1.  Surfel and keyframe sharding exclude each
- * other on one context. */
+ * The PCG stage entry points (bahip_pcg_begin ...), bahip_assign_colors and the surfel lifecycle are refused in this mode (their
+ * per-surfel chains run over all keyframes in order; use surfel sharding).  A hook or an RCCL communicator must be installed when
+ * world > 1.  Surfel and keyframe sharding exclude each other on one context. */
 int bahip_context_set_keyframe_sharding(bahip_context* ctx, int rank, int world);
 /* The number of interleaved partial sums (keyframe classes) the per-surfel sums of the normals and geometry passes are DEFINED
  * over: 4 (default) or 8.  In exact arithmetic both are the reference's sum (B/kernel_opt_geometry.cu: keyframe after keyframe);
@@ -142,6 +147,13 @@ int bahip_context_set_sum_classes(bahip_context* ctx, int classes);
  * (kernels_intrinsics.hip).  C = 1 is the one chain over all keyframes.  Keyframe sharding over `world` ranks needs C >= world, and
  * the single-GPU run it is compared with the same C.  The per-cell sums do not depend on it.  Takes effect with the next step. */
 int bahip_context_set_intrinsics_sum_classes(bahip_context* ctx, int classes);
+/* The number of keyframe classes C the surfel block of the PCG scheme's r, M (PCGInit) and g (PCGStep1) is DEFINED over: 1 (default),
+ * 2, 4 or 8.  Keyframe k (bound index) belongs to class k % C; per surfel entry and class a binary32 chain over the class's keyframes
+ * in ascending order, p_c, and the entry is ((p0 + p1) + p2) + ... (the combination rule of the normals / geometry passes).  C = 1
+ * is the one chain over all keyframes.  Keyframe sharding of bahip_pcg_iteration over `world` ranks needs C >= world, and the
+ * single-GPU run it is compared with the same C.  The dense head (poses, intrinsics, cfactor cells) and the dot products are exact
+ * sums and do not depend on it.  Takes effect with the next call. */
+int bahip_context_set_pcg_sum_classes(bahip_context* ctx, int classes);
 /* Order in which the surfels a keyframe creates are appended: 0 (default) = by tiles of 8 x 8 sparse cells of the creating
  * keyframe, row-major inside a tile -- the 64 surfels of a wavefront form a compact patch, which is what the sweeps' culling wants;
  * 1 = row-major over the whole image, the reference's order (B/kernel_create_surfels.cu:357-390).  The same surfels either way;
