@@ -309,6 +309,30 @@ void launch_create_append(hipStream_t st, const Intrinsics& in, const KfEntry& f
                           const uint32_t* indices, uint32_t surfels_size, const SurfelsView& s);
 void launch_delete_update(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,
                           int min_obs, uint32_t* deleted_count);
+// Keyframe sharding of the lifecycle (capi_lifecycle.hip): the owner of a frame / item runs its part of the batch kernels alone (a grid
+// of one row over pointers advanced to its rows); the filter of a creation batch is cut into count (over this rank's co-visible
+// keyframes, from the owner's raw words of each candidate) and decide; deletion into a partial sweep over this rank's keyframes and a
+// decide launch.
+void launch_merge_batch_associate_frame(hipStream_t st, const Intrinsics& in, const MergeBatchFrame* frame, uint32_t positions, const SurfelsView& s,
+                                        const uint32_t* lists, uint32_t bounded_tiles, uint32_t* counts_row, uint32_t* pair_cells, uint32_t* pair_ranks);
+void launch_merge_batch_fill_frame(hipStream_t st, const Intrinsics& in, const MergeBatchFrame* frame, uint32_t positions, uint32_t surfels_size,
+                                   const uint32_t* lists, uint32_t bounded_tiles, const uint32_t* offsets_row, const uint32_t* pair_cells,
+                                   const uint32_t* pair_ranks, uint32_t* members, void* member_cell);
+hipError_t launch_merge_batch_offsets(hipStream_t st, const Intrinsics& in, int num_frames, const uint32_t* counts, uint32_t* offsets, uint32_t* frame_first,
+                                      void* scan_temp, size_t scan_temp_bytes);
+void launch_create_batch_item_candidates(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, const CreateBatchItem* item, uint32_t positions,
+                                         const SurfelsView& cloud_at_begin, const uint32_t* lists, uint32_t bounded_tiles, uint8_t* occupancy_row,
+                                         uint8_t* candidates_row, uint32_t* cand_px_row, const KfEntry& frame);
+void launch_create_batch_filter_count(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, const CreateBatchItem* items, int num_items, const int* covis,
+                                      const float* covis_T_frame, const uint8_t* candidates, const uint32_t* cand_px, void* counts /* uint2 [n][cells] */,
+                                      int kf_rank, int kf_world);
+void launch_create_batch_filter_decide(hipStream_t st, const Intrinsics& in, int num_items, const void* counts, int min_obs, uint8_t* candidates);
+hipError_t launch_create_batch_scan(hipStream_t st, const Intrinsics& in, int num_items, const uint8_t* candidates, uint32_t* scan, void* scan_temp, size_t scan_temp_bytes);
+void launch_create_batch_item_records(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, const CreateBatchItem* item, const uint8_t* candidates_row,
+                                      const uint32_t* scan_row, uint32_t* cand_cell, const SurfelsView& records, uint32_t* first_of_item2);
+void launch_delete_partial(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, int kf_rank, int kf_world,
+                           uint32_t* partial, uint32_t stride);
+void launch_delete_decide(hipStream_t st, const SurfelsView& s, const uint32_t* partial, uint32_t stride, int kf_world, int min_obs, uint32_t* deleted_count);
 void launch_shard_to_cloud(hipStream_t st, const SurfelsView& shard, const SurfelsView& cloud, uint32_t rank, uint32_t world, uint32_t chunk);
 void launch_cloud_to_shard(hipStream_t st, const SurfelsView& cloud, const SurfelsView& shard, uint32_t rank, uint32_t world, uint32_t chunk);
 size_t sort_scratch_bytes(uint32_t n);

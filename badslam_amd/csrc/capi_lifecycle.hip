@@ -1,5 +1,7 @@
 // capi_lifecycle.hip -- the surfel lifecycle behind the C boundary: supporting surfels and merging, creation (one keyframe or a batch on
 // the device), deletion + radius update, compaction, the spatial reorder.
+#include <functional>
+
 #include "capi_internal.h"
 
 using namespace bahip;
@@ -103,23 +105,177 @@ int bahip_determine_supporting_surfels(bahip_context* ctx, int merge, float merg
   return determine_supporting_impl(ctx, merge, merge_dist_factor, e, surfels, sup, merged_count_out);
 }
 
+// A sum over the ranks of a keyframe-sharded lifecycle call: zero-filled partials (or integer counts) as 64-bit integers, `bytes` a
+// multiple of 8.  A failure says which exchange it was; the context stays usable (what a failed call has written lies beyond the
+// caller's surfels_size or in scratch: the surfel count it reports is unchanged).
+static int kf_exchange(bahip_context* ctx, void* buffer, size_t bytes, const char* what) {
+  if (reduce_over_ranks(ctx, buffer, bytes / 8, BAHIP_SUM_I64))
+    return fail((std::string("keyframe sharding: the exchange of ") + what + " failed: " + g_last_error).c_str(), __FILE__, __LINE__);
+  return 0;
+}
+#define REQUIRE_KF_TRANSPORT() \
+  REQUIRE(!kf_sharded(ctx) || is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator")
+
+// A merge batch by cell lists (round 6; kernels_lifecycle.hip: merge_pairs_kernel): the associated (surfel, frame) pairs are grouped by
+// (frame, cell) up front and each frame costs ONE launch of one thread per pair.  table: every frame's entry, list and first sweep
+// position.  *done = false: the batch is too large for the lists (nothing has been launched).
+// Keyframe sharding (owned != NULL): the association sweep reads frame j's BA plane, so the owner of j runs j's rows of the association
+// and of the fill; the per-(frame, cell) counts and then the members (with their cells' begin and count) are summed over the ranks as
+// zero-filled partials.  The scan, the per-frame decisions and the markers run on every rank: they read no image, and a decision depends
+// on the set of a cell's members, not on their order.
+static int merge_by_cell_lists(bahip_context* ctx, const std::vector<MergeBatchFrame>& table, const std::vector<char>* owned, uint64_t positions,
+                               uint32_t max_positions, float merge_dist_factor, const bahip_surfels* surfels, const SupportingView& sup, bool* done) {
+  *done = false;
+  hipStream_t st = ctx->stream;
+  const int num_frames = (int)table.size();
+  const uint32_t bounded_tiles = ctx->lifecycle_bounds_tiles;
+  const uint32_t all_tiles = (surfels->surfels_size + 63u) / 64u, tail = all_tiles > bounded_tiles ? all_tiles - bounded_tiles : 0u;
+  const size_t cells = (size_t)ctx->in.cf_width * (size_t)ctx->in.cf_height;
+  const size_t entries = (size_t)num_frames * cells + 1;
+  if (!(positions * 64 < ((uint64_t)1 << 31) && entries < ((size_t)1 << 31))) return 0;
+  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t sweep = 64 * (size_t)positions;   // lanes of all sweep positions: an upper bound of the pairs
+  const size_t table_bytes = align(sizeof(MergeBatchFrame) * (size_t)num_frames), entry_bytes = align(sizeof(uint32_t) * entries),
+               word_bytes = align(sizeof(uint32_t) * sweep), first_bytes = align(sizeof(uint32_t) * ((size_t)num_frames + 1)),
+               temp_bytes = align(merge_batch_scan_temp_bytes(entries));
+  const size_t need = table_bytes + 2 * entry_bytes + 3 * word_bytes + 2 * word_bytes + first_bytes + temp_bytes;
+  if (need > ctx->merge_batch_bytes) {
+    HIP_TRY(hipStreamSynchronize(st));
+    hipFree(ctx->dev_merge_batch); ctx->dev_merge_batch = nullptr; ctx->merge_batch_bytes = 0;
+    HIP_TRY(hipMalloc(&ctx->dev_merge_batch, need + need / 4));
+    ctx->merge_batch_bytes = need + need / 4;
+  }
+  char* p = static_cast<char*>(ctx->dev_merge_batch);
+  MergeBatchFrame* dev_table = reinterpret_cast<MergeBatchFrame*>(p); p += table_bytes;
+  uint32_t* counts = reinterpret_cast<uint32_t*>(p); p += entry_bytes;
+  uint32_t* offsets = reinterpret_cast<uint32_t*>(p); p += entry_bytes;
+  uint32_t* pair_cells = reinterpret_cast<uint32_t*>(p); p += word_bytes;
+  uint32_t* pair_ranks = reinterpret_cast<uint32_t*>(p); p += word_bytes;
+  uint32_t* members = reinterpret_cast<uint32_t*>(p); p += word_bytes;
+  void* member_cell = p; p += 2 * word_bytes;
+  uint32_t* frame_first = reinterpret_cast<uint32_t*>(p); p += first_bytes;
+  void* scan_temp = p;
+  HIP_TRY(hipMemcpyAsync(dev_table, table.data(), sizeof(MergeBatchFrame) * (size_t)num_frames, hipMemcpyHostToDevice, st));
+  const SurfelsView s = make_view(surfels);
+  std::vector<uint32_t> first((size_t)num_frames + 1);
+  if (!owned) {
+    HIP_TRY(launch_merge_batch_lists(st, ctx->in, dev_table, num_frames, max_positions, s, ctx->dev_lifecycle_lists, bounded_tiles, counts, offsets, pair_cells,
+                                     pair_ranks, members, member_cell, frame_first, scan_temp, temp_bytes));
+  } else {
+    HIP_TRY(hipMemsetAsync(counts, 0, sizeof(uint32_t) * entries, st));
+    for (int j = 0; j < num_frames; ++j)
+      if ((*owned)[(size_t)j])
+        launch_merge_batch_associate_frame(st, ctx->in, dev_table + j, table[(size_t)j].list_count + tail, s, ctx->dev_lifecycle_lists, bounded_tiles,
+                                           counts + (size_t)j * cells, pair_cells, pair_ranks);
+    CHECK_LAUNCH();
+    // (an even number of words: the last entry is the scan's zero sentinel, the same on every rank)
+    if (kf_exchange(ctx, counts, sizeof(uint32_t) * (((size_t)num_frames * cells + 1) & ~(size_t)1), "the merge batch's cell counts")) return 1;
+    HIP_TRY(launch_merge_batch_offsets(st, ctx->in, num_frames, counts, offsets, frame_first, scan_temp, temp_bytes));
+    HIP_TRY(hipMemcpyAsync(first.data(), frame_first, sizeof(uint32_t) * first.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // members and member_cell packed behind each other for one exchange: [pairs] words, then [pairs] uint2 (pairs <= sweep)
+    const size_t pairs = ((size_t)first[(size_t)num_frames] + 1) & ~(size_t)1;
+    member_cell = members + pairs;
+    HIP_TRY(hipMemsetAsync(members, 0, 3 * sizeof(uint32_t) * pairs, st));
+    for (int j = 0; j < num_frames; ++j)
+      if ((*owned)[(size_t)j])
+        launch_merge_batch_fill_frame(st, ctx->in, dev_table + j, table[(size_t)j].list_count + tail, s.size, ctx->dev_lifecycle_lists, bounded_tiles,
+                                      offsets + (size_t)j * cells, pair_cells, pair_ranks, members, member_cell);
+    CHECK_LAUNCH();
+    if (kf_exchange(ctx, members, 3 * sizeof(uint32_t) * pairs, "the merge batch's cell members")) return 1;
+  }
+  // per-surfel words "deleted at step" in accum row 0 (scratch by contract, B/kernels.cuh:78-90): ~0 = not deleted by this batch
+  uint32_t* deleted_at = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)kSurfelAccum0 * surfels->pitch_bytes);
+  HIP_TRY(hipMemsetAsync(deleted_at, 0xff, sizeof(uint32_t) * (size_t)surfels->surfels_size, st));
+  if (!owned) {
+    HIP_TRY(hipMemcpyAsync(first.data(), frame_first, sizeof(uint32_t) * first.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // `table` is pageable and goes out of scope; the grids below come from `first`
+  }
+  const float cell = (float)ctx->in.cell;
+  const float cell_merge_dist_sq = cell * cell * merge_dist_factor * merge_dist_factor;
+  uint32_t* counter = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 3;   // the deferred count of bahip_take_merged_count
+  for (int j = 0; j < num_frames; ++j) {
+    launch_merge_pairs(st, s, members, member_cell, first[(size_t)j], first[(size_t)j + 1], (uint32_t)j, deleted_at, cell_merge_dist_sq,
+                       kCosNormalCompat);
+    CHECK_LAUNCH();
+  }
+  launch_merge_batch_apply(st, s, deleted_at, counter);
+  CHECK_LAUNCH();
+  // (the planes are not used; the batch's contract is that they end empty)
+  if (ctx->supporting_planes_empty != sup.b[0]) launch_supporting_fill(st, sup, ctx->in.cf_width, ctx->in.cf_height);
+  ctx->supporting_planes_empty = sup.b[0];
+  ++g_merge_cells_batches;
+  *done = true;
+  return 0;
+}
+
 // The merges of a batch of keyframes, pipelined: per keyframe two dependent launches -- [apply of the previous keyframe beside the insert
 // of this one], decide -- instead of three (kernels_lifecycle.hip: merge_apply_insert_kernel).  The keyframes alternate between the
-// caller's supporting planes and a second set the context owns; both end empty.
+// caller's supporting planes and a second set the context owns; both end empty.  entry_of(j, &entry): frame j's entry, pose included.
+static int merge_pipelined(bahip_context* ctx, int num_frames, const std::function<int(int, KfEntry*)>& entry_of, float merge_dist_factor, const bahip_surfels* surfels,
+                           SupportingView* sup /* [2]: the caller's, then the context's */, uint32_t supporting_pitch) {
+  hipStream_t st = ctx->stream;
+  // the second set of planes: same pitch, the sparse-cell region's rows
+  const size_t plane_bytes = (size_t)supporting_pitch * (size_t)ctx->in.cf_height;
+  if (plane_bytes > ctx->merge_planes_bytes) {
+    for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) {
+      hipFree(ctx->merge_planes[b]);
+      ctx->merge_planes[b] = nullptr;
+    }
+    ctx->merge_planes_bytes = 0;
+    for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) HIP_TRY(hipMalloc(&ctx->merge_planes[b], plane_bytes));
+    ctx->merge_planes_bytes = plane_bytes;
+  }
+  for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) sup[1].b[b] = ctx->merge_planes[b];
+  sup[1].pitch = supporting_pitch;
+  if (ctx->supporting_planes_empty != sup[0].b[0]) launch_supporting_fill(st, sup[0], ctx->in.cf_width, ctx->in.cf_height);
+  launch_supporting_fill(st, sup[1], ctx->in.cf_width, ctx->in.cf_height);
+  ctx->supporting_planes_empty = nullptr;
+  const float cell = (float)ctx->in.cell;
+  const float cell_merge_dist_sq = cell * cell * merge_dist_factor * merge_dist_factor;
+  // per-surfel decision words and cells live in accum rows 0 and 1 (scratch by contract, B/kernels.cuh:78-90); the decision words
+  // start cleared: an insert sweep reads them for surfels no decide sweep of this batch has visited
+  uint32_t* flags = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)kSurfelAccum0 * surfels->pitch_bytes);
+  uint32_t* cell_of = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)(kSurfelAccum0 + 1) * surfels->pitch_bytes);
+  HIP_TRY(hipMemsetAsync(flags, 0, sizeof(uint32_t) * (size_t)surfels->surfels_size, st));
+  uint32_t* counter = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 3;   // the deferred count of bahip_take_merged_count
+  const SurfelsView s = make_view(surfels);
+  std::vector<KfEntry> entries((size_t)num_frames);
+  std::vector<LifecycleCull> culls((size_t)num_frames);
+  for (int j = 0; j <= num_frames; ++j) {
+    if (j < num_frames) {
+      // (here, not up front: frames handed over without BA planes share ONE packing slot of the context, re-packed on the stream by
+      // make_entry -- behind keyframe j - 1's decide sweep, the last reader of the previous packing; an apply sweep reads no image)
+      if (entry_of(j, &entries[j])) return 1;
+      culls[j] = lifecycle_cull_for(ctx, surfels, entries[j].pose.F);
+    }
+    // [apply of keyframe j - 1] beside [insert of keyframe j]
+    launch_merge_apply_insert(st, ctx->in, j > 0 ? &entries[j - 1] : nullptr, j < num_frames ? &entries[j] : nullptr, s, flags, cell_of,
+                              sup[(j + 1) & 1], sup[j & 1], counter, j > 0 ? culls[j - 1] : LifecycleCull(), j < num_frames ? culls[j] : LifecycleCull());
+    CHECK_LAUNCH();
+    if (j < num_frames) {
+      launch_merge_decide(st, ctx->in, entries[j], s, sup[j & 1], cell_merge_dist_sq, kCosNormalCompat, flags, cell_of, culls[j]);
+      CHECK_LAUNCH();
+    }
+  }
+  ctx->supporting_planes_empty = sup[0].b[0];   // (every apply sweep left its set empty)
+  return 0;
+}
+
 int bahip_merge_surfels_for_keyframes(bahip_context* ctx, float merge_dist_factor, const bahip_frame* frames, const float* frame_T_global_3x4,
                                       int num_frames, const bahip_surfels* surfels, uint32_t* const* supporting, uint32_t supporting_pitch,
                                       uint32_t* merged_count_out) {
-  REQUIRE_NO_KF_SHARDING("bahip_merge_surfels_for_keyframes");
+  // (a rank cannot tell from a bahip_frame which keyframe, and so which rank, it is)
+  REQUIRE(!kf_sharded(ctx), "bahip_merge_surfels_for_keyframes is not available under keyframe sharding (a frame does not say which rank owns it): "
+                            "use bahip_merge_surfels_for_bound_keyframes inside a lifecycle batch that knows its keyframes");
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
   REQUIRE(num_frames >= 0 && (num_frames == 0 || (frames != nullptr && frame_T_global_3x4 != nullptr)) && surfels != nullptr,
           "bahip_merge_surfels_for_keyframes: NULL argument");
   SupportingView sup[2];
   REQUIRE(supporting_view(supporting, supporting_pitch, &sup[0]) == 0, "supporting-surfel planes missing");
   if (merged_count_out) *merged_count_out = 0;
-  hipStream_t st = ctx->stream;
-  // By cell lists (round 6; kernels_lifecycle.hip: merge_pairs_kernel): when the open lifecycle batch knows every frame of this call and
-  // the frames' BA planes can all be held at once (the association sweep reads them together), the associated (surfel, frame) pairs are
-  // grouped by (frame, cell) up front and each frame costs ONE launch of one thread per pair.
+  // By cell lists when the open lifecycle batch knows every frame of this call and the frames' BA planes can all be held at once (the
+  // association sweep reads them together).
   bool by_cells = false;
   if (g_merge_cells_enabled && num_frames > 0 && surfels->surfels_size > 0) {
     const bool bounds_valid = ctx->lifecycle_bounds_tiles != 0 && ctx->lifecycle_bounds_data == surfels->data &&
@@ -147,104 +303,68 @@ int bahip_merge_surfels_for_keyframes(bahip_context* ctx, float merge_dist_facto
       positions += (uint64_t)table[j].list_count + tail;
       max_positions = std::max(max_positions, table[j].list_count + tail);
     }
-    const size_t cells = (size_t)ctx->in.cf_width * (size_t)ctx->in.cf_height;
-    const size_t entries = (size_t)num_frames * cells + 1;
-    if (known && positions * 64 < ((uint64_t)1 << 31) && entries < ((size_t)1 << 31)) {
-      auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-      const size_t sweep = 64 * (size_t)positions;   // lanes of all sweep positions: an upper bound of the pairs
-      const size_t table_bytes = align(sizeof(MergeBatchFrame) * (size_t)num_frames), entry_bytes = align(sizeof(uint32_t) * entries),
-                   word_bytes = align(sizeof(uint32_t) * sweep), first_bytes = align(sizeof(uint32_t) * ((size_t)num_frames + 1)),
-                   temp_bytes = align(merge_batch_scan_temp_bytes(entries));
-      const size_t need = table_bytes + 2 * entry_bytes + 3 * word_bytes + 2 * word_bytes + first_bytes + temp_bytes;
-      if (need > ctx->merge_batch_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        hipFree(ctx->dev_merge_batch); ctx->dev_merge_batch = nullptr; ctx->merge_batch_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->dev_merge_batch, need + need / 4));
-        ctx->merge_batch_bytes = need + need / 4;
-      }
-      char* p = static_cast<char*>(ctx->dev_merge_batch);
-      MergeBatchFrame* dev_table = reinterpret_cast<MergeBatchFrame*>(p); p += table_bytes;
-      uint32_t* counts = reinterpret_cast<uint32_t*>(p); p += entry_bytes;
-      uint32_t* offsets = reinterpret_cast<uint32_t*>(p); p += entry_bytes;
-      uint32_t* pair_cells = reinterpret_cast<uint32_t*>(p); p += word_bytes;
-      uint32_t* pair_ranks = reinterpret_cast<uint32_t*>(p); p += word_bytes;
-      uint32_t* members = reinterpret_cast<uint32_t*>(p); p += word_bytes;
-      void* member_cell = p; p += 2 * word_bytes;
-      uint32_t* frame_first = reinterpret_cast<uint32_t*>(p); p += first_bytes;
-      void* scan_temp = p;
-      HIP_TRY(hipMemcpyAsync(dev_table, table.data(), sizeof(MergeBatchFrame) * (size_t)num_frames, hipMemcpyHostToDevice, st));
-      const SurfelsView s = make_view(surfels);
-      HIP_TRY(launch_merge_batch_lists(st, ctx->in, dev_table, num_frames, max_positions, s, ctx->dev_lifecycle_lists, bounded_tiles, counts, offsets, pair_cells,
-                                       pair_ranks, members, member_cell, frame_first, scan_temp, temp_bytes));
-      // per-surfel words "deleted at step" in accum row 0 (scratch by contract, B/kernels.cuh:78-90): ~0 = not deleted by this batch
-      uint32_t* deleted_at = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)kSurfelAccum0 * surfels->pitch_bytes);
-      HIP_TRY(hipMemsetAsync(deleted_at, 0xff, sizeof(uint32_t) * (size_t)surfels->surfels_size, st));
-      std::vector<uint32_t> first((size_t)num_frames + 1);
-      HIP_TRY(hipMemcpyAsync(first.data(), frame_first, sizeof(uint32_t) * first.size(), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));   // `table` is pageable and goes out of scope; the grids below come from `first`
-      const float cell = (float)ctx->in.cell;
-      const float cell_merge_dist_sq = cell * cell * merge_dist_factor * merge_dist_factor;
-      uint32_t* counter = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 3;   // the deferred count of bahip_take_merged_count
-      for (int j = 0; j < num_frames; ++j) {
-        launch_merge_pairs(st, s, members, member_cell, first[(size_t)j], first[(size_t)j + 1], (uint32_t)j, deleted_at, cell_merge_dist_sq,
-                           kCosNormalCompat);
-        CHECK_LAUNCH();
-      }
-      launch_merge_batch_apply(st, s, deleted_at, counter);
-      CHECK_LAUNCH();
-      // (the planes are not used; the batch's contract is that they end empty)
-      if (ctx->supporting_planes_empty != sup[0].b[0]) launch_supporting_fill(st, sup[0], ctx->in.cf_width, ctx->in.cf_height);
-      ctx->supporting_planes_empty = sup[0].b[0];
-      by_cells = true;
-      ++g_merge_cells_batches;
-    }
+    if (known && merge_by_cell_lists(ctx, table, nullptr, positions, max_positions, merge_dist_factor, surfels, sup[0], &by_cells)) return 1;
   }
   if (!by_cells && num_frames > 0 && surfels->surfels_size > 0) {
-    // the second set of planes: same pitch, the sparse-cell region's rows
-    const size_t plane_bytes = (size_t)supporting_pitch * (size_t)ctx->in.cf_height;
-    if (plane_bytes > ctx->merge_planes_bytes) {
-      for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) {
-        hipFree(ctx->merge_planes[b]);
-        ctx->merge_planes[b] = nullptr;
-      }
-      ctx->merge_planes_bytes = 0;
-      for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) HIP_TRY(hipMalloc(&ctx->merge_planes[b], plane_bytes));
-      ctx->merge_planes_bytes = plane_bytes;
+    auto entry_of = [&](int j, KfEntry* e) {
+      if (make_entry(ctx, frames[j], 0, e)) return 1;
+      memcpy(e->pose.F, frame_T_global_3x4 + 12 * (size_t)j, 12 * sizeof(float));
+      return 0;
+    };
+    if (merge_pipelined(ctx, num_frames, entry_of, merge_dist_factor, surfels, sup, supporting_pitch)) return 1;
+  }
+  if (merged_count_out) return bahip_take_merged_count(ctx, merged_count_out);
+  return 0;
+}
+
+// The same merges for bound keyframes, named by index: their packed entries and poses (bahip_set_keyframes).  Under keyframe sharding the
+// batch must know its keyframes (bahip_lifecycle_batch_set_keyframes): it runs by cell lists, each rank sweeping the keyframes it owns.
+int bahip_merge_surfels_for_bound_keyframes(bahip_context* ctx, float merge_dist_factor, const int* keyframe_indices, int num_keyframes,
+                                            const bahip_surfels* surfels, uint32_t* const* supporting, uint32_t supporting_pitch,
+                                            uint32_t* merged_count_out) {
+  REQUIRE_KF_TRANSPORT();
+  REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
+  REQUIRE(num_keyframes >= 0 && (num_keyframes == 0 || keyframe_indices != nullptr) && surfels != nullptr,
+          "bahip_merge_surfels_for_bound_keyframes: NULL argument");
+  SupportingView sup[2];
+  REQUIRE(supporting_view(supporting, supporting_pitch, &sup[0]) == 0, "supporting-surfel planes missing");
+  for (int j = 0; j < num_keyframes; ++j) REQUIRE(keyframe_indices[j] >= 0 && keyframe_indices[j] < ctx->num_kfs, "keyframe index out of range");
+  if (merged_count_out) *merged_count_out = 0;
+  const bool sharded = kf_sharded(ctx);
+  bool by_cells = false;
+  if ((g_merge_cells_enabled || sharded) && num_keyframes > 0 && surfels->surfels_size > 0) {
+    const bool bounds_valid = ctx->lifecycle_bounds_tiles != 0 && ctx->lifecycle_bounds_data == surfels->data &&
+                              (uint64_t)ctx->lifecycle_bounds_tiles * 64 <= surfels->surfels_size && !ctx->lifecycle_list_counts.empty();
+    const uint32_t bounded_tiles = ctx->lifecycle_bounds_tiles;
+    const uint32_t all_tiles = (surfels->surfels_size + 63u) / 64u, tail = all_tiles > bounded_tiles ? all_tiles - bounded_tiles : 0u;
+    std::vector<MergeBatchFrame> table((size_t)num_keyframes);
+    std::vector<char> owned((size_t)num_keyframes);
+    bool known = bounds_valid;
+    uint64_t positions = 0;
+    uint32_t max_positions = 0;
+    for (int j = 0; j < num_keyframes && known; ++j) {
+      const KfEntry& e = ctx->host_kfs[keyframe_indices[j]];
+      const size_t listed = ctx->lifecycle_list_counts.size();
+      size_t f = 0;
+      while (f < listed && memcmp(&ctx->lifecycle_frames[12 * f], e.pose.F, 12 * sizeof(float)) != 0) ++f;
+      if (f == listed) { known = false; break; }
+      table[j].entry = e;
+      table[j].list_offset = ctx->lifecycle_list_offsets[f];
+      table[j].list_count = ctx->lifecycle_list_counts[f];
+      table[j].pair_offset = (uint32_t)positions;
+      table[j].pad_ = 0;
+      owned[j] = kf_owned(ctx, keyframe_indices[j]) ? 1 : 0;
+      positions += (uint64_t)table[j].list_count + tail;
+      max_positions = std::max(max_positions, table[j].list_count + tail);
     }
-    for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) sup[1].b[b] = ctx->merge_planes[b];
-    sup[1].pitch = supporting_pitch;
-    if (ctx->supporting_planes_empty != sup[0].b[0]) launch_supporting_fill(st, sup[0], ctx->in.cf_width, ctx->in.cf_height);
-    launch_supporting_fill(st, sup[1], ctx->in.cf_width, ctx->in.cf_height);
-    ctx->supporting_planes_empty = nullptr;
-    const float cell = (float)ctx->in.cell;
-    const float cell_merge_dist_sq = cell * cell * merge_dist_factor * merge_dist_factor;
-    // per-surfel decision words and cells live in accum rows 0 and 1 (scratch by contract, B/kernels.cuh:78-90); the decision words
-    // start cleared: an insert sweep reads them for surfels no decide sweep of this batch has visited
-    uint32_t* flags = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)kSurfelAccum0 * surfels->pitch_bytes);
-    uint32_t* cell_of = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)(kSurfelAccum0 + 1) * surfels->pitch_bytes);
-    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(uint32_t) * (size_t)surfels->surfels_size, st));
-    uint32_t* counter = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 3;   // the deferred count of bahip_take_merged_count
-    const SurfelsView s = make_view(surfels);
-    std::vector<KfEntry> entries((size_t)num_frames);
-    std::vector<LifecycleCull> culls((size_t)num_frames);
-    for (int j = 0; j <= num_frames; ++j) {
-      if (j < num_frames) {
-        // (here, not up front: frames handed over without BA planes share ONE packing slot of the context, re-packed on the stream by
-        // make_entry -- behind keyframe j - 1's decide sweep, the last reader of the previous packing; an apply sweep reads no image)
-        if (make_entry(ctx, frames[j], 0, &entries[j])) return 1;
-        memcpy(entries[j].pose.F, frame_T_global_3x4 + 12 * (size_t)j, 12 * sizeof(float));
-        culls[j] = lifecycle_cull_for(ctx, surfels, entries[j].pose.F);
-      }
-      // [apply of keyframe j - 1] beside [insert of keyframe j]
-      launch_merge_apply_insert(st, ctx->in, j > 0 ? &entries[j - 1] : nullptr, j < num_frames ? &entries[j] : nullptr, s, flags, cell_of,
-                                sup[(j + 1) & 1], sup[j & 1], counter, j > 0 ? culls[j - 1] : LifecycleCull(), j < num_frames ? culls[j] : LifecycleCull());
-      CHECK_LAUNCH();
-      if (j < num_frames) {
-        launch_merge_decide(st, ctx->in, entries[j], s, sup[j & 1], cell_merge_dist_sq, kCosNormalCompat, flags, cell_of, culls[j]);
-        CHECK_LAUNCH();
-      }
-    }
-    ctx->supporting_planes_empty = sup[0].b[0];   // (every apply sweep left its set empty)
+    REQUIRE(known || !sharded, "keyframe sharding: bahip_merge_surfels_for_bound_keyframes needs an open lifecycle batch that knows its keyframes "
+                               "(bahip_lifecycle_batch_begin, bahip_lifecycle_batch_set_keyframes)");
+    if (known && merge_by_cell_lists(ctx, table, sharded ? &owned : nullptr, positions, max_positions, merge_dist_factor, surfels, sup[0], &by_cells)) return 1;
+    REQUIRE(by_cells || !sharded, "keyframe sharding: the merge batch is too large for its cell lists: split it");
+  }
+  if (!by_cells && num_keyframes > 0 && surfels->surfels_size > 0) {
+    auto entry_of = [&](int j, KfEntry* e) { *e = ctx->host_kfs[keyframe_indices[j]]; return 0; };
+    if (merge_pipelined(ctx, num_keyframes, entry_of, merge_dist_factor, surfels, sup, supporting_pitch)) return 1;
   }
   if (merged_count_out) return bahip_take_merged_count(ctx, merged_count_out);
   return 0;
@@ -405,6 +525,158 @@ int bahip_create_surfels_for_keyframe(bahip_context* ctx, int keyframe_index, in
   return 0;
 }
 
+// A creation batch under keyframe sharding.  Every keyframe of the batch takes the chain (create_chain_kernel), the last one and a batch
+// of one included; the parts that read images are dealt out by owner (keyframe k lives on rank k % world) and exchanged as zero-filled
+// partials or integer counts, the order-dependent chain runs on every rank:
+//   owner of j: occupancy row j at the batch's begin, candidates row j, the candidates' raw words      -> exchange (rows of all j)
+//   every rank: filter counts over the co-visible keyframes it owns                                   -> exchange (integer counts)
+//   every rank: the filter's decision, the scan, the compact list's positions
+//   owner of j: the records of j's candidates, their cells                                            -> exchange (bit patterns)
+//   every rank, per keyframe j: the chain's append; the owner of j + 1 pushes / pulls into row j + 1  -> exchange of row j + 1
+// Occupancy is only tested == 0.  The caller's supporting planes end empty, as a merge batch leaves them.
+static int create_batch_keyframe_sharded(bahip_context* ctx, const int* keyframe_indices, int n, bool filter_counts, bool filter_new_surfels,
+                                         int min_observation_count, const int* covis_offsets, const bahip_surfels* surfels, const SupportingView& sup,
+                                         uint32_t* new_surfel_count_out) {
+  hipStream_t st = ctx->stream;
+  const size_t px = create_padded_count(ctx->in);
+  const size_t cells = (size_t)ctx->in.cf_width * (size_t)ctx->in.cf_height;
+  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  // the items; their visible-tile lists when the open batch knows the keyframes, else every tile is swept
+  std::vector<CreateBatchItem> items((size_t)n);
+  bool known = ctx->lifecycle_bounds_tiles != 0 && ctx->lifecycle_bounds_data == surfels->data &&
+               (uint64_t)ctx->lifecycle_bounds_tiles * 64 <= surfels->surfels_size && !ctx->lifecycle_list_counts.empty();
+  for (int j = 0; j < n && known; ++j) {
+    const float* F = ctx->host_kfs[keyframe_indices[j]].pose.F;
+    const size_t frames = ctx->lifecycle_list_counts.size();
+    size_t f = 0;
+    while (f < frames && memcmp(&ctx->lifecycle_frames[12 * f], F, 12 * sizeof(float)) != 0) ++f;
+    if (f == frames) { known = false; break; }
+    items[j].list_offset = ctx->lifecycle_list_offsets[f];
+    items[j].list_count = ctx->lifecycle_list_counts[f];
+  }
+  for (int j = 0; j < n; ++j) {
+    items[j].kf_index = keyframe_indices[j];
+    if (!known) { items[j].list_offset = 0; items[j].list_count = 0; }
+    items[j].covis_offset = covis_offsets[j];
+    items[j].n_covis = covis_offsets[j + 1] - covis_offsets[j];
+  }
+  const uint32_t bounded_tiles = known ? ctx->lifecycle_bounds_tiles : 0u;
+  const uint32_t all_tiles = (surfels->surfels_size + 63u) / 64u, tail = all_tiles > bounded_tiles ? all_tiles - bounded_tiles : 0u;
+  // one block: occupancy rows (a multiple of 8 bytes each: a row is exchanged on its own), candidates, their raw words, the filter counts,
+  // the scan, the compact list's cells followed by its records, the items, two words of scratch, the library's temporary
+  const size_t N = (size_t)n, occ_stride = align(cells), columns = (N * cells + 63) & ~(size_t)63;
+  const size_t occupancy_bytes = N * occ_stride, candidates_bytes = align(N * px), cand_px_bytes = align(sizeof(uint32_t) * N * cells),
+               counts_bytes = align(sizeof(uint32_t) * 2 * N * cells), scan_bytes = align(sizeof(uint32_t) * N * px),
+               list_bytes = align(sizeof(uint32_t) * columns) + align(sizeof(float) * columns * kSurfelAccum0),
+               items_bytes = align(sizeof(CreateBatchItem) * N), scan_temp_bytes = create_batch_scan_temp_bytes(N * px);
+  const size_t need = occupancy_bytes + candidates_bytes + cand_px_bytes + counts_bytes + scan_bytes + list_bytes + items_bytes + align(2 * sizeof(uint32_t)) +
+                      align(scan_temp_bytes);
+  REQUIRE(need <= ((size_t)16 << 30) && sizeof(float) * columns * (kSurfelAccum0 + 1) < ((size_t)1 << 32) && N * px < ((size_t)1 << 31),
+          "keyframe sharding: the creation batch is too large for one pass: split it");
+  if (need > ctx->create_batch_bytes) {
+    HIP_TRY(hipStreamSynchronize(st));
+    hipFree(ctx->dev_create_batch); ctx->dev_create_batch = nullptr; ctx->create_batch_bytes = 0;
+    HIP_TRY(hipMalloc(&ctx->dev_create_batch, need + need / 4));
+    ctx->create_batch_bytes = need + need / 4;
+  }
+  char* p = static_cast<char*>(ctx->dev_create_batch);
+  uint8_t* occupancy = reinterpret_cast<uint8_t*>(p); p += occupancy_bytes;
+  uint8_t* candidates = reinterpret_cast<uint8_t*>(p); p += candidates_bytes;
+  uint32_t* cand_px = reinterpret_cast<uint32_t*>(p); p += cand_px_bytes;
+  void* filter_counts_buf = p; p += counts_bytes;
+  uint32_t* scan = reinterpret_cast<uint32_t*>(p); p += scan_bytes;
+  uint32_t* cand_cell = reinterpret_cast<uint32_t*>(p); p += list_bytes;
+  CreateBatchItem* dev_items = reinterpret_cast<CreateBatchItem*>(p); p += items_bytes;
+  uint32_t* scratch2 = reinterpret_cast<uint32_t*>(p); p += align(2 * sizeof(uint32_t));
+  void* scan_temp = p;
+  HIP_TRY(hipMemcpyAsync(dev_items, items.data(), N * sizeof(CreateBatchItem), hipMemcpyHostToDevice, st));
+  // ---- what the owners compute from their images: occupancy at the batch's begin, candidates, their raw words
+  const size_t span_a = occupancy_bytes + candidates_bytes + cand_px_bytes;
+  HIP_TRY(hipMemsetAsync(occupancy, 0, span_a, st));
+  const SurfelsView cloud_at_begin = make_view(surfels);
+  for (int j = 0; j < n; ++j)
+    if (kf_owned(ctx, keyframe_indices[j]))
+      launch_create_batch_item_candidates(st, ctx->in, ctx->dev_kfs, dev_items + j, items[j].list_count + tail, cloud_at_begin, ctx->dev_lifecycle_lists,
+                                          bounded_tiles, occupancy + (size_t)j * occ_stride, candidates + (size_t)j * px, cand_px + (size_t)j * cells,
+                                          ctx->host_kfs[keyframe_indices[j]]);
+  CHECK_LAUNCH();
+  if (kf_exchange(ctx, occupancy, span_a, "the creation batch's candidates")) return 1;
+  // ---- the outlier filter: counts over this rank's co-visible keyframes, summed; the decision on every rank
+  if (filter_new_surfels) {
+    HIP_TRY(hipMemsetAsync(filter_counts_buf, 0, counts_bytes, st));
+    if (filter_counts) {
+      launch_create_batch_filter_count(st, ctx->in, ctx->dev_kfs, dev_items, n, ctx->dev_covis, ctx->dev_covis_T, candidates, cand_px, filter_counts_buf,
+                                       ctx->kf_rank, ctx->kf_world);
+      CHECK_LAUNCH();
+      if (kf_exchange(ctx, filter_counts_buf, counts_bytes, "the creation batch's filter counts")) return 1;
+    }
+    launch_create_batch_filter_decide(st, ctx->in, n, filter_counts_buf, min_observation_count, candidates);
+    CHECK_LAUNCH();
+  }
+  // ---- the compact candidate list: first[j] = the list position of keyframe j's first candidate (the inclusive scan's row ends)
+  HIP_TRY(launch_create_batch_scan(st, ctx->in, n, candidates, scan, scan_temp, scan_temp_bytes));
+  std::vector<uint32_t> first(N + 1, 0u);
+  HIP_TRY(hipMemcpy2DAsync(first.data() + 1, sizeof(uint32_t), scan + (px - 1), sizeof(uint32_t) * px, sizeof(uint32_t), N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));   // `items` is pageable and goes out of scope; the chain's grids come from `first`
+  const size_t total = first[N], total_al = (total + 63) & ~(size_t)63;
+  // ---- the owners' records: the list's cells, then kSurfelAccum0 rows of total_al columns, one exchange
+  SurfelsView records;
+  records.data = reinterpret_cast<float*>(cand_cell + total_al); records.pitch = (uint32_t)(sizeof(float) * total_al); records.active = nullptr;
+  records.size = (uint32_t)total_al;
+  if (total) {
+    HIP_TRY(hipMemsetAsync(cand_cell, 0, sizeof(uint32_t) * total_al * (kSurfelAccum0 + 1), st));
+    for (int j = 0; j < n; ++j)
+      if (kf_owned(ctx, keyframe_indices[j]) && first[(size_t)j + 1] > first[(size_t)j])
+        launch_create_batch_item_records(st, ctx->in, ctx->dev_kfs, dev_items + j, candidates + (size_t)j * px, scan + (size_t)j * px, cand_cell, records, scratch2);
+    CHECK_LAUNCH();
+    if (kf_exchange(ctx, cand_cell, sizeof(uint32_t) * total_al * (kSurfelAccum0 + 1), "the creation batch's records")) return 1;
+  }
+  // ---- the chain, keyframe by keyframe (the size cells and the appends' scratch as bahip_create_surfels_for_keyframes sets them up)
+  uint32_t* size_cell[2] = {reinterpret_cast<uint32_t*>(ctx->dev_counter) + 4, reinterpret_cast<uint32_t*>(ctx->dev_counter) + 5};
+  uint32_t* exceeded_on_device = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 6;
+  ctx->pinned_i[2] = (int)surfels->surfels_size; ctx->pinned_i[3] = (int)surfels->surfels_size; ctx->pinned_i[4] = 0;
+  HIP_TRY(hipMemcpyAsync(size_cell[0], ctx->pinned_i + 2, 3 * sizeof(int), hipMemcpyHostToDevice, st));
+  const int groups = create_append_groups();
+  REQUIRE((size_t)groups <= px, "bahip_create_surfels_for_keyframes: flag sequence shorter than the append's scratch");
+  uint32_t* group_words = ctx->dev_indices;
+  HIP_TRY(hipMemsetAsync(group_words, 0, sizeof(uint32_t) * (size_t)groups, st));
+  bahip_surfels whole = *surfels;
+  whole.surfels_size = surfels->capacity;   // (the chain addresses rows by index; sizes are read on the device)
+  const SurfelsView s = make_view(&whole);
+  if (total) {
+    for (int j = 0; j < n; ++j) {
+      const uint32_t tag = (uint32_t)(j % 255) + 1u;
+      if (j > 0 && tag == 1u) HIP_TRY(hipMemsetAsync(group_words, 0, sizeof(uint32_t) * (size_t)groups, st));   // the tags start over
+      const bool has_next = j + 1 < n, next_owned = has_next && kf_owned(ctx, keyframe_indices[j + 1]);
+      uint8_t* next_row = has_next ? occupancy + (size_t)(j + 1) * occ_stride : nullptr;
+      const uint32_t appended_bound = (uint32_t)std::min<uint64_t>((uint64_t)surfels->capacity - surfels->surfels_size, (uint64_t)first[(size_t)j]);
+      launch_create_chain(st, ctx->in, next_owned ? &ctx->host_kfs[keyframe_indices[j + 1]] : nullptr, cand_cell, records, first[(size_t)j], first[(size_t)j + 1],
+                          occupancy + (size_t)j * occ_stride, next_owned ? next_row : nullptr, s, (uint32_t)surfels->surfels_size, size_cell[j & 1],
+                          size_cell[(j & 1) ^ 1], (uint32_t)surfels->capacity, exceeded_on_device, group_words, tag, appended_bound);
+      CHECK_LAUNCH();
+      if (has_next) {
+        // occupancy of keyframe j + 1 as the owner's push and pull completed it; the other ranks contribute zeros
+        if (!next_owned) HIP_TRY(hipMemsetAsync(next_row, 0, occ_stride, st));
+        if (kf_exchange(ctx, next_row, occ_stride, "the creation chain's occupancy of the next keyframe")) return 1;
+      }
+    }
+  }
+  ++g_creation_chain_batches;
+  // the caller's supporting planes end empty
+  if (ctx->supporting_planes_empty != sup.b[0]) launch_supporting_fill(st, sup, ctx->in.cf_width, ctx->in.cf_height);
+  ctx->supporting_planes_empty = sup.b[0];
+  CHECK_LAUNCH();
+  HIP_TRY(hipMemcpyAsync(ctx->pinned_i + 2, size_cell[total ? (n & 1) : 0], sizeof(int), hipMemcpyDeviceToHost, st));   // (no candidate: no chain)
+  HIP_TRY(hipMemcpyAsync(ctx->pinned_i + 3, exceeded_on_device, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *new_surfel_count_out = (uint32_t)ctx->pinned_i[2] - surfels->surfels_size;
+  if (ctx->pinned_i[3]) {
+    g_last_error = "Maximum surfel count exceeded! Retry with a higher max_surfel_count.";
+    ctx->capacity_exceeded = true;
+  }
+  return 0;
+}
+
 // A batch of keyframes creating surfels, one after the other as the reference does (each sees what the ones before it appended,
 // B/direct_ba_alternating.cc:389-425), but without the host in between: the cloud's size lives on the device for the duration of
 // the batch, the co-visibility lists and relative poses of all keyframes go up front in one copy, and the host reads the final size
@@ -413,7 +685,7 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
                                        int min_observation_count, const int* covis_offsets, const int* covis_indices,
                                        const bahip_surfels* surfels, uint32_t* const* supporting, uint32_t supporting_pitch,
                                        uint32_t* new_surfel_count_out) {
-  REQUIRE_NO_KF_SHARDING("bahip_create_surfels_for_keyframes");
+  REQUIRE_KF_TRANSPORT();
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
   REQUIRE(keyframe_indices != nullptr && covis_offsets != nullptr && new_surfel_count_out != nullptr && num_keyframes >= 0,
           "bahip_create_surfels_for_keyframes: NULL argument");
@@ -458,6 +730,9 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
     HIP_TRY(hipMemcpyAsync(ctx->dev_covis_T, rel.data(), sizeof(float) * 12 * (size_t)total_covis, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));   // `rel` is pageable and goes out of scope
   }
+  if (kf_sharded(ctx))
+    return create_batch_keyframe_sharded(ctx, keyframe_indices, num_keyframes, filter_new_surfels != 0 && total_covis > 0, filter_new_surfels != 0,
+                                         min_observation_count, covis_offsets, surfels, sup, new_surfel_count_out);
   // The cloud's size lives on the device between the keyframes of the batch, in TWO cells: a keyframe's launches read one, its append
   // writes the other (kernels_lifecycle.hip: create_append_fused_kernel); [6] = the sticky "capacity exceeded" flag.
   uint32_t* size_cell[2] = {reinterpret_cast<uint32_t*>(ctx->dev_counter) + 4, reinterpret_cast<uint32_t*>(ctx->dev_counter) + 5};
@@ -590,10 +865,29 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
 
 int bahip_delete_surfels_and_update_radii(bahip_context* ctx, int min_observation_count, const bahip_surfels* surfels,
                                           uint32_t* deleted_count_out) {
-  REQUIRE_NO_KF_SHARDING("bahip_delete_surfels_and_update_radii");
+  REQUIRE_KF_TRANSPORT();
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
   *deleted_count_out = 0;
   if (surfels->surfels_size == 0) return 0;
+  if (kf_sharded(ctx)) {
+    // delete_update_kernel cut at its sums over the keyframes: this rank's counts and minimum radius (into the context's scratch, not
+    // the surfels' rows), summed over the ranks, then the decision on every rank
+    const SurfelsView v = make_view(surfels);
+    const size_t stride = ((size_t)v.size + 63) & ~(size_t)63, words = (2 + (size_t)ctx->kf_world) * stride;
+    if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, words, 0, "the partial sums of the deletion")) return 1;
+    uint32_t* partial = reinterpret_cast<uint32_t*>(ctx->kf_partials);
+    HIP_TRY(hipMemsetAsync(partial, 0, sizeof(uint32_t) * words, ctx->stream));
+    launch_delete_partial(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, v, ctx->kf_rank, ctx->kf_world, partial, (uint32_t)stride);
+    CHECK_LAUNCH();
+    if (kf_exchange(ctx, partial, sizeof(uint32_t) * words, "the deletion's observation counts and radii")) return 1;
+    HIP_TRY(hipMemsetAsync(ctx->dev_counter, 0, sizeof(int), ctx->stream));
+    launch_delete_decide(ctx->stream, v, partial, (uint32_t)stride, ctx->kf_world, min_observation_count, reinterpret_cast<uint32_t*>(ctx->dev_counter));
+    CHECK_LAUNCH();
+    HIP_TRY(hipMemcpyAsync(ctx->pinned_i, ctx->dev_counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *deleted_count_out = (uint32_t)ctx->pinned_i[0];
+    return 0;
+  }
   HIP_TRY(hipMemsetAsync(ctx->dev_counter, 0, sizeof(int), ctx->stream));
   launch_delete_update(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels), min_observation_count,
                        reinterpret_cast<uint32_t*>(ctx->dev_counter));

@@ -802,6 +802,105 @@ create_chain_kernel(Intrinsics in, KfEntry next_frame, const uint32_t* __restric
   }
 }
 
+// ---- a creation batch under keyframe sharding (capi_lifecycle.hip: create_batch_keyframe_sharded) -----------------------------------
+// A rank holds the images of its own keyframes only.  The outlier filter of a candidate of keyframe j reads j's depth and normal at
+// the candidate pixel (create_filter_body) and the co-visible keyframes' images: the owner of j exports the two raw words of every
+// candidate (one u32 per (keyframe, cell): depth << 16 | normal), every rank counts the observations and violations over the co-visible
+// keyframes IT owns, the integer counts are summed over the ranks and every rank decides with create_filter_body's test.
+__global__ void __launch_bounds__(kLcBlock)
+create_batch_export_kernel(Intrinsics in, KfEntry frame, const uint8_t* __restrict__ candidates /* the keyframe's row */, int padded_count,
+                           uint32_t* __restrict__ cand_px /* the keyframe's row, one word per cell, zeroed */) {
+  const int seq = blockIdx.x * kLcBlock + threadIdx.x;
+  int x, y;
+  if (seq >= padded_count || candidates[seq] != 1 || !tile_xy(in, (size_t)seq, &x, &y)) return;
+  const uint32_t depth = pitched_load(frame.depth, frame.depth_pitch, y, x), normal = pitched_load(frame.normals, frame.normals_pitch, y, x);
+  cand_px[(size_t)(y / in.cell) * (size_t)in.cf_width + (size_t)(x / in.cell)] = (depth << 16) | normal;
+}
+__global__ void __launch_bounds__(kLcBlock)
+create_batch_filter_count_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, const CreateBatchItem* __restrict__ items, const int* __restrict__ covis,
+                                 const float* __restrict__ covis_T_frame, int padded_count, const uint8_t* __restrict__ candidates, const uint32_t* __restrict__ cand_px,
+                                 size_t cells, uint2* __restrict__ counts /* [n][cells], zeroed */, int kf_rank, int kf_world) {
+  const CreateBatchItem item = items[blockIdx.y];
+  const int seq = blockIdx.x * kLcBlock + threadIdx.x;
+  int x, y;
+  if (seq >= padded_count || candidates[(size_t)blockIdx.y * (size_t)padded_count + seq] != 1 || !tile_xy(in, (size_t)seq, &x, &y)) return;
+  const size_t cell = (size_t)blockIdx.y * cells + (size_t)(y / in.cell) * (size_t)in.cf_width + (size_t)(x / in.cell);
+  const uint32_t word = cand_px[cell];
+  // create_filter_body's candidate point and normal, from the owner's raw words
+  const float cd = raw_to_calibrated_depth(in.a, cfactor_at(in, x, y), in.raw_to_float_depth, (uint16_t)(word >> 16));
+  const Vec3 input_pos = unproject(in, x, y, cd);
+  const Vec3 m = unpack_normal8((uint16_t)(word & 0xffffu));
+  const int* cv = covis + item.covis_offset;
+  const float* cT = covis_T_frame + 12 * (size_t)item.covis_offset;
+  uint32_t obs = 0, vio = 0;
+  for (int c = 0; c < item.n_covis; ++c) {
+    if ((cv[c] & (kf_world - 1)) != kf_rank) continue;
+    const uint32_t r = create_filter_pair(in, kfs, cv, cT, c, input_pos, m);
+    obs += r & 1u;
+    vio += r >> 1;
+  }
+  counts[cell] = make_uint2(obs, vio);
+}
+// ... and, on every rank from the summed counts, create_filter_body's decision (the keyframe's own observation is the 1)
+__global__ void __launch_bounds__(kLcBlock)
+create_batch_filter_decide_kernel(Intrinsics in, int padded_count, size_t cells, const uint2* __restrict__ counts, int min_observation_count,
+                                  uint8_t* __restrict__ candidates) {
+  const int seq = blockIdx.x * kLcBlock + threadIdx.x;
+  int x, y;
+  uint8_t* flag = candidates + (size_t)blockIdx.y * (size_t)padded_count + seq;
+  if (seq >= padded_count || *flag != 1 || !tile_xy(in, (size_t)seq, &x, &y)) return;
+  const uint2 c = counts[(size_t)blockIdx.y * cells + (size_t)(y / in.cell) * (size_t)in.cf_width + (size_t)(x / in.cell)];
+  const uint32_t observations = 1u + c.x, violations = c.y;
+  if (observations < (uint32_t)min_observation_count || violations > observations) *flag = 0;
+}
+
+// ---- deletion + radius update under keyframe sharding: delete_update_kernel cut at its sums over the keyframes ------------------------
+// partial rows of `stride` words: [0] observations, [1] violations (integer counts over this rank's keyframes), [2 + rank] the minimum
+// radius over them as binary32 bits (the other ranks' rows stay zero); the rows are summed over the ranks, then delete_decide_kernel
+// takes the minimum of the world rows -- fminf over one set of radii, whatever the grouping, is the same value.
+__global__ void __launch_bounds__(kLcBlock)
+delete_partial_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s, int kf_rank, int kf_world,
+                      uint32_t* __restrict__ partial, uint32_t stride) {
+  const uint32_t i = blockIdx.x * kLcBlock + threadIdx.x;
+  if (i >= s.size) return;
+  const Vec3 gp = surfel_position(s, i);
+  const Vec3 gn = surfel_normal(s, i);
+  uint32_t obs = 0, viol = 0;
+  float min_r = __builtin_huge_valf();
+  for (int k = kf_rank; k < num_kfs; k += kf_world) {
+    Assoc r;
+    bool fsv = false;
+    if (project_associate<true>(in, kfs[k].pose.F, kfs[k].geom, gp, gn, &r, &fsv)) {
+      ++obs;
+      min_r = fminf(min_r, __half2float(__ushort_as_half(pitched_load(kfs[k].radius, kfs[k].radius_pitch, r.py, r.px))));
+    } else if (fsv) {
+      ++viol;
+    }
+  }
+  partial[i] = obs;
+  partial[(size_t)stride + i] = viol;
+  partial[(size_t)(2 + kf_rank) * stride + i] = __float_as_uint(min_r);
+}
+__global__ void __launch_bounds__(kLcBlock)
+delete_decide_kernel(SurfelsView s, const uint32_t* __restrict__ partial, uint32_t stride, int kf_world, int min_observation_count,
+                     uint32_t* __restrict__ deleted_count) {
+  const uint32_t i = blockIdx.x * kLcBlock + threadIdx.x;
+  bool newly_deleted = false;
+  if (i < s.size) {
+    const float obs = (float)partial[i], viol = (float)partial[(size_t)stride + i];
+    float min_r = __builtin_huge_valf();
+    for (int r = 0; r < kf_world; ++r) min_r = fminf(min_r, __uint_as_float(partial[(size_t)(2 + r) * stride + i]));
+    s.row(kSurfelAccum0 + 0)[i] = obs; s.row(kSurfelAccum0 + 1)[i] = viol; s.row(kSurfelAccum0 + 2)[i] = min_r;
+    if (obs < (float)min_observation_count || viol > obs) {
+      if (!is_deleted_bits(s.row(kSurfelX)[i])) { s.row(kSurfelX)[i] = __uint_as_float(kDeletedSurfelBits); newly_deleted = true; }
+    } else {
+      s.row(kSurfelRadiusSquared)[i] = min_r;
+    }
+  }
+  const unsigned long long m = __ballot(newly_deleted);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(deleted_count, (uint32_t)__popcll(m));
+}
+
 // ---- deletion + radius update (B/kernel_delete_surfels.cu:42-176), one launch for all keyframes ------
 __global__ void __launch_bounds__(kLcBlock)
 delete_update_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s,
@@ -1070,6 +1169,81 @@ void launch_create_chain(hipStream_t st, const Intrinsics& in, const KfEntry* ne
 void launch_delete_update(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,
                           int min_obs, uint32_t* deleted_count) {
   if (s.size) hipLaunchKernelGGL(delete_update_kernel, dim3(g1(s.size)), dim3(kLcBlock), 0, st, in, kfs, num_kfs, s, min_obs, deleted_count);
+}
+
+// ---- keyframe sharding of the lifecycle ---------------------------------------------------------------------------------------------
+// One frame / item of a batch on its own: the batch kernels index their tables, counts and occupancy rows by blockIdx.y, so a grid of
+// one row over pointers advanced to the frame's row is that frame's part of the whole launch.
+void launch_merge_batch_associate_frame(hipStream_t st, const Intrinsics& in, const MergeBatchFrame* frame, uint32_t positions, const SurfelsView& s,
+                                        const uint32_t* lists, uint32_t bounded_tiles, uint32_t* counts_row, uint32_t* pair_cells, uint32_t* pair_ranks) {
+  const uint32_t cells = (uint32_t)in.cf_width * (uint32_t)in.cf_height;
+  if (positions)
+    hipLaunchKernelGGL(merge_batch_associate_kernel, dim3(std::min<unsigned>(g1(positions * 64u), 2048u), 1), dim3(kLcBlock), 0, st, in, frame, s, lists,
+                       bounded_tiles, counts_row, cells, pair_cells, pair_ranks);
+}
+void launch_merge_batch_fill_frame(hipStream_t st, const Intrinsics& in, const MergeBatchFrame* frame, uint32_t positions, uint32_t surfels_size,
+                                   const uint32_t* lists, uint32_t bounded_tiles, const uint32_t* offsets_row, const uint32_t* pair_cells,
+                                   const uint32_t* pair_ranks, uint32_t* members, void* member_cell) {
+  const uint32_t cells = (uint32_t)in.cf_width * (uint32_t)in.cf_height;
+  if (positions)
+    hipLaunchKernelGGL(merge_batch_fill_kernel, dim3(std::min<unsigned>(g1(positions * 64u), 2048u), 1), dim3(kLcBlock), 0, st, frame, surfels_size, lists,
+                       bounded_tiles, offsets_row, cells, pair_cells, pair_ranks, members, static_cast<uint2*>(member_cell));
+}
+// the scan of the summed counts and the first pair of every frame (launch_merge_batch_lists' middle)
+hipError_t launch_merge_batch_offsets(hipStream_t st, const Intrinsics& in, int num_frames, const uint32_t* counts, uint32_t* offsets, uint32_t* frame_first,
+                                      void* scan_temp, size_t scan_temp_bytes) {
+  const uint32_t cells = (uint32_t)in.cf_width * (uint32_t)in.cf_height;
+  const size_t entries = (size_t)num_frames * cells + 1;
+  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, counts, offsets, (int)entries, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(merge_batch_frame_first_kernel, dim3(g1((uint32_t)num_frames + 1u)), dim3(kLcBlock), 0, st, offsets, cells, (uint32_t)num_frames, frame_first);
+  return hipGetLastError();
+}
+// what the owner of a creation item computes from its images: the occupancy row at the batch's begin, the candidates, their raw words
+void launch_create_batch_item_candidates(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, const CreateBatchItem* item, uint32_t positions,
+                                         const SurfelsView& cloud_at_begin, const uint32_t* lists, uint32_t bounded_tiles, uint8_t* occupancy_row,
+                                         uint8_t* candidates_row, uint32_t* cand_px_row, const KfEntry& frame) {
+  const size_t cells = (size_t)in.cf_width * (size_t)in.cf_height;
+  const int padded = (int)create_padded_count(in);
+  if (cloud_at_begin.size && positions)
+    hipLaunchKernelGGL(create_batch_occupancy_kernel, dim3(std::min<unsigned>(g1(positions * 64u), 1024u), 1), dim3(kLcBlock), 0, st, in, kfs, item,
+                       cloud_at_begin, lists, bounded_tiles, occupancy_row, cells);
+  hipLaunchKernelGGL(create_batch_flag_kernel, dim3(g1((uint32_t)cells), 1), dim3(kLcBlock), 0, st, in, kfs, item, occupancy_row, cells, candidates_row, (size_t)padded);
+  hipLaunchKernelGGL(create_batch_export_kernel, dim3(g1(padded)), dim3(kLcBlock), 0, st, in, frame, candidates_row, padded, cand_px_row);
+}
+void launch_create_batch_filter_count(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, const CreateBatchItem* items, int num_items, const int* covis,
+                                      const float* covis_T_frame, const uint8_t* candidates, const uint32_t* cand_px, void* counts, int kf_rank, int kf_world) {
+  const int padded = (int)create_padded_count(in);
+  const size_t cells = (size_t)in.cf_width * (size_t)in.cf_height;
+  if (num_items > 0)
+    hipLaunchKernelGGL(create_batch_filter_count_kernel, dim3(g1(padded), num_items), dim3(kLcBlock), 0, st, in, kfs, items, covis, covis_T_frame, padded, candidates,
+                       cand_px, cells, static_cast<uint2*>(counts), kf_rank, kf_world);
+}
+void launch_create_batch_filter_decide(hipStream_t st, const Intrinsics& in, int num_items, const void* counts, int min_obs, uint8_t* candidates) {
+  const int padded = (int)create_padded_count(in);
+  const size_t cells = (size_t)in.cf_width * (size_t)in.cf_height;
+  if (num_items > 0)
+    hipLaunchKernelGGL(create_batch_filter_decide_kernel, dim3(g1(padded), num_items), dim3(kLcBlock), 0, st, in, padded, cells, static_cast<const uint2*>(counts),
+                       min_obs, candidates);
+}
+hipError_t launch_create_batch_scan(hipStream_t st, const Intrinsics& in, int num_items, const uint8_t* candidates, uint32_t* scan, void* scan_temp, size_t scan_temp_bytes) {
+  hipcub::TransformInputIterator<uint32_t, U8ToU32, const uint8_t*> it(candidates, U8ToU32());
+  return hipcub::DeviceScan::InclusiveSum(scan_temp, scan_temp_bytes, it, scan, (int)((size_t)num_items * create_padded_count(in)), st);
+}
+// the records of one item (create_batch_records_kernel over the item's rows; first_of_item2: two words of scratch)
+void launch_create_batch_item_records(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, const CreateBatchItem* item, const uint8_t* candidates_row,
+                                      const uint32_t* scan_row, uint32_t* cand_cell, const SurfelsView& records, uint32_t* first_of_item2) {
+  const int padded = (int)create_padded_count(in);
+  hipLaunchKernelGGL(create_batch_records_kernel, dim3(g1(padded), 1), dim3(kLcBlock), 0, st, in, kfs, item, candidates_row, scan_row, padded, cand_cell, records,
+                     first_of_item2);
+}
+// partial: (2 + kf_world) rows of `stride` words, zeroed
+void launch_delete_partial(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, int kf_rank, int kf_world,
+                           uint32_t* partial, uint32_t stride) {
+  if (s.size) hipLaunchKernelGGL(delete_partial_kernel, dim3(g1(s.size)), dim3(kLcBlock), 0, st, in, kfs, num_kfs, s, kf_rank, kf_world, partial, stride);
+}
+void launch_delete_decide(hipStream_t st, const SurfelsView& s, const uint32_t* partial, uint32_t stride, int kf_world, int min_obs, uint32_t* deleted_count) {
+  if (s.size) hipLaunchKernelGGL(delete_decide_kernel, dim3(g1(s.size)), dim3(kLcBlock), 0, st, s, partial, stride, kf_world, min_obs, deleted_count);
 }
 
 // Inclusive scan u8 -> u32 (new surfel indices) and exclusive scan u32 -> u32 (free ranks).

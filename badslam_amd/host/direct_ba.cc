@@ -288,6 +288,7 @@ void DirectBA::CreateSurfelsForKeyframe(hipStream_t stream, bool filter_new_surf
 // 389-425 in their order, the cloud's size on the device in between.
 void DirectBA::CreateSurfelsForKeyframes(hipStream_t stream, bool filter_new_surfels, const vector<u32>& keyframe_ids) {
   if (keyframe_ids.empty()) return;
+  CHECK(batched_creation_ || keyframe_shard_world_ == 1) << "keyframe sharding creates surfels through the batched call only";
   if (!batched_creation_) {
     for (u32 id : keyframe_ids) CreateSurfelsForKeyframe(stream, filter_new_surfels, keyframes_[id]);
     return;
@@ -349,6 +350,22 @@ void DirectBA::MergeForKeyframes(const vector<u32>& keyframe_ids) {
   }
   if (frames.empty()) return;
   LifecycleBatch batch(this);
+  if (keyframe_shard_world_ > 1) {
+    // by bound index: a rank knows which keyframes it owns (the bound poses are the keyframes' current ones: every merge pass follows a
+    // binding of the scene)
+    CHECK(batched_creation_) << "keyframe sharding merges through the batched call only";
+    vector<int> bound;
+    for (u32 id : keyframe_ids)
+      if (keyframes_[id]) bound.push_back(id_to_bound_[id]);
+    uint32_t* sup[kMergeBufferCount];
+    for (int i = 0; i < kMergeBufferCount; ++i) sup[i] = supporting_surfels_[i]->ToCUDA().address();
+    const bahip_surfels s = SurfelsStruct();
+    BAHIP_CHECKED_CALL(bahip_lifecycle_batch_set_keyframes(ctx_, bound.data(), (int)bound.size()));
+    BAHIP_CHECKED_CALL(bahip_merge_surfels_for_bound_keyframes(ctx_, surfel_merge_dist_factor_, bound.data(), (int)bound.size(), &s, sup,
+                                                               (uint32_t)supporting_surfels_[0]->ToCUDA().pitch(), nullptr));
+    TakeDeferredMergeCount();
+    return;
+  }
   BAHIP_CHECKED_CALL(bahip_lifecycle_batch_set_frames(ctx_, frames.data(), (int)(frames.size() / 12)));
   if (batched_creation_) {
     // one call for the batch: two dependent launches per keyframe instead of three (bahip_merge_surfels_for_keyframes)
@@ -413,9 +430,8 @@ void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsi
   }
   last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = 0;
   if (keyframe_shard_world_ > 1)
-    CHECK(!do_surfel_updates && !increase_ba_iteration_count)
-        << "keyframe sharding covers the alternating scheme over poses, geometry and intrinsics and the PCG scheme (SetPCGSumClasses), "
-           "without surfel updates and end tasks (their per-surfel sums run over all keyframes in order): use surfel sharding for the rest";
+    CHECK(batched_creation_ || (!do_surfel_updates && !increase_ba_iteration_count))
+        << "keyframe sharding runs the surfel lifecycle through the batched calls only (SetBatchedCreation(true))";
   if (use_pcg) {
     BundleAdjustmentPCG(stream, optimize_depth_intrinsics, optimize_color_intrinsics, do_surfel_updates, optimize_poses,
                         optimize_geometry, min_iterations, max_iterations, pcg_max_inner_iterations, pcg_max_keyframes,

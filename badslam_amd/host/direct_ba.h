@@ -149,11 +149,11 @@ class DirectBA {
   // Multi-GPU KEYFRAME sharding (bahip_context_set_keyframe_sharding): this object holds ALL surfels; of the keyframes it needs
   // the images of those with (index among the non-deleted keyframes) % world == rank only (world = 1, 2, 4, or 8 after
   // SetSumClasses(8)).  Covers the
-  // alternating scheme over poses, geometry and the depth / colour intrinsics -- BundleAdjustment(stream, ..., /*do_surfel_updates*/
-  // false, ..., /*increase_ba_iteration_count*/ false), the intrinsics after SetIntrinsicsSumClasses(c) with
-  // c >= world, the PCG scheme (use_pcg, after SetPCGSumClasses(c) with c >= world) -- and ends with the unsharded run's bits (same class
-  // counts) on every rank; the surfel lifecycle (end tasks included) is refused.  Needs SetAllReduce or an RCCL communicator when
-  // world > 1.
+  // whole BundleAdjustment call: the alternating scheme over poses, geometry and the depth / colour intrinsics (the intrinsics after
+  // SetIntrinsicsSumClasses(c) with c >= world), the PCG scheme (use_pcg, after SetPCGSumClasses(c) with c >= world) and the surfel
+  // lifecycle -- creation, merging, deletion and the end tasks (do_surfel_updates, increase_ba_iteration_count) through the batched
+  // backend calls by keyframe index, so SetBatchedCreation(false) is refused -- and ends with the unsharded run's bits (same class
+  // counts) on every rank.  Needs SetAllReduce or an RCCL communicator when world > 1.
   void SetKeyframeSharding(int rank, int world);
   // The per-surfel sums of the normals / geometry passes are defined over 4 (default) or 8 interleaved keyframe classes
   // (bahip_context_set_sum_classes); keyframe sharding over 8 ranks needs 8 -- and so does the single-GPU run it is compared with.

@@ -269,6 +269,19 @@ class Scene:
         planes = np.stack([b.download()[:self.cf_h, :self.cf_w] for b in self.supporting])
         return planes, merged.value
 
+    def merge_surfels_for_bound_keyframes(self, keyframes, merge_dist_factor=0.8):
+        """bahip_merge_surfels_for_bound_keyframes: the merges of a batch of bound keyframes, named by index (the keyframes as last bound);
+        returns (the three supporting planes afterwards -- left empty --, surfels merged away)."""
+        n = len(keyframes)
+        merged = C.c_uint32()
+        s = self.surfels_struct()
+        capi.check(self.lib.bahip_merge_surfels_for_bound_keyframes(self.ctx.handle, float(merge_dist_factor), (C.c_int * max(1, n))(*keyframes), n,
+                                                                    C.byref(s), self._supporting_ptrs(), self.supporting[0].pitch, C.byref(merged)))
+        self.ctx.synchronize()
+        self.surfel_count -= merged.value
+        planes = np.stack([b.download()[:self.cf_h, :self.cf_w] for b in self.supporting])
+        return planes, merged.value
+
     def delete_surfels_and_update_radii(self, min_observation_count):
         deleted = C.c_uint32()
         s = self.surfels_struct()

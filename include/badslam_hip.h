@@ -131,10 +131,23 @@ int bahip_context_set_allreduce(bahip_context* ctx, bahip_allreduce_fn fn, void*
  *     summed over the ranks as BAHIP_SUM_I64 over their bit patterns (C x 2 x (1 or 3) and C x (1 or 3) binary32 values per surfel),
  *     the exact accumulators as under surfel sharding; the normals update before it (bahip_update_surfel_normals) exchanges its
  *     class partials like the geometry step's normals pass (world must not exceed bahip_context_set_sum_classes);
+ *   - the batched surfel lifecycle deals the image reads out by owner and runs the order-dependent rest on every rank, every
+ *     exchange an integer sum (BAHIP_SUM_I64) of zero-filled partials or counts:
+ *       bahip_create_surfels_for_keyframes: every keyframe of the batch takes the creation chain (the last one and a batch of one
+ *         too, so the caller's supporting planes end EMPTY, as a merge batch leaves them); one exchange of the owners' occupancy at
+ *         the batch's begin, candidates and their raw depth / normal words (n x (cells + padded pixels + 4 cells) bytes), one of the
+ *         outlier filter's counts over each rank's co-visible keyframes (n x cells x 8 bytes, when filtering), one of the owners'
+ *         records (36 bytes per candidate), then ONE exchange per keyframe of the chain: the next keyframe's occupancy (cells bytes);
+ *       bahip_merge_surfels_for_bound_keyframes (inside a lifecycle batch that knows its keyframes): the per-(keyframe, cell) counts
+ *         (n x cells x 4 bytes) and the cells' members (12 bytes per associated pair);
+ *       bahip_delete_surfels_and_update_radii: per surfel the observation and violation counts and one minimum-radius word per rank
+ *         ((2 + world) x 4 bytes);
+ *     compaction and the spatial order read no image and run as they are;
  *   - everything ends with the bits of the unsharded run (with the same class counts) on every rank.
- * The PCG stage entry points (bahip_pcg_begin ...), bahip_assign_colors and the surfel lifecycle are refused in this mode (their
- * per-surfel chains run over all keyframes in order; use surfel sharding).  A hook or an RCCL communicator must be installed when
- * world > 1.  Surfel and keyframe sharding exclude each other on one context. */
+ * The PCG stage entry points (bahip_pcg_begin ...), bahip_assign_colors and the one-keyframe lifecycle entry points
+ * (bahip_create_surfels_for_keyframe, bahip_determine_supporting_surfels) and bahip_merge_surfels_for_keyframes (a frame does not
+ * say which rank owns it) are refused in this mode.  A hook or an RCCL communicator must be installed when world > 1.  Surfel and
+ * keyframe sharding exclude each other on one context. */
 int bahip_context_set_keyframe_sharding(bahip_context* ctx, int rank, int world);
 /* The number of interleaved partial sums (keyframe classes) the per-surfel sums of the normals and geometry passes are DEFINED
  * over: 4 (default) or 8.  In exact arithmetic both are the reference's sum (B/kernel_opt_geometry.cu: keyframe after keyframe);
@@ -388,6 +401,14 @@ int bahip_take_merged_count(bahip_context* ctx, uint32_t* merged_count_out);
 int bahip_merge_surfels_for_keyframes(bahip_context* ctx, float merge_dist_factor, const bahip_frame* frames, const float* frame_T_global_3x4,
                                       int num_frames, const bahip_surfels* surfels, uint32_t* const* supporting, uint32_t supporting_pitch_bytes,
                                       uint32_t* merged_count_out);
+/* The same merges for BOUND keyframes named by index (bahip_set_keyframes): their packed entries and poses, in the order given; the
+ * same deletions as bahip_merge_surfels_for_keyframes with those keyframes' frames and frame_T_global (no repacking into a slot of the
+ * context).  Inside a lifecycle batch that knows the keyframes (bahip_lifecycle_batch_set_keyframes) it runs by cell lists.  Under
+ * keyframe sharding it is the merging entry point: the batch must know its keyframes, each rank lists the members of the keyframes it
+ * owns, the counts and members are summed over the ranks, the decisions run on every rank. */
+int bahip_merge_surfels_for_bound_keyframes(bahip_context* ctx, float merge_dist_factor, const int* keyframe_indices, int num_keyframes,
+                                            const bahip_surfels* surfels, uint32_t* const* supporting, uint32_t supporting_pitch_bytes,
+                                            uint32_t* merged_count_out);
 /* A batch of keyframes creating or merging surfels on one cloud (the BA loop's creation pass, its merge pass, the merges of the
  * end tasks): bahip_lifecycle_batch_begin takes the bounding spheres of the cloud's 64-surfel tiles once; until
  * bahip_lifecycle_batch_end the per-keyframe sweeps of bahip_determine_supporting_surfels / bahip_create_surfels_for_keyframe over
