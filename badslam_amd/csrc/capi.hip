@@ -84,15 +84,15 @@ KfEntry raw_entry(const bahip_frame& f) {
 }
 
 // Frame table entry for `f`.  The sweeps read the tiled BA planes; a caller that maintains them (Keyframe does) passes
-// them in f.planes, otherwise they are packed here, on the context stream, into library-owned planes (`slot`).
-int make_entry(bahip_context* ctx, const bahip_frame& f, size_t slot, KfEntry* out) {
+// them in f.planes, otherwise they are packed here, on the context stream, into library-owned planes (`slot` of `pool`).
+static int make_entry_in(bahip_context* ctx, std::vector<bahip_frame_planes*>& pool, const bahip_frame& f, size_t slot, KfEntry* out) {
   KfEntry e = raw_entry(f);
   const bahip_frame_planes* p = f.planes;
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics must precede any call that takes frames");
   const int w = ctx->in.width, h = ctx->in.height, cw = ctx->in.cwidth, ch = ctx->in.cheight;
   if (!p) {
-    if (ctx->auto_planes.size() <= slot) ctx->auto_planes.resize(slot + 1, nullptr);
-    bahip_frame_planes*& mine = ctx->auto_planes[slot];
+    if (pool.size() <= slot) pool.resize(slot + 1, nullptr);
+    bahip_frame_planes*& mine = pool[slot];
     if (mine && (mine->width != w || mine->height != h || mine->cwidth != cw || mine->cheight != ch)) { planes_free(mine); mine = nullptr; }
     if (!mine && planes_alloc(w, h, cw, ch, &mine)) return 1;
     launch_pack_planes(ctx->stream, e, w, h, cw, ch, mine->geom, mine->lumafp);
@@ -103,6 +103,12 @@ int make_entry(bahip_context* ctx, const bahip_frame& f, size_t slot, KfEntry* o
   e.geom = p->geom; e.lumafp = p->lumafp;
   *out = e;
   return 0;
+}
+int make_entry(bahip_context* ctx, const bahip_frame& f, size_t slot, KfEntry* out) {
+  return make_entry_in(ctx, ctx->auto_planes, f, slot, out);
+}
+int make_batch_entry(bahip_context* ctx, const bahip_frame& f, size_t j, KfEntry* out) {
+  return make_entry_in(ctx, ctx->batch_planes, f, j, out);
 }
 
 SurfelsView make_view(const bahip_surfels* s) {
@@ -287,6 +293,7 @@ void bahip_context_destroy(bahip_context* ctx) {
   if (ctx->host_loop_ctl) hipHostFree(ctx->host_loop_ctl);
   rccl_destroy_communicator(ctx);
   for (bahip_frame_planes* p : ctx->auto_planes) planes_free(p);
+  for (bahip_frame_planes* p : ctx->batch_planes) planes_free(p);
   for (auto& t : ctx->timers) for (auto e : t.ev) hipEventDestroy(e);
   delete ctx;
 }

@@ -210,6 +210,9 @@ struct bahip_context {
   // planes packed by the library itself for frames handed over without bahip_frame.planes:
   // slot 0 = the single frame of the per-frame entry points, slot 1 + k = bound keyframe k
   std::vector<bahip_frame_planes*> auto_planes;
+  // and for frame j of a merge batch by cell lists (at most 64 frames): a pool of its own, so that a batch in any order never
+  // writes into the planes a bound keyframe's table entry points at
+  std::vector<bahip_frame_planes*> batch_planes;
 
   bahip_allreduce_fn allreduce = nullptr;
   void* allreduce_user = nullptr;
@@ -229,6 +232,7 @@ int planes_alloc(int width, int height, int cwidth, int cheight, bahip_frame_pla
 void planes_free(bahip_frame_planes* p);
 KfEntry raw_entry(const bahip_frame& f);
 int make_entry(bahip_context* ctx, const bahip_frame& f, size_t slot, KfEntry* out);
+int make_batch_entry(bahip_context* ctx, const bahip_frame& f, size_t j, KfEntry* out);
 SurfelsView make_view(const bahip_surfels* s);
 template <typename T>
 int grow_device(T** ptr, size_t* capacity, size_t need, size_t slack, const char* what) {

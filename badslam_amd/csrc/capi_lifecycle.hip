@@ -292,9 +292,10 @@ int bahip_merge_surfels_for_keyframes(bahip_context* ctx, float merge_dist_facto
       size_t f = 0;
       while (f < listed && memcmp(&ctx->lifecycle_frames[12 * f], F, 12 * sizeof(float)) != 0) ++f;
       // (the association sweep reads the BA planes of all frames at once: a frame handed over without them gets a packing slot of its
-      // own -- for a small batch; a long one without planes takes the pipelined path, which re-packs ONE slot frame after frame)
+      // own -- for a small batch, in the context's batch pool, never in a bound keyframe's slot; a long one without planes takes the
+      // pipelined path, which re-packs ONE slot frame after frame)
       if (f == listed || (frames[j].planes == nullptr && num_frames > 64)) { known = false; break; }
-      if (make_entry(ctx, frames[j], frames[j].planes ? 0 : (size_t)j + 1, &table[j].entry)) return 1;
+      if (make_batch_entry(ctx, frames[j], (size_t)j, &table[j].entry)) return 1;
       memcpy(table[j].entry.pose.F, F, 12 * sizeof(float));
       table[j].list_offset = ctx->lifecycle_list_offsets[f];
       table[j].list_count = ctx->lifecycle_list_counts[f];

@@ -598,9 +598,11 @@ int bahip_debug_set_append_groups(int groups);
  * surfels either way.  ..._batches: how many calls have taken the chain so far (tests assert the route). */
 int bahip_debug_set_creation_chain(int enabled);
 int bahip_debug_creation_chain_batches(long long* batches_out);
-/* A merge batch by cell lists (bahip_merge_surfels_for_keyframes inside a lifecycle batch that knows the frames, every frame with its
- * BA planes): 1 (default; BAHIP_MERGE_CELLS=0 switches it off) or 0 = the pipelined insert / decide / apply sweeps of round 6's first
- * version; the same deletions either way.  ..._batches: how many calls have gone by cell lists. */
+/* A merge batch by cell lists (bahip_merge_surfels_for_keyframes inside a lifecycle batch that knows the frames; frames without BA
+ * planes are allowed up to 64 per batch, each packed into a slot of its own that no bound keyframe uses, so the bound keyframes' planes
+ * are never touched; a longer batch with such frames takes the pipelined form): 1 (default; BAHIP_MERGE_CELLS=0 switches it off) or
+ * 0 = the pipelined insert / decide / apply sweeps of round 6's first version; the same deletions either way.  ..._batches: how many
+ * calls have gone by cell lists. */
 int bahip_debug_set_merge_cells(int enabled);
 int bahip_debug_merge_cells_batches(long long* batches_out);
 /* The LDS form holds the normal equations of at most 292 work items; longer lists are cut into slices, one launch each.  items > 0

@@ -339,6 +339,14 @@ def test_lifecycle_batches_on_other_scenes(seed, width, height, cell, keyframes)
         orc.compact_surfels()
         assert g.surfels_size == orc.surfels_size
         assert np.array_equal(_rows(g.download_surfels()), _rows(orc.surfel_data[:, :orc.surfels_size])), round_
+        # the merge batch (frames without planes) must leave the bound keyframes' planes as they were: a sweep that reads them,
+        # before the next round rebinds
+        orc.use_depth, orc.use_desc = 1, 1
+        g.update_surfel_activation()
+        orc.update_surfel_activation()
+        g.optimize_geometry_iteration(True, True)
+        orc.optimize_geometry_iteration()
+        assert np.array_equal(_rows(g.download_surfels()), _rows(orc.surfel_data[:, :orc.surfels_size])), round_
     after = C.c_longlong()
     capi.check(lib.bahip_debug_merge_cells_batches(C.byref(after)))
     assert _chain_batches() - chains == 3 and after.value - cells.value == 3
