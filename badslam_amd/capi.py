@@ -74,6 +74,11 @@ class PCGOptions(C.Structure):
 SUM_F32, SUM_I64, SUM_F64 = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128
 # int fn(void* device_buffer, size_t count, int dtype, void* hip_stream, void* user)
+class Cost(C.Structure):           # bahip_cost: the value of the BA objective (bahip_evaluate_cost)
+    _fields_ = [("depth", C.c_double), ("descriptor_1", C.c_double), ("descriptor_2", C.c_double),
+                ("depth_residuals", C.c_uint64), ("descriptor_pairs", C.c_uint64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol declared in include/badslam_hip.h
@@ -181,6 +186,10 @@ SIGNATURES = {
     "bahip_pcg_step3": (C.c_int, [C.c_void_p, C.POINTER(PCGLayout), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bahip_update_surfels_from_pcg_delta": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.c_int, C.c_uint32, C.c_void_p]),
     "bahip_update_cfactors_from_pcg_delta": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bahip_evaluate_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Surfels), C.POINTER(Cost), C.POINTER(Cost)]),
+    "bahip_evaluate_frame_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
+                                            C.POINTER(Cost)]),
+    "bahip_debug_set_cost_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

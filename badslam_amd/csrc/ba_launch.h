@@ -391,4 +391,30 @@ namespace exact { BAHIP_FLAVOURED_DECLARATIONS }
 namespace fast { BAHIP_FLAVOURED_DECLARATIONS }
 #define BAHIP_PICK(in, call) do { if ((in).fast_math) fast::call; else exact::call; } while (0)
 
+// kernels_cost.hip: the value of the BA objective per keyframe.  Output row of a keyframe (kCostWords int64, summed over workgroups and
+// ranks as integers): the ExactCells of the depth, descriptor-1 and descriptor-2 sums, the depth residual count, the descriptor pair
+// count and a non-finite flag.  Launch shape: `waves` wavefronts per workgroup, at most `workgroups` of them, keyframes in slices of
+// at most `slice` (the LDS table of a workgroup: slice x kCostWords x 8 bytes).
+constexpr int kCostCellWords = 9;   // = kExactLimbs (exact_sum.h; kernels_cost.hip checks)
+constexpr int kCostWords = 3 * kCostCellWords + 3;
+constexpr int kCostDepthCountWord = 3 * kCostCellWords, kCostPairCountWord = kCostDepthCountWord + 1, kCostFlagWord = kCostDepthCountWord + 2;
+constexpr int kCostMaxWaves = 8;
+constexpr int kCostMaxSlice = 256;   // 60 KB of LDS: two workgroups of 8 wavefronts per compute unit
+struct CostShape {
+  int waves, workgroups, slice;
+};
+namespace exact {
+void launch_cost(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, int num_kfs, int kf_rank,
+                 int kf_world, const SurfelsView& s, const uint32_t* sched, const CostShape& shape, long long* out);
+}
+namespace fast {
+void launch_cost(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, int num_kfs, int kf_rank,
+                 int kf_world, const SurfelsView& s, const uint32_t* sched, const CostShape& shape, long long* out);
+}
+void launch_cost(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, int num_kfs, int kf_rank,
+                 int kf_world, const SurfelsView& s, const uint32_t* sched, const CostShape& shape, long long* out);
+// rows [num][kCostWords] (summed over the ranks) -> out[0 .. num): per row, out[num]: the total from the summed limbs; `total`: kCostWords
+// zeroed words of scratch
+void launch_cost_resolve(hipStream_t stream, const long long* rows, int num, long long* total, bahip_cost* out);
+
 }  // namespace bahip

@@ -272,7 +272,7 @@ void bahip_context_destroy(bahip_context* ctx) {
   }
 #endif
   if (ctx->pinned_work) hipHostFree(ctx->pinned_work);
-  hipFree(ctx->dev_kfs); hipFree(ctx->dev_work); hipFree(ctx->dev_Hb);
+  hipFree(ctx->dev_kfs); hipFree(ctx->dev_work); hipFree(ctx->dev_Hb); hipFree(ctx->dev_cost);
   hipFree(ctx->dev_frame1); hipFree(ctx->dev_work1); hipFree(ctx->dev_Hb1); hipFree(ctx->dev_tile_counters);
   hipFree(ctx->dev_counter);
   if (ctx->pinned_i) hipHostFree(ctx->pinned_i);

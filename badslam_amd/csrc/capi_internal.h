@@ -6,6 +6,7 @@
 //   capi_lifecycle.hip  supporting surfels, merging, creation (single and batched), deletion, compaction, spatial order
 //   capi_solvers.hip    the intrinsics step and the PCG scheme (whole iteration and stage by stage)
 //   capi_debug.hip      test hooks and experiment switches
+//   capi_cost.hip       the value of the BA objective (bahip_evaluate_cost, bahip_evaluate_frame_cost)
 #pragma once
 
 #include <dlfcn.h>
@@ -204,6 +205,8 @@ struct bahip_context {
   int intr_sums_cells = -1;        // sparse cells of the accumulators the last intrinsics step left in intr_scratch (-1: none; bahip_debug_read_intrinsics_sums)
   float* kf_partials = nullptr;    // class partials of the geometry step (normals, then position) / hit words of the activation
   size_t kf_partials_capacity = 0; // floats
+  long long* dev_cost = nullptr;   // rows of the cost sweep (kernels_cost.hip): kCostWords int64 per keyframe
+  size_t cost_capacity = 0;        // int64 words
   long long exchange_calls = 0;    // sums over the ranks requested since the last reset (bahip_exchange_stats), and their bytes
   long long exchange_bytes = 0;
 

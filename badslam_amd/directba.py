@@ -40,6 +40,7 @@ def _load():
         L.dba_create_surfels_for_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.dba_estimate_frame_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.dba_bundle_adjustment.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+        L.dba_compute_cost.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(capi.Cost), C.POINTER(capi.Cost)]
         L.dba_surfel_count.restype = C.c_uint32
         L.dba_surfel_count.argtypes = [C.c_void_p]
         L.dba_surfels_size.restype = C.c_uint32
@@ -210,6 +211,16 @@ class DirectBA:
         out = _F7()
         assert self.L.dba_estimate_frame_pose(self.h, self.stream, int(k), _F7(*[float(v) for v in init_pose]), out) == 0
         return np.array(list(out), np.float64)
+
+    def compute_cost(self, per_keyframe=True):
+        """DirectBA::ComputeCost: the value of the BA objective with this object's residual switches (exact sums; the same bits under
+        either sharding).  Returns (total, list indexed by keyframe id or None), dicts as lowlevel.cost_dict."""
+        from badslam_amd.lowlevel import cost_dict
+        total = capi.Cost()
+        n = self.keyframe_count()
+        per = (capi.Cost * max(1, n))() if per_keyframe else None
+        assert self.L.dba_compute_cost(self.h, self.stream, C.byref(total), per) == 0
+        return cost_dict(total), ([cost_dict(c) for c in per[:n]] if per_keyframe else None)
 
     def BundleAdjustment(self, optimize_depth_intrinsics=False, optimize_color_intrinsics=False, do_surfel_updates=False,
                          optimize_poses=True, optimize_geometry=True, min_iterations=1, max_iterations=1, use_pcg=False,

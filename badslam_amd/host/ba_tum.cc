@@ -11,8 +11,10 @@
 //   ba_tum <dataset_dir> <trajectory_file> <out_prefix> [--interval N] [--iterations N] [--cell N] [--max_depth M]
 //          [--raw_to_float_depth S] [--pcg] [--intrinsics] [--incremental | --parallel_ba] [--save_state F] [--load_state F]
 //          [--ba_call_iterations N] [--baseline_fx F] [--spatial_sort_cell C] [--row_major_creation]
-//          [--bilateral_sigma_xy S] [--bilateral_sigma_inv_depth S] [--bilateral_radius_factor R]
+//          [--bilateral_sigma_xy S] [--bilateral_sigma_inv_depth S] [--bilateral_radius_factor R] [--report_cost]
 //
+// --report_cost: prints the value of the BA objective (DirectBA::ComputeCost: total and the depth / descriptor sums and counts) before
+// the first and after the last BA call.
 // --ba_call_iterations N: every BA call runs exactly N iterations (min = max = N) instead of 1 .. 10; the remaining options set
 // what B/bad_slam_config.h makes configurable (and the two order switches of this backend): together they let a TUM-format copy of
 // a test scene go through exactly the chain of tests/e2e_vga.py (tests/test_gpu_tum_pipeline.py holds the result against the
@@ -91,7 +93,7 @@ int main(int argc, char** argv) {
   float raw_to_float_depth = 1.0f / 5000;   // TUM RGB-D depth PNGs: 5000 units per metre
   float baseline_fx = 40.f, spatial_sort_cell = -1.f;
   int ba_call_iterations = 0;
-  bool row_major_creation = false;
+  bool row_major_creation = false, report_cost = false;
   bool use_pcg = false, intrinsics = false, incremental = false, parallel_ba = false;
   std::string save_state, load_state;
   PreprocessConfig config;
@@ -106,6 +108,7 @@ int main(int argc, char** argv) {
     else if (a == "--baseline_fx" && i + 1 < argc) baseline_fx = (float)atof(argv[++i]);
     else if (a == "--spatial_sort_cell" && i + 1 < argc) spatial_sort_cell = (float)atof(argv[++i]);
     else if (a == "--row_major_creation") row_major_creation = true;
+    else if (a == "--report_cost") report_cost = true;
     else if (a == "--bilateral_sigma_xy" && i + 1 < argc) config.bilateral_filter_sigma_xy = (float)atof(argv[++i]);
     else if (a == "--bilateral_sigma_inv_depth" && i + 1 < argc) config.bilateral_filter_sigma_inv_depth = (float)atof(argv[++i]);
     else if (a == "--bilateral_radius_factor" && i + 1 < argc) config.bilateral_filter_radius_factor = (float)atof(argv[++i]);
@@ -135,6 +138,14 @@ int main(int argc, char** argv) {
     if (spatial_sort_cell >= 0.f) ba.SetSpatialSortCellSize(spatial_sort_cell);
     if (row_major_creation) ba.SetRowMajorCreation(true);
     vector<SE3f> original_keyframe_T_global;
+    auto print_cost = [&](const char* when) {
+      if (!report_cost) return;
+      DirectBA::BACost c;
+      ba.ComputeCost(stream, &c);
+      printf("cost %s: %.9g (depth %.9g over %llu residuals, descriptor %.9g + %.9g over %llu pairs)\n", when,
+             c.depth + c.descriptor_1 + c.descriptor_2, c.depth, (unsigned long long)c.depth_residuals, c.descriptor_1, c.descriptor_2,
+             (unsigned long long)c.descriptor_pairs);
+    };
     if (incremental) {
       BASchedulerConfig scheduler_config;
       scheduler_config.parallel_ba = parallel_ba;
@@ -156,6 +167,7 @@ int main(int argc, char** argv) {
       }
       scheduler.WaitForQueuedWork();
       scheduler.StopBAThreadAndWaitForIt();
+      print_cost("after the last BA call");
       printf("%zu keyframes through the scheduler (%s), %d parallel iteration(s), %u surfels\n", ba.keyframes().size(),
              parallel_ba ? "BA thread" : "sequential", scheduler.parallel_iterations_done(), ba.surfel_count());
     } else {
@@ -168,6 +180,7 @@ int main(int argc, char** argv) {
       }
       printf("%zu keyframes\n", ba.keyframes().size());
       RememberKeyframePoses(&ba, &original_keyframe_T_global);   // B/bad_slam.cc:1230 (before the BA that moves them)
+      print_cost("before the first BA call");
       for (int i = 0; i < iterations; ++i) {
         int done = 0;
         bool converged = false;
@@ -177,6 +190,7 @@ int main(int argc, char** argv) {
                             (int)ba.keyframes().size() - 1, /*increase_ba_iteration_count*/ true, &done, &converged);
         printf("BA call %d: %d iteration(s)%s, %u surfels\n", i + 1, done, converged ? ", converged" : "", ba.surfel_count());
       }
+      print_cost("after the last BA call");
     }
     // keyframe poses back into the video (the reference shares the pose object between keyframe and video frame), then the
     // frames in between follow their keyframes (B/bad_slam.cc:1259-1269; the scheduler has done that after every BA)

@@ -136,6 +136,21 @@ int dba_bundle_adjustment(dba_handle* h, void* stream, int optimize_depth_intrin
   return 0;
 }
 
+int dba_compute_cost(dba_handle* h, void* stream, bahip_cost* total, bahip_cost* per_keyframe) {
+  DirectBA::BACost sum;
+  std::vector<DirectBA::BACost> per;
+  h->ba->ComputeCost(static_cast<hipStream_t>(stream), &sum, per_keyframe ? &per : nullptr);
+  auto convert = [](const DirectBA::BACost& c) {
+    bahip_cost out;
+    out.depth = c.depth; out.descriptor_1 = c.descriptor_1; out.descriptor_2 = c.descriptor_2;
+    out.depth_residuals = c.depth_residuals; out.descriptor_pairs = c.descriptor_pairs;
+    return out;
+  };
+  if (total) *total = convert(sum);
+  for (size_t id = 0; per_keyframe && id < per.size(); ++id) per_keyframe[id] = convert(per[id]);
+  return 0;
+}
+
 uint32_t dba_surfel_count(dba_handle* h) { return h->ba->surfel_count(); }
 uint32_t dba_surfels_size(dba_handle* h) { return h->ba->surfels_size(); }
 int dba_set_surfel_count(dba_handle* h, uint32_t surfel_count, uint32_t surfels_size) {

@@ -414,6 +414,26 @@ void DirectBA::EstimateFramePose(hipStream_t stream, const SE3f& global_T_frame_
 }
 
 // ---- dispatcher (B/direct_ba.cc:407-454) ---------------------------------------------------------------------------------
+void DirectBA::ComputeCost(hipStream_t stream, BACost* total, vector<BACost>* per_keyframe) {
+  BindScene(stream);
+  const bahip_surfels s = SurfelsStruct(/*with_active*/ false);
+  bahip_cost sum{};
+  vector<bahip_cost> bound(bound_ids_.size());
+  BAHIP_CHECKED_CALL(bahip_evaluate_cost(ctx_, use_depth_residuals_ ? 1 : 0, use_descriptor_residuals_ ? 1 : 0, &s, &sum,
+                                         per_keyframe ? bound.data() : nullptr));
+  auto convert = [](const bahip_cost& c) {
+    BACost out;
+    out.depth = c.depth; out.descriptor_1 = c.descriptor_1; out.descriptor_2 = c.descriptor_2;
+    out.depth_residuals = c.depth_residuals; out.descriptor_pairs = c.descriptor_pairs;
+    return out;
+  };
+  if (total) *total = convert(sum);
+  if (per_keyframe) {
+    per_keyframe->assign(keyframes_.size(), BACost());
+    for (size_t j = 0; j < bound_ids_.size(); ++j) (*per_keyframe)[bound_ids_[j]] = convert(bound[j]);
+  }
+}
+
 void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsics, bool optimize_color_intrinsics,
                                 bool do_surfel_updates, bool optimize_poses, bool optimize_geometry, int min_iterations,
                                 int max_iterations, bool use_pcg, int active_keyframe_window_start,

@@ -47,6 +47,13 @@ class DirectBA {
                         int* iterations_done = nullptr, bool* converged = nullptr, double time_limit = 0, Timer* timer = nullptr,
                         int pcg_max_inner_iterations = 30, int pcg_max_keyframes = 2500,
                         std::function<bool(int)> progress_function = nullptr);
+  // The value of the objective BundleAdjustment minimises (bahip_evaluate_cost: exact sums, the same bits under either sharding), with
+  // this object's residual switches, over every keyframe and surfel.  per_keyframe: indexed by keyframe id, deleted ids left at zero.
+  struct BACost {
+    double depth = 0, descriptor_1 = 0, descriptor_2 = 0;
+    uint64_t depth_residuals = 0, descriptor_pairs = 0;
+  };
+  void ComputeCost(hipStream_t stream, BACost* total, vector<BACost>* per_keyframe = nullptr);
   void UpdateKeyframeCoVisibility(const shared_ptr<Keyframe>& keyframe);
   // B/direct_ba.h:167, B/direct_ba.cc:456-459: surfel colours := mean of their observations in all keyframes (before an export).
   void AssignColors(hipStream_t stream);

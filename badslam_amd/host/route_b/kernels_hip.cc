@@ -131,8 +131,8 @@ void AccumulatePoseEstimationCoeffsCUDA(cudaStream_t stream, bool use_depth_resi
                                         const DepthParameters& depth_params, const CUDABuffer<u16>& depth_buffer,
                                         const CUDABuffer<u16>& normals_buffer, cudaTextureObject_t color_texture,
                                         const CUDAMatrix3x4& frame_T_global_estimate, u32 surfels_size,
-                                        const CUDABuffer<float>& surfels, bool /*debug*/, u32* /*residual_count*/,
-                                        float* /*residual_sum*/, float* H, float* b, PoseEstimationHelperBuffers*) {
+                                        const CUDABuffer<float>& surfels, bool debug, u32* residual_count,
+                                        float* residual_sum, float* H, float* b, PoseEstimationHelperBuffers*) {
   CHECK(use_depth_residuals || use_descriptor_residuals);   // B/kernel_opt_pose.cc:58
   bahip_context* ctx = Ctx(stream);
   BindIntrinsics(ctx, color_camera, depth_camera, depth_params);
@@ -140,6 +140,16 @@ void AccumulatePoseEstimationCoeffsCUDA(cudaStream_t stream, bool use_depth_resi
   const bahip_surfels s = Surfels(surfels, nullptr, surfels_size);
   BAHIP_CHECKED_CALL(bahip_accumulate_pose_estimation_coeffs(ctx, use_depth_residuals, use_descriptor_residuals, &frame,
                                                              &frame_T_global_estimate.row0.x, &s, H, b));
+  if (debug) {
+    // The reference's debug outputs (B/kernel_opt_pose.cu:373-380): one count per associated pair and residual type, and the sum of
+    // the depth term and the FIRST descriptor term only (the second descriptor term is not in it).  From the
+    // cost sweep, which sums the same terms exactly (bahip_evaluate_frame_cost).
+    bahip_cost c;
+    BAHIP_CHECKED_CALL(bahip_evaluate_frame_cost(ctx, use_depth_residuals, use_descriptor_residuals, &frame, &frame_T_global_estimate.row0.x,
+                                                 &s, &c));
+    *residual_count = (u32)(c.depth_residuals + c.descriptor_pairs);
+    *residual_sum = (float)(c.depth + c.descriptor_1);
+  }
 }
 
 void UpdateSurfelNormalsCUDA(cudaStream_t stream, const PinholeCamera4f& depth_camera, const DepthParameters& depth_params,

@@ -11,6 +11,12 @@ import numpy as np
 from . import capi
 
 
+def cost_dict(c):
+    """A bahip_cost as a dict (depth, descriptor_1, descriptor_2: float; depth_residuals, descriptor_pairs: int)."""
+    return dict(depth=c.depth, descriptor_1=c.descriptor_1, descriptor_2=c.descriptor_2, depth_residuals=int(c.depth_residuals),
+                descriptor_pairs=int(c.descriptor_pairs))
+
+
 class DeviceBuffer2D:
     """libvis CUDABuffer<T> semantics: (height, width) pitched device allocation."""
 
@@ -411,6 +417,23 @@ class Scene:
         capi.check(self.lib.bahip_debug_read_pcg_vector(self.ctx.handle, int(which), int(offset), int(count),
                                                         out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def evaluate_cost(self, use_depth=True, use_desc=True, per_keyframe=True):
+        """The value of the BA objective over the bound keyframes (bahip_evaluate_cost): (total, per-keyframe list or None), each a
+        dict of the three exactly summed costs (binary64) and the two counts.  Call bind_keyframes first."""
+        s = self.surfels_struct()
+        total = capi.Cost()
+        per = (capi.Cost * max(1, len(self.keyframes)))() if per_keyframe else None
+        capi.check(self.lib.bahip_evaluate_cost(self.ctx.handle, int(use_depth), int(use_desc), C.byref(s), C.byref(total), per))
+        return cost_dict(total), ([cost_dict(c) for c in per[:len(self.keyframes)]] if per_keyframe else None)
+
+    def evaluate_frame_cost(self, i, frame_T_global, use_depth=True, use_desc=True):
+        """The same for keyframe i's images at an arbitrary frame_T_global (12 floats; bahip_evaluate_frame_cost)."""
+        F = (C.c_float * 12)(*[float(v) for v in frame_T_global])
+        fr, s = self.frame_struct(i), self.surfels_struct()
+        out = capi.Cost()
+        capi.check(self.lib.bahip_evaluate_frame_cost(self.ctx.handle, int(use_depth), int(use_desc), C.byref(fr), F, C.byref(s), C.byref(out)))
+        return cost_dict(out)
 
     def exact_sum(self, values, mode=0):
         """Exactly rounded binary64 sum of binary32 values through the device's exact accumulators (test hook)."""

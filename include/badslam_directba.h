@@ -58,6 +58,10 @@ int dba_bundle_adjustment(dba_handle* h, void* hip_stream, int optimize_depth_in
                           int increase_ba_iteration_count, int* iterations_done, int* converged,
                           int pcg_max_inner_iterations);
 
+/* DirectBA::ComputeCost (ours): the value of the BA objective with the object's residual switches (bahip_evaluate_cost; the same bits
+ * under surfel or keyframe sharding).  per_keyframe: NULL or dba_keyframe_count entries indexed by keyframe id, deleted ids zero. */
+int dba_compute_cost(dba_handle* h, void* hip_stream, bahip_cost* total, bahip_cost* per_keyframe);
+
 /* accessors */
 uint32_t dba_surfel_count(dba_handle* h);
 uint32_t dba_surfels_size(dba_handle* h);

@@ -530,6 +530,28 @@ int bahip_update_surfels_from_pcg_delta(bahip_context* ctx, const bahip_surfels*
                                         uint32_t surfel_unknown_start_index, const float* pcg_delta);
 int bahip_update_cfactors_from_pcg_delta(bahip_context* ctx, uint32_t cfactor_unknown_start_index, const float* pcg_delta);
 
+/* ---- the value of the BA objective (kernels_cost.hip) ---------------------------------------------------------
+ * Over every associated (surfel, keyframe) pair, activation flags ignored: with use_depth the depth term 1 * TukeyCost(raw, 10) (one
+ * residual), with use_desc -- for the pairs whose depth-to-colour transform is valid -- the two descriptor terms 1e-2 * HuberCost(raw, 10)
+ * (one pair).  Each sum is the exact sum of its binary32 terms rounded once to binary64: it does not depend on the launch shape, the
+ * tile order, the surfel order or the sharding.  A non-finite term makes its keyframe's sum (and the total) NaN.
+ * bahip_evaluate_cost: every bound keyframe (bahip_set_keyframes) x surfels [0, surfels_size); per_keyframe: NULL or num_keyframes
+ * entries in bound order; the total is resolved from the summed limbs, not from the per-keyframe doubles.  Surfel sharding: the
+ * rows of all ranks are summed as int64 (one exchange of K x 30 words; a rank with an empty shard takes part too); keyframe sharding: each rank sweeps its own keyframes and
+ * the rows are summed the same way.  Every rank returns the same bits.  bahip_evaluate_frame_cost: one arbitrary frame at
+ * frame_T_global (as bahip_accumulate_pose_estimation_coeffs takes it; an exchange under surfel sharding only).  Synchronise. */
+typedef struct bahip_cost {
+  double depth, descriptor_1, descriptor_2;
+  uint64_t depth_residuals, descriptor_pairs;
+} bahip_cost;
+int bahip_evaluate_cost(bahip_context* ctx, int use_depth, int use_desc, const bahip_surfels* surfels, bahip_cost* total,
+                        bahip_cost* per_keyframe);
+int bahip_evaluate_frame_cost(bahip_context* ctx, int use_depth, int use_desc, const bahip_frame* frame, const float frame_T_global[12],
+                              const bahip_surfels* surfels, bahip_cost* out);
+/* Launch shape of the cost sweep (test hook; results never depend on it): wavefronts per workgroup 1 .. 8, workgroups >= 1, keyframes
+ * per launch 1 .. 256, tile_order 0 = buffer order, 1 = the sweeps' heavy-first order when there is one; 0 / -1 = the default. */
+int bahip_debug_set_cost_shape(int waves, int workgroups, int slice, int tile_order);
+
 /* ---- test hook --------------------------------------------------------------------------------------
  * Per-pair evaluation with the production device functions (association, the three raw residuals,
  * weights, pose Jacobians, image gradients) for `count` surfel indices against one frame; 40 floats
