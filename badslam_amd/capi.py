@@ -174,6 +174,9 @@ SIGNATURES = {
                                             C.POINTER(Camera), C.POINTER(C.c_float)]),
     "bahip_pcg_iteration": (C.c_int, [C.c_void_p, C.POINTER(PCGOptions), C.POINTER(Surfels), C.POINTER(Camera),
                                       C.POINTER(Camera), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bahip_pcg_iteration_windowed": (C.c_int, [C.c_void_p, C.POINTER(PCGOptions), C.POINTER(Surfels), C.POINTER(Camera),
+                                               C.POINTER(Camera), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bahip_pcg_window_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "bahip_pcg_begin": (C.c_int, [C.c_void_p, C.POINTER(PCGLayout), C.c_uint32]),
     "bahip_pcg_init": (C.c_int, [C.c_void_p, C.POINTER(PCGLayout), C.POINTER(Frame), C.POINTER(C.c_float), C.c_uint32, C.c_int,
                                  C.POINTER(Surfels), C.c_void_p, C.c_void_p]),

@@ -359,6 +359,15 @@ struct PcgClasses {
   int classes;
   int entries;
 };
+// The window of the windowed PCG sweeps (kernels_pcg_window.hip): the swept keyframes (bound indices, ascending) with the index of
+// their first pose unknown (0xffffffff: pose fixed), and the 64-surfel tiles that hold an active surfel.
+struct PcgWindow {
+  const int32_t* kf;
+  const uint32_t* pose_index;
+  int num_kfs;
+  const uint32_t* tiles;
+  uint32_t num_tiles;
+};
 
 // A pointer read from a device table (KfEntry::geom, ...) is a generic pointer to the compiler, which then emits flat_load
 // (checked against the LDS / scratch apertures, counted on vmcnt AND lgkmcnt).  Every such pointer here is a hipMalloc

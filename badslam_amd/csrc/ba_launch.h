@@ -230,6 +230,14 @@ void launch_pcg_step3(hipStream_t st, const PcgLayout& L, const PcgExact& ex, co
 void launch_exact_sum_debug(hipStream_t st, const PcgExact& ex, const float* values, size_t n, int mode, double* out);
 void launch_pcg_update_surfels(hipStream_t st, const PcgLayout& L, const SurfelsView& s, const float* delta);
 void launch_pcg_update_cfactors(hipStream_t st, const Intrinsics& in, uint32_t start, const float* delta, float* cfactor, uint32_t pitch);
+// kernels_pcg_window.hip: the sweeps over a keyframe window (PcgWindow), the tile list they run over (`count` zeroed by the caller) and
+// the surfel update that leaves inactive surfels alone
+void launch_pcg_window_tiles(hipStream_t st, const SurfelsView& s, uint32_t* tiles, uint32_t* count);
+void launch_pcg_window_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, const PcgWindow& w,
+                            const SurfelsView& s, float* r, float* M);
+void launch_pcg_window_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs, const PcgWindow& w,
+                             const SurfelsView& s, const float* p, float* g, const void* ctl);
+void launch_pcg_window_update_surfels(hipStream_t st, const PcgLayout& L, const SurfelsView& s, const float* delta);
 
 // kernels_lifecycle.hip
 void launch_supporting_fill(hipStream_t st, const SupportingView& sup, int w, int h);
@@ -386,7 +394,12 @@ hipError_t launch_compact(hipStream_t st, const SurfelsView& s, uint32_t* invali
                         const SurfelsView& s, const float* p, float* g, const void* ctl, const uint32_t* sched, uint32_t* tile_counters,      \
                         int* parity_inout, const PcgClasses* classes);                                                                        \
   void set_pcg_lds_form(int mode);                                                                                                            \
-  void pcg_step1_form_launches(long long out[2]);
+  void pcg_step1_form_launches(long long out[2]);                                                                                             \
+  /* kernels_pcg_window.hip */                                                                                                                \
+  void launch_pcg_window_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs,              \
+                              const PcgWindow& w, const SurfelsView& s, float* r, float* M);                                                  \
+  void launch_pcg_window_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs,             \
+                               const PcgWindow& w, const SurfelsView& s, const float* p, float* g, const void* ctl);
 namespace exact { BAHIP_FLAVOURED_DECLARATIONS }
 namespace fast { BAHIP_FLAVOURED_DECLARATIONS }
 #define BAHIP_PICK(in, call) do { if ((in).fast_math) fast::call; else exact::call; } while (0)

@@ -192,6 +192,10 @@ struct bahip_context {
   float* pcg_buf = nullptr;        // PCG vectors r, M, delta, g, p (5 * pcg_capacity floats) + 16 scalars
   size_t pcg_capacity = 0;
   void* pcg_exact = nullptr;       // exact accumulators of the PCG solve (ExactCell[pcg_exact_capacity]; kernels_pcg.hip)
+  uint32_t* pcg_window = nullptr;  // windowed PCG (kernels_pcg_window.hip): [tile count | keyframe list | pose indices | tile list]
+  size_t pcg_window_capacity = 0;  // words
+  uint32_t pcg_window_last_tiles = 0;   // tiles and swept keyframes of the last windowed call (bahip_pcg_window_size)
+  int pcg_window_last_kfs = 0;
   size_t pcg_exact_capacity = 0;
   void* pcg_stage_ctl = nullptr;   // stage API (bahip_pcg_begin ...): a control block that never stops, the head size the
   uint32_t pcg_stage_head = 0;     // accumulators were set up for, and the bahip_pcg_step1 calls since the last step 2

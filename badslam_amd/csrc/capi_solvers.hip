@@ -460,6 +460,233 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
   return 0;
 }
 
+// One outer iteration of the PCG scheme over the active keyframe window (kernels_pcg_window.hip: "DEFINITION of the windowed
+// system").  The inner loop, the exchanges under surfel sharding and the intrinsics update are those of bahip_pcg_iteration.
+int bahip_pcg_iteration_windowed(bahip_context* ctx, const bahip_pcg_options* opt, const bahip_surfels* surfels,
+                                 bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a, int* inner_steps_out,
+                                 int* num_converged_out) {
+  REQUIRE(!kf_sharded(ctx), "bahip_pcg_iteration_windowed is not available under keyframe sharding: use surfel sharding, or "
+                            "bahip_pcg_iteration for the whole map");
+  REQUIRE(ctx->pcg_sum_classes == 1, "bahip_pcg_iteration_windowed needs one keyframe class of the PCG surfel block "
+                                     "(bahip_context_set_pcg_sum_classes(ctx, 1)): its surfel block is the one chain over the swept keyframes");
+  REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
+  const bool sharded = is_sharded(ctx);
+  ctx->pcg_stage_head = 0xffffffffu;   // (as bahip_pcg_iteration: the accumulators are re-used)
+  const int K = ctx->num_kfs;
+  REQUIRE(K >= 1, "PCG needs at least one keyframe");
+  const uint32_t N = surfels->surfels_size;
+  const int S = ctx->in.cf_width * ctx->in.cf_height;
+  hipStream_t st = ctx->stream;
+  *out_color_camera = ctx->color_cam; *out_depth_camera = ctx->depth_cam; *out_a = ctx->dp.a;
+  if (inner_steps_out) *inner_steps_out = 0;
+  if (num_converged_out) *num_converged_out = 0;
+  // the device table is authoritative for the activations (the window functions change it there)
+  HIP_TRY(hipMemcpyAsync(ctx->host_kfs.data(), ctx->dev_kfs, sizeof(KfEntry) * K, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint32_t kInvalid = 0xffffffffu;
+  int first_active = -1;
+  bool any_covisible = false;
+  std::vector<int32_t> swept;
+  for (int k = 0; k < K; ++k) {
+    const int32_t a = ctx->host_kfs[k].activation;
+    if (a == BAHIP_KF_INACTIVE) continue;
+    swept.push_back(k);
+    if (a == BAHIP_KF_COVISIBLE_ACTIVE) any_covisible = true;
+    else if (first_active < 0) first_active = k;
+  }
+  if (first_active < 0) {   // no kActive keyframe: nothing to solve
+    if (num_converged_out) *num_converged_out = K;
+    return 0;
+  }
+  // the gauge: the fixed co-visible poses if there are any, else one kActive keyframe
+  int gauge = -1;
+  if (!any_covisible) {
+    const int g = opt->gauge_keyframe;
+    gauge = (g >= 0 && g < K && ctx->host_kfs[g].activation == BAHIP_KF_ACTIVE) ? g : first_active;
+  }
+  std::vector<uint32_t> pose_index(swept.size(), kInvalid);
+  uint32_t pose_kfs = 0;
+  for (size_t j = 0; j < swept.size(); ++j)
+    if (opt->optimize_poses && ctx->host_kfs[swept[j]].activation == BAHIP_KF_ACTIVE && swept[j] != gauge) pose_index[j] = 6u * pose_kfs++;
+
+  PcgLayout L{};
+  L.use_depth = opt->use_depth_residuals; L.use_desc = opt->use_descriptor_residuals;
+  L.optimize_poses = opt->optimize_poses; L.optimize_geometry = opt->optimize_geometry;
+  L.optimize_depth_intrinsics = opt->optimize_depth_intrinsics; L.optimize_color_intrinsics = opt->optimize_color_intrinsics;
+  L.geom_stride = L.use_desc ? 3 : 1;
+  L.gauge = gauge;   // (the windowed sweeps take the pose indices from the keyframe list)
+  uint32_t cur = 6u * pose_kfs;
+  L.surfel_start = kInvalid;
+  if (L.optimize_geometry) { L.surfel_start = cur; cur += (uint32_t)L.geom_stride * N; }
+  L.depth_intr_start = kInvalid; L.a_index = kInvalid;
+  if (L.optimize_depth_intrinsics) { L.depth_intr_start = cur; cur += 5u + (uint32_t)S; L.a_index = L.depth_intr_start + 4; }
+  L.color_intr_start = kInvalid;
+  if (L.optimize_color_intrinsics) { L.color_intr_start = cur; cur += 4; }
+  L.unknown_count = cur;
+  L.head_lo = L.optimize_geometry ? L.surfel_start : cur;
+  L.head_hi = L.optimize_geometry ? L.surfel_start + (uint32_t)L.geom_stride * N : cur;
+  L.single_keyframe = -1; L.single_pose_index = kInvalid; L.accumulate = 0;
+  const size_t U = cur;
+  const uint32_t head_count = L.head_lo + (L.unknown_count - L.head_hi);
+  if (U == 0 && !sharded) {
+    if (num_converged_out) *num_converged_out = K;
+    return 0;
+  }
+  if (U > ctx->pcg_capacity || ctx->pcg_buf == nullptr) {
+    const size_t cap = (U + U / 8 + 4096 + 3) & ~(size_t)3;
+    float* grown = nullptr;
+    HIP_TRY(hipMalloc(&grown, sizeof(float) * (5 * cap + 16)));
+    hipFree(ctx->pcg_buf);
+    ctx->pcg_buf = grown;
+    ctx->pcg_capacity = cap;
+  }
+  if (ensure_pcg_exact(ctx, head_count)) return 1;
+  // the window on the device: [tile count | keyframe list | pose indices | tile list]
+  const uint32_t tiles = (N + 63) / 64;
+  const size_t words = 1 + 2 * swept.size() + tiles;
+  if (grow_device(&ctx->pcg_window, &ctx->pcg_window_capacity, words, 1024, "the window lists of the windowed PCG scheme")) return 1;
+  uint32_t* tile_count = ctx->pcg_window;
+  int32_t* kf_list = reinterpret_cast<int32_t*>(ctx->pcg_window + 1);
+  uint32_t* pose_list = ctx->pcg_window + 1 + swept.size();
+  uint32_t* tile_list = pose_list + swept.size();
+  const SurfelsView sv = make_view(surfels);
+  HIP_TRY(hipMemcpyAsync(kf_list, swept.data(), sizeof(int32_t) * swept.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(pose_list, pose_index.data(), sizeof(uint32_t) * swept.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(tile_count, 0, sizeof(uint32_t), st));
+  launch_pcg_window_tiles(st, sv, tile_list, tile_count);
+  CHECK_LAUNCH();
+  HIP_TRY(hipMemcpyAsync(ctx->pinned_i, tile_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));   // (also: swept / pose_index have been read)
+  PcgWindow win{kf_list, pose_list, (int)swept.size(), tile_list, (uint32_t)ctx->pinned_i[0]};
+  ctx->pcg_window_last_tiles = win.num_tiles;
+  ctx->pcg_window_last_kfs = win.num_kfs;
+
+  const PcgExact ex = pcg_exact_view(ctx->pcg_exact, head_count);
+  const size_t cap = ctx->pcg_capacity;
+  float* r_ = ctx->pcg_buf; float* M_ = r_ + cap; float* delta = M_ + cap; float* g_ = delta + cap; float* p_ = g_ + cap;
+  float* sc = p_ + cap;
+  int i_an = 0, i_bn = 2;
+  HIP_TRY(hipMemsetAsync(sc, 0, sizeof(float) * 16, st));
+  HIP_TRY(hipMemsetAsync(ctx->pcg_exact, 0, sizeof(ExactCell) * pcg_exact_cells(head_count), st));
+  // the init sweep writes the rows of active surfels only: every other row of r and M is zero
+  if (U) {
+    HIP_TRY(hipMemsetAsync(r_, 0, sizeof(float) * U, st));
+    HIP_TRY(hipMemsetAsync(M_, 0, sizeof(float) * U, st));
+  }
+  const size_t x1_init = ((size_t)kHotExchanged1 * kHotReplicas + 2 * (size_t)head_count) * kExactLimbs;
+  const size_t x1_step = ((size_t)kHotExchanged1 * kHotReplicas + (size_t)head_count) * kExactLimbs;
+  const size_t x2 = ((size_t)kHotReplicas + 1) * kExactLimbs;
+  void* const x2_from = ex.invalid;
+  launch_pcg_window_init(st, L, ex, ctx->in, ctx->dev_kfs, win, sv, r_, M_);
+  CHECK_LAUNCH();
+  if (sharded && reduce_over_ranks(ctx, ex.hot, x1_init, BAHIP_SUM_I64)) return 1;
+  launch_pcg_resolve_init(st, L, ex, r_, M_);
+  CHECK_LAUNCH();
+  launch_pcg_init2(st, L, ex, ctx->dp.a, r_, M_, delta, g_, p_);
+  CHECK_LAUNCH();
+  if (sharded && reduce_over_ranks(ctx, x2_from, x2, BAHIP_SUM_I64)) return 1;
+
+  void* ctl = sc + 8;
+  if (pcg_control_bytes() > sizeof(float) * 8) return fail("PcgControl does not fit behind the scalars", __FILE__, __LINE__);
+  launch_pcg_control_init(st, ex, ctl, sc + i_an);
+  CHECK_LAUNCH();
+  // the epsilon terms of alpha_d once per SWEPT keyframe (bahip_pcg_iteration: once per keyframe)
+  const double eps_repeat = (N > 0 || sharded) ? (double)swept.size() : 0.0;
+  constexpr int kStepsPerGroup = 6;
+  int steps = 0;
+  for (int step = 0; step < opt->max_inner_iterations; ++step) {
+    if (step > 0) { const int t = i_an; i_an = i_bn; i_bn = t; }
+    timer_begin(ctx, 5, step == 0);
+    launch_pcg_window_step1(st, L, ex, ctx->in, ctx->dev_kfs, win, sv, p_, g_, ctl);
+    timer_end(ctx, 5);
+    CHECK_LAUNCH();
+    if (sharded && reduce_over_ranks(ctx, ex.hot, x1_step, BAHIP_SUM_I64)) return 1;
+    launch_pcg_resolve_step1(st, L, ex, g_, sc + 1, eps_repeat, ctl);
+    CHECK_LAUNCH();
+    launch_pcg_step2(st, L, ex, r_, M_, delta, g_, p_, sc + i_an, sc + 1, ctl);
+    CHECK_LAUNCH();
+    if (sharded && reduce_over_ranks(ctx, x2_from, x2, BAHIP_SUM_I64)) return 1;
+    launch_pcg_control(st, ex, ctl, sc + i_bn);
+    CHECK_LAUNCH();
+    if (step < opt->max_inner_iterations - 1) {
+      launch_pcg_step3(st, L, ex, g_, p_, sc + i_an, sc + i_bn, ctl);
+      CHECK_LAUNCH();
+    }
+    if ((step + 1) % kStepsPerGroup == 0 || step == opt->max_inner_iterations - 1) {
+      HIP_TRY(hipMemcpyAsync(ctx->pinned_i, ctl, 24, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(ctx->pinned_i + 8, ex.invalid, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      steps = ctx->pinned_i[4];
+      if (ctx->pinned_i[8])
+        return fail("PCG scheme: a non-finite term was added to the exact sums (on this rank or on another one); the surfels or images of "
+                    "the swept keyframes hold non-finite values", __FILE__, __LINE__);
+      if (ctx->pinned_i[3]) break;
+    }
+  }
+  if (inner_steps_out) *inner_steps_out = steps;
+
+  // ---- apply the update to the pose unknowns only; every other bound keyframe counts as converged ----
+  int num_converged = K - (int)pose_kfs;
+  if (pose_kfs > 0) {
+    std::vector<float> d(6 * (size_t)pose_kfs);
+    HIP_TRY(hipMemcpy(d.data(), delta, sizeof(float) * d.size(), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < swept.size(); ++j) {
+      if (pose_index[j] == kInvalid) continue;
+      KfEntry& e = ctx->host_kfs[swept[j]];
+      const float* dk = &d[pose_index[j]];
+      float upd[7], next[7], lg[6];
+      se3_exp(dk, upd);
+      se3_mul(e.global_T_frame, upd, next);
+      fill_pose(&e, next);
+      se3_log(upd, lg);
+      float sq = 0.f;
+      for (int c = 0; c < 3; ++c) sq += lg[c] * lg[c];
+      for (int c = 3; c < 6; ++c) { const float v = lg[c] * 10.f; sq += v * v; }
+      if (sq < 1e-06f) ++num_converged;
+    }
+    // (host_kfs is the device table as this call found it: activations included)
+    HIP_TRY(hipMemcpyAsync(ctx->dev_kfs, ctx->host_kfs.data(), sizeof(KfEntry) * K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (num_converged_out) *num_converged_out = num_converged;
+  if (L.optimize_geometry) {
+    ctx->lifecycle_bounds_tiles = 0;   // positions change: the tile bounds of an open lifecycle batch end here
+    launch_pcg_window_update_surfels(st, L, sv, delta);
+    CHECK_LAUNCH();
+  }
+  if (L.optimize_depth_intrinsics) {
+    float b[5];
+    HIP_TRY(hipMemcpy(b, delta + L.depth_intr_start, sizeof(b), hipMemcpyDeviceToHost));
+    const double old_fx_inv = 1. / ctx->depth_cam.fx, old_fy_inv = 1. / ctx->depth_cam.fy;
+    const double old_cx_pc = ctx->depth_cam.cx - 0.5, old_cy_pc = ctx->depth_cam.cy - 0.5;
+    const double old_cx_inv = -old_cx_pc * old_fx_inv, old_cy_inv = -old_cy_pc * old_fy_inv;
+    const double new_fx = 1. / (old_fx_inv + b[0]), new_fy = 1. / (old_fy_inv + b[1]);
+    out_depth_camera->fx = (float)new_fx;
+    out_depth_camera->fy = (float)new_fy;
+    out_depth_camera->cx = (float)(-(new_fx * (old_cx_inv + b[2])) + 0.5);
+    out_depth_camera->cy = (float)(-(new_fy * (old_cy_inv + b[3])) + 0.5);
+    *out_a = ctx->dp.a + b[4];
+    launch_pcg_update_cfactors(st, ctx->in, L.depth_intr_start + 5, delta, ctx->dp.cfactor, ctx->dp.cfactor_pitch_bytes);
+    CHECK_LAUNCH();
+  }
+  if (L.optimize_color_intrinsics) {
+    float b[4];
+    HIP_TRY(hipMemcpy(b, delta + L.color_intr_start, sizeof(b), hipMemcpyDeviceToHost));
+    out_color_camera->fx = (float)(ctx->color_cam.fx + b[0]);
+    out_color_camera->fy = (float)(ctx->color_cam.fy + b[1]);
+    out_color_camera->cx = (float)(ctx->color_cam.cx + b[2]);
+    out_color_camera->cy = (float)(ctx->color_cam.cy + b[3]);
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+int bahip_pcg_window_size(bahip_context* ctx, int* swept_keyframes_out, uint32_t* tiles_out) {
+  if (swept_keyframes_out) *swept_keyframes_out = ctx->pcg_window_last_kfs;
+  if (tiles_out) *tiles_out = ctx->pcg_window_last_tiles;
+  return 0;
+}
+
 // ---- the PCG scheme stage by stage (B/kernels.h:397-491) ----------------------------------------------------------------------
 }  // extern "C"
 namespace {

@@ -34,6 +34,7 @@ def _load():
         L.dba_get_keyframe_pose.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         L.dba_set_keyframe_pose.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         L.dba_get_keyframe_activation.argtypes = [C.c_void_p, C.c_int]
+        L.dba_get_keyframe_ba_iterations.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dba_download_keyframe_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.dba_upload_keyframe_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.dba_delete_keyframe.argtypes = [C.c_void_p, C.c_int]
@@ -56,6 +57,7 @@ def _load():
         L.dba_set_surfel_sharding.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
         L.dba_set_keyframe_sharding.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_set_pcg_gauge_keyframe.argtypes = [C.c_void_p, C.c_int]
+        L.dba_set_windowed_pcg.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_ba_iteration_counts.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dba_backend_context.restype = C.c_void_p
@@ -150,6 +152,13 @@ class DirectBA:
 
     def keyframe_activation(self, k):
         return self.L.dba_get_keyframe_activation(self.h, k)
+
+    def keyframe_ba_iterations(self, k):
+        """(last_active_in_ba_iteration, last_covis_in_ba_iteration) of keyframe k: the BA iteration counts of the last creation loops
+        that met it kActive / kCovisibleActive (-1: none)."""
+        a, c = C.c_int(), C.c_int()
+        assert self.L.dba_get_keyframe_ba_iterations(self.h, int(k), C.byref(a), C.byref(c)) == 0
+        return a.value, c.value
 
     def keyframe_image(self, k, which):
         names = {"depth": (0, np.uint16, 1), "normals": (1, np.uint16, 1), "radius": (2, np.uint16, 1), "color": (3, np.uint8, 4)}
@@ -306,3 +315,10 @@ class DirectBA:
 
     def set_pcg_gauge_keyframe(self, k):
         self.L.dba_set_pcg_gauge_keyframe(self.h, int(k))
+
+    def SetWindowedPCG(self, enabled):
+        """Windowed PCG scheme (default off): BundleAdjustment(use_pcg=True) honours a fixed active keyframe window and skips deleted
+        keyframes.  Raises under keyframe sharding and after SetPCGSumClasses(c > 1)."""
+        if self.L.dba_set_windowed_pcg(self.h, int(bool(enabled))) != 0:
+            raise RuntimeError("SetWindowedPCG: the windowed PCG scheme is not available under keyframe sharding or with more than one "
+                               "PCG sum class")

@@ -63,6 +63,13 @@ int dba_get_keyframe_activation(dba_handle* h, int id) {
   Keyframe* kf = get_kf(h, id);
   return kf ? (int)kf->activation() : -1;
 }
+int dba_get_keyframe_ba_iterations(dba_handle* h, int id, int* last_active_in_ba_iteration, int* last_covis_in_ba_iteration) {
+  Keyframe* kf = get_kf(h, id);
+  if (!kf) return 1;
+  if (last_active_in_ba_iteration) *last_active_in_ba_iteration = kf->last_active_in_ba_iteration();
+  if (last_covis_in_ba_iteration) *last_covis_in_ba_iteration = kf->last_covis_in_ba_iteration();
+  return 0;
+}
 
 int dba_download_keyframe_image(dba_handle* h, void* stream, int id, int which, void* out) {
   Keyframe* kf = get_kf(h, id);
@@ -250,6 +257,7 @@ int dba_set_pcg_gauge_keyframe(dba_handle* h, int id) {
   h->ba->SetPCGGaugeKeyframe(id);
   return 0;
 }
+int dba_set_windowed_pcg(dba_handle* h, int enabled) { return h->ba->SetWindowedPCG(enabled != 0) ? 0 : 1; }
 int dba_last_stats(dba_handle* h, int* pose_rounds, int* pose_steps, int* pcg_inner_steps) {
   if (pose_rounds) *pose_rounds = h->ba->last_pose_rounds();
   if (pose_steps) *pose_steps = h->ba->last_pose_steps();

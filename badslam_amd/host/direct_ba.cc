@@ -219,11 +219,29 @@ void DirectBA::SetSurfelSharding(int rank, int world, u32 chunk) {
 
 void DirectBA::SetSumClasses(int classes) { BAHIP_CHECKED_CALL(bahip_context_set_sum_classes(ctx_, classes)); }
 void DirectBA::SetIntrinsicsSumClasses(int classes) { BAHIP_CHECKED_CALL(bahip_context_set_intrinsics_sum_classes(ctx_, classes)); }
-void DirectBA::SetPCGSumClasses(int classes) { BAHIP_CHECKED_CALL(bahip_context_set_pcg_sum_classes(ctx_, classes)); }
+void DirectBA::SetPCGSumClasses(int classes) {
+  CHECK(!windowed_pcg_ || classes == 1) << "the windowed PCG scheme needs one PCG sum class: SetWindowedPCG(false) first";
+  BAHIP_CHECKED_CALL(bahip_context_set_pcg_sum_classes(ctx_, classes));
+  pcg_sum_classes_ = classes;
+}
 void DirectBA::SetFastArithmetic(bool enabled) { BAHIP_CHECKED_CALL(bahip_context_set_arithmetic(ctx_, enabled ? BAHIP_ARITHMETIC_FAST : BAHIP_ARITHMETIC_EXACT)); }
 void DirectBA::SetRowMajorCreation(bool enabled) { BAHIP_CHECKED_CALL(bahip_context_set_creation_order(ctx_, enabled ? 1 : 0)); }
 
+bool DirectBA::SetWindowedPCG(bool enabled) {
+  if (enabled && keyframe_shard_world_ > 1) {
+    LOG(ERROR) << "SetWindowedPCG: the windowed PCG scheme is not available under keyframe sharding";
+    return false;
+  }
+  if (enabled && pcg_sum_classes_ > 1) {
+    LOG(ERROR) << "SetWindowedPCG: the windowed PCG scheme needs one PCG sum class (SetPCGSumClasses(1))";
+    return false;
+  }
+  windowed_pcg_ = enabled;
+  return true;
+}
+
 void DirectBA::SetKeyframeSharding(int rank, int world) {
+  CHECK(!windowed_pcg_ || world == 1) << "the windowed PCG scheme is not available under keyframe sharding: SetWindowedPCG(false) first";
   CHECK_EQ(shard_world_, 1) << "surfel and keyframe sharding exclude each other";
   BAHIP_CHECKED_CALL(bahip_context_set_keyframe_sharding(ctx_, rank, world));
   keyframe_shard_world_ = world;
@@ -830,18 +848,37 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
                                    int active_keyframe_window_start, int active_keyframe_window_end, bool increase_ba_iteration_count,
                                    int* num_iterations_done, bool* converged, double time_limit, Timer* timer,
                                    std::function<bool(int)> progress_function) {
-  if ((active_keyframe_window_start != -1 || active_keyframe_window_end != -1) &&
+  // SetWindowedPCG(false): the reference's refusals (B/direct_ba_pcg.cc:125,140).  SetWindowedPCG(true): deleted keyframes are left
+  // out, and a fixed window that excludes a living keyframe runs bahip_pcg_iteration_windowed over it.
+  const bool windowed = windowed_pcg_;
+  if (!windowed && (active_keyframe_window_start != -1 || active_keyframe_window_end != -1) &&
       (active_keyframe_window_start != 0 || active_keyframe_window_end != (int)keyframes_.size() - 1))
     LOG(WARNING) << "The PCG-based solver implementation does not support an active window! These parameters will be ignored.";
   if (num_iterations_done) *num_iterations_done = 0;
   if (converged) *converged = false;
+  int living = 0;
+  bool window_excludes = false;   // does the fixed window leave out a living keyframe?
+  const bool fixed_active_keyframe_set = active_keyframe_window_start > 0 || active_keyframe_window_end > 0;
   for (auto& keyframe : keyframes_) {
     if (!keyframe) {
+      if (windowed) continue;
       LOG(ERROR) << "The PCG-based solver implementation does not support having deleted keyframes yet! Aborting.";
       return;
     }
+    ++living;
+    const int id = (int)keyframe->id();
+    if (id < active_keyframe_window_start || id > active_keyframe_window_end) window_excludes = true;
   }
-  CHECK_LE((int)keyframes_.size(), max_keyframe_count);
+  const bool use_window = windowed && fixed_active_keyframe_set && window_excludes;
+  CHECK_LE(living, max_keyframe_count);
+  auto set_window_activation = [this, active_keyframe_window_start, active_keyframe_window_end]() {   // as in the alternating scheme
+    for (u32 i = 0; i < keyframes_.size(); ++i) {
+      if (!keyframes_[i]) continue;
+      keyframes_[i]->SetActivation(((int)i >= active_keyframe_window_start && (int)i <= active_keyframe_window_end)
+                                       ? Keyframe::Activation::kActive : Keyframe::Activation::kInactive);
+    }
+    DetermineCovisibleActiveKeyframes();
+  };
   if (!increase_ba_iteration_count && ba_iteration_count_ != last_ba_iteration_count_) {
     last_ba_iteration_count_ = ba_iteration_count_;
     PerformBASchemeEndTasks(stream, do_surfel_updates);
@@ -864,15 +901,21 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
     if (progress_function && !progress_function(iteration)) break;
     if (num_iterations_done) ++*num_iterations_done;
     keyframes_with_new_surfels.clear();
+    if (use_window) {
+      Lock();
+      set_window_activation();
+      Unlock();
+    }
     if (optimize_geometry && do_surfel_updates) {
       bool any_new = false;
       for (const shared_ptr<Keyframe>& keyframe : keyframes_)
-        any_new |= keyframe->activation() == Keyframe::Activation::kActive && keyframe->last_active_in_ba_iteration() != ba_iteration_count_;
+        any_new |= keyframe && keyframe->activation() == Keyframe::Activation::kActive && keyframe->last_active_in_ba_iteration() != ba_iteration_count_;
       std::unique_ptr<WholeCloudScope> whole_cloud(any_new ? new WholeCloudScope(this, stream) : nullptr);   // one gather for the batch
       if (any_new) BindScene(stream);                                                                          // ... and one binding
       creation_batch_bound_ = any_new;
       std::unique_ptr<LifecycleBatch> batch(any_new ? new LifecycleBatch(this) : nullptr);
       for (shared_ptr<Keyframe>& keyframe : keyframes_) {
+        if (!keyframe) continue;
         if (keyframe->activation() == Keyframe::Activation::kActive && keyframe->last_active_in_ba_iteration() != ba_iteration_count_) {
           keyframe->SetLastActiveInBAIteration(ba_iteration_count_);
           keyframes_with_new_surfels.push_back(keyframe->id());
@@ -885,7 +928,19 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
       creation_batch_bound_ = false;
     }
     BindScene(stream);
-    BAHIP_CHECKED_CALL(bahip_memset_async(stream, active_surfels_->ToCUDA().address(), 1, surfels_size_));
+    if (use_window) {
+      // the window on the device table (BindScene took the Keyframe objects' activations; this re-derives them there), and the surfels
+      // the kActive keyframes see
+      vector<uint8_t> in_window(bound_ids_.size());
+      for (usize b = 0; b < bound_ids_.size(); ++b)
+        in_window[b] = (bound_ids_[b] >= active_keyframe_window_start && bound_ids_[b] <= active_keyframe_window_end) ? 1 : 0;
+      BAHIP_CHECKED_CALL(bahip_set_activation_window(ctx_, in_window.data(), (int)in_window.size()));
+      BAHIP_CHECKED_CALL(bahip_apply_activation_window(ctx_));
+      const bahip_surfels s = SurfelsStruct();
+      BAHIP_CHECKED_CALL(bahip_update_surfel_activation(ctx_, &s, (uint32_t)surfels_size_));
+    } else {
+      BAHIP_CHECKED_CALL(bahip_memset_async(stream, active_surfels_->ToCUDA().address(), 1, surfels_size_));
+    }
     if (optimize_geometry) {
       const bahip_surfels s = SurfelsStruct();
       BAHIP_CHECKED_CALL(bahip_update_surfel_normals(ctx_, &s));
@@ -898,17 +953,30 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
     opt.max_inner_iterations = max_inner_iterations;
     // B/direct_ba_pcg.cc:328 draws rand() % K; under keyframe sharding every rank must hold the same gauge, and a rand() stream is
     // neither shared by the instances of one process nor by those of several: there the default is keyframe 0
-    opt.gauge_keyframe = (pcg_gauge_keyframe_ >= 0) ? pcg_gauge_keyframe_ : keyframe_shard_world_ > 1 ? 0 : (rand() % (int)keyframes_.size());
+    // (a keyframe id; the gauge is a bound index: the same number while no keyframe is deleted, and rand() % living keyframes then
+    // draws what rand() % K does)
+    opt.gauge_keyframe = (pcg_gauge_keyframe_ >= 0) ? pcg_gauge_keyframe_ : keyframe_shard_world_ > 1 ? 0 : (rand() % living);
+    if (windowed && pcg_gauge_keyframe_ >= 0)
+      opt.gauge_keyframe = pcg_gauge_keyframe_ < (int)id_to_bound_.size() ? id_to_bound_[pcg_gauge_keyframe_] : -1;
     bahip_camera out_color, out_depth;
     float out_a = depth_params_.a;
     int inner_steps = 0, num_converged = 0;
     const bahip_surfels s = SurfelsStruct();
-    BAHIP_CHECKED_CALL(bahip_pcg_iteration(ctx_, &opt, &s, &out_color, &out_depth, &out_a, &inner_steps, &num_converged));
+    if (use_window) BAHIP_CHECKED_CALL(bahip_pcg_iteration_windowed(ctx_, &opt, &s, &out_color, &out_depth, &out_a, &inner_steps, &num_converged));
+    else BAHIP_CHECKED_CALL(bahip_pcg_iteration(ctx_, &opt, &s, &out_color, &out_depth, &out_a, &inner_steps, &num_converged));
     last_pcg_inner_steps_ += inner_steps;
+    num_converged += (int)keyframes_.size() - (int)bound_ids_.size();   // deleted keyframes count as converged
     if (optimize_poses) {
-      vector<float> poses(7 * keyframes_.size());
-      BAHIP_CHECKED_CALL(bahip_get_keyframe_poses(ctx_, poses.data(), (int)keyframes_.size()));
-      for (usize k = 0; k < keyframes_.size(); ++k) keyframes_[k]->set_global_T_frame(SE3f(&poses[7 * k]));
+      const int K = (int)bound_ids_.size();
+      vector<float> poses(7 * (size_t)K);
+      BAHIP_CHECKED_CALL(bahip_get_keyframe_poses(ctx_, poses.data(), K));
+      for (int b = 0; b < K; ++b) {
+        Keyframe* keyframe = keyframes_[bound_ids_[b]].get();
+        // windowed: the poses that were not unknowns keep their SE3f objects bit for bit (set_global_T_frame would rebuild
+        // frame_T_global as the inverse)
+        if (use_window && memcmp(keyframe->global_T_frame().data(), &poses[7 * (size_t)b], 7 * sizeof(float)) == 0) continue;
+        keyframe->set_global_T_frame(SE3f(&poses[7 * (size_t)b]));
+      }
     }
     if (optimize_color_intrinsics) color_camera_ = PinholeCamera4f(out_color.width, out_color.height, &out_color.fx);
     if (optimize_depth_intrinsics) {

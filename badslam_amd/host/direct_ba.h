@@ -144,6 +144,14 @@ class DirectBA {
   // (B/direct_ba_pcg.cc:328).  < 0 (default) = same rand() stream; under keyframe sharding keyframe 0 (every rank must hold the
   // same gauge).
   void SetPCGGaugeKeyframe(int keyframe_id) { pcg_gauge_keyframe_ = keyframe_id; }
+  // Windowed PCG scheme (ours; default off).  Off: BundleAdjustment(use_pcg) behaves as the reference -- it ignores an active window
+  // and does nothing while a keyframe is deleted.  On: deleted keyframes are skipped (the gauge id of SetPCGGaugeKeyframe is
+  // translated to its place among the living keyframes), and a fixed window (start > 0 or end > 0) that leaves out a living keyframe
+  // runs every outer iteration over it: window activation with co-visible keyframes, surfel creation for the kActive keyframes,
+  // surfel activation, normals, bahip_pcg_iteration_windowed.  Every other window is the whole-map iteration.  Refused (returns
+  // false) under keyframe sharding and after SetPCGSumClasses(c > 1).
+  bool SetWindowedPCG(bool enabled);
+  bool windowed_pcg() const { return windowed_pcg_; }
   // Multi-GPU surfel sharding: sums of the per-keyframe normal equations go through this hook
   // (see include/badslam_hip.h, bahip_allreduce_fn).
   void SetAllReduce(bahip_allreduce_fn fn, void* user) { BAHIP_CHECKED_CALL(bahip_context_set_allreduce(ctx_, fn, user)); }
@@ -257,6 +265,8 @@ class DirectBA {
   vector<int> bound_ids_;        // bound list index -> keyframe id
   vector<int> id_to_bound_;      // keyframe id -> bound list index (-1 for deleted keyframes)
   int pcg_gauge_keyframe_ = -1;
+  bool windowed_pcg_ = false;
+  int pcg_sum_classes_ = 1;        // (SetPCGSumClasses: the windowed scheme needs 1)
   int shard_rank_ = 0, shard_world_ = 1, whole_cloud_depth_ = 0;
   int keyframe_shard_world_ = 1;
   u32 shard_chunk_ = 0;

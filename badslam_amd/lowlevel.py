@@ -386,16 +386,18 @@ class Scene:
         return cc, dc, a.value
 
     def pcg_iteration(self, optimize_poses=True, optimize_geometry=True, optimize_depth_intrinsics=False,
-                      optimize_color_intrinsics=False, use_depth=True, use_desc=True, max_inner_iterations=30, gauge_keyframe=0):
-        """One outer iteration of the PCG scheme on the bound keyframes; adopts new poses / intrinsics."""
+                      optimize_color_intrinsics=False, use_depth=True, use_desc=True, max_inner_iterations=30, gauge_keyframe=0,
+                      windowed=False):
+        """One outer iteration of the PCG scheme on the bound keyframes; adopts new poses / intrinsics.  windowed: over the active
+        keyframe window of the device table and the active surfels (bahip_pcg_iteration_windowed)."""
         opt = capi.PCGOptions(int(optimize_poses), int(optimize_geometry), int(optimize_depth_intrinsics),
                               int(optimize_color_intrinsics), int(use_depth), int(use_desc), int(max_inner_iterations),
                               int(gauge_keyframe))
         cc, dc, a = capi.Camera(), capi.Camera(), C.c_float()
         steps, conv = C.c_int(), C.c_int()
         s = self.surfels_struct()
-        capi.check(self.lib.bahip_pcg_iteration(self.ctx.handle, C.byref(opt), C.byref(s), C.byref(cc), C.byref(dc), C.byref(a),
-                                                C.byref(steps), C.byref(conv)))
+        fn = self.lib.bahip_pcg_iteration_windowed if windowed else self.lib.bahip_pcg_iteration
+        capi.check(fn(self.ctx.handle, C.byref(opt), C.byref(s), C.byref(cc), C.byref(dc), C.byref(a), C.byref(steps), C.byref(conv)))
         K = len(self.keyframes)
         if optimize_poses and K:
             poses = (C.c_float * (7 * K))()

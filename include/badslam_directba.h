@@ -35,6 +35,9 @@ int dba_keyframe_count(dba_handle* h);
 int dba_get_keyframe_pose(dba_handle* h, int keyframe_id, float global_T_frame[7]);
 int dba_set_keyframe_pose(dba_handle* h, int keyframe_id, const float global_T_frame[7]);
 int dba_get_keyframe_activation(dba_handle* h, int keyframe_id);
+/* Keyframe::last_active_in_ba_iteration / last_covis_in_ba_iteration: the BA iteration count of the last surfel-creation loop that met
+ * the keyframe kActive (it then created surfels) / kCovisibleActive; -1 before any */
+int dba_get_keyframe_ba_iterations(dba_handle* h, int keyframe_id, int* last_active_in_ba_iteration, int* last_covis_in_ba_iteration);
 /* Keyframe image access (tests poke depth / normals in place like the reference's do):
  * which: 0 depth u16, 1 normals u16, 2 radius u16, 3 colour rgba u8x4.  Dense host arrays. */
 int dba_download_keyframe_image(dba_handle* h, void* hip_stream, int keyframe_id, int which, void* out);
@@ -86,6 +89,9 @@ int dba_cfactor_size(dba_handle* h, int* width, int* height);
 int dba_download_cfactor(dba_handle* h, void* hip_stream, float* out);
 int dba_clear_cfactor(dba_handle* h, void* hip_stream);
 int dba_set_pcg_gauge_keyframe(dba_handle* h, int keyframe_id);
+/* DirectBA::SetWindowedPCG (ours, default off): BundleAdjustment(use_pcg) honours a fixed active keyframe window and skips deleted
+ * keyframes; returns 1 (refused) under keyframe sharding and with more than one PCG sum class */
+int dba_set_windowed_pcg(dba_handle* h, int enabled);
 /* DirectBA::SetSurfelSharding: this object holds rank `rank`'s chunk-cyclic shard of one surfel cloud (bahip_gather_surfel_shards) */
 int dba_set_surfel_sharding(dba_handle* h, int rank, int world, uint32_t chunk);
 /* DirectBA::SetSumClasses: 4 (default) or 8 interleaved keyframe classes in the definition of the per-surfel sums

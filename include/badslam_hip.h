@@ -481,6 +481,23 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
                         bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a,
                         int* inner_steps_out, int* num_converged_out /* keyframes whose pose update is below the
                         convergence threshold, gauge keyframe included (B/direct_ba_pcg.cc:556-575) */);
+/* The same outer iteration over the active keyframe window (ours; B/direct_ba_pcg.cc:125,140 refuse windows).  The system
+ * (kernels_pcg_window.hip: "DEFINITION of the windowed system"): keyframes whose activation in the device table is not
+ * BAHIP_KF_INACTIVE are swept in bound order (a kInactive one is not read at all); 6 pose unknowns per BAHIP_KF_ACTIVE keyframe;
+ * BAHIP_KF_COVISIBLE_ACTIVE keyframes contribute residuals with fixed poses and then anchor the gauge -- without any, the gauge
+ * is opt->gauge_keyframe (a bound index) if it is kActive, else the first kActive keyframe; surfel unknowns are the surfels with
+ * the active bit (the layout stays 1 or 3 per surfel; inactive surfels keep zero rows and are left bit-identical).  The epsilon
+ * terms of alpha_d count once per swept keyframe.  Poses of keyframes that are not unknowns are not touched, and count as
+ * converged in num_converged_out.  With every keyframe kActive and every surfel active: the system of bahip_pcg_iteration.
+ * Surfel sharding: the exchanges of bahip_pcg_iteration, the same bits as one GPU.  Refused (error text, context usable) under
+ * keyframe sharding and with bahip_context_set_pcg_sum_classes(c > 1).  No kActive keyframe or no unknowns: returns 0 with every
+ * keyframe counted as converged. */
+int bahip_pcg_iteration_windowed(bahip_context* ctx, const bahip_pcg_options* opt, const bahip_surfels* surfels,
+                                 bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a,
+                                 int* inner_steps_out, int* num_converged_out);
+/* Size of the window of the last bahip_pcg_iteration_windowed call that got as far as building it: swept keyframes and 64-surfel
+ * tiles with an active surfel on this rank (diagnostics). */
+int bahip_pcg_window_size(bahip_context* ctx, int* swept_keyframes_out, uint32_t* tiles_out);
 
 /* ---- PCG solver, stage by stage (B/kernels.h:397-491): the entry points a caller that keeps the reference's own PCG driver
  * (B/direct_ba_pcg.cc:229-646) binds -- one bahip_ function per *CUDA function, same call sequence:
