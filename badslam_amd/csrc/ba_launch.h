@@ -341,6 +341,13 @@ void launch_create_batch_item_records(hipStream_t st, const Intrinsics& in, cons
 void launch_delete_partial(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, int kf_rank, int kf_world,
                            uint32_t* partial, uint32_t stride);
 void launch_delete_decide(hipStream_t st, const SurfelsView& s, const uint32_t* partial, uint32_t stride, int kf_world, int min_obs, uint32_t* deleted_count);
+// The lifecycle dealt over a surfel partition (kernels_lifecycle_dealt.hip): deletion + radius update over this rank's chunks of the
+// gathered cloud (chunk c belongs to rank c % world) into packed[i] = (x, radius^2) words of a zero-filled vector of s.size uint2, the
+// count of what it newly deleted into *deleted_count; after the sum over the ranks, the unpack writes the two rows for every surfel.
+uint32_t dealt_surfel_count(uint32_t total, uint32_t rank, uint32_t world, uint32_t chunk);   // surfels of `total` in rank's chunks
+void launch_delete_chunks(hipStream_t st, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, uint32_t rank, uint32_t world,
+                          uint32_t chunk, int min_obs, void* packed, uint32_t* deleted_count);
+void launch_delete_unpack(hipStream_t st, const SurfelsView& s, const void* packed);
 void launch_shard_to_cloud(hipStream_t st, const SurfelsView& shard, const SurfelsView& cloud, uint32_t rank, uint32_t world, uint32_t chunk);
 void launch_cloud_to_shard(hipStream_t st, const SurfelsView& cloud, const SurfelsView& shard, uint32_t rank, uint32_t world, uint32_t chunk);
 size_t sort_scratch_bytes(uint32_t n);

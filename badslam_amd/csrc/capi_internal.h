@@ -84,9 +84,13 @@ int stage_upload(UploadStage* stage, void* dev_dst, const void* src, size_t byte
                  const void* src2 = nullptr, size_t bytes2 = 0, void* dev_dst2 = nullptr);
 void stage_free(UploadStage* stage);
 
+constexpr int kGatherTableWords = 128;   // bahip_gather_surfel_shards: (size, count) of at most 64 ranks
+constexpr int kDealStats = 8;            // bahip_debug_lifecycle_deal_stats
 constexpr int kIntrMaxSlices = 16;   // slices of the intrinsics sweep (capi_solvers.hip): automatic up to 8, forced up to 16 (half the record memory again)
 struct bahip_context {
   UploadStage stage_kfs, stage_covis, stage_window;
+  UploadStage stage_gather;        // bahip_gather_surfel_shards: the (size, count) table goes up and comes back through its page-locked buffer
+  long long* dev_gather_table = nullptr;   // ... and is summed here (kGatherTableWords int64, allocated once)
   hipStream_t stream = nullptr;
   bool have_intrinsics = false;
   bahip_camera color_cam{}, depth_cam{};
@@ -211,6 +215,14 @@ struct bahip_context {
   size_t kf_partials_capacity = 0; // floats
   long long* dev_cost = nullptr;   // rows of the cost sweep (kernels_cost.hip): kCostWords int64 per keyframe
   size_t cost_capacity = 0;        // int64 words
+  // dealing the lifecycle under surfel sharding (bahip_context_set_lifecycle_dealing): the switch, and the surfel partition of the
+  // whole-cloud phase in progress -- set by bahip_gather_surfel_shards, cleared by bahip_extract_surfel_shard (deal_world 1: none) --
+  // with the gathered cloud it belongs to: lifecycle calls on any other buffer are not dealt
+  int lifecycle_dealing = 0;
+  int deal_rank = 0, deal_world = 1;
+  uint32_t deal_chunk = 0;
+  const void* deal_data = nullptr;
+  long long deal_stats[kDealStats] = {};   // what this rank swept of the dealt phases (bahip_debug_lifecycle_deal_stats)
   long long exchange_calls = 0;    // sums over the ranks requested since the last reset (bahip_exchange_stats), and their bytes
   long long exchange_bytes = 0;
 
@@ -292,6 +304,15 @@ inline uint32_t owned_classes(const bahip_context* ctx, int classes) {
   for (int c = 0; c < classes; ++c) if ((c & (ctx->kf_world - 1)) == ctx->kf_rank) owned |= 1u << c;
   return owned;
 }
+// The lifecycle dealt over the ranks of a surfel partition (bahip_context_set_lifecycle_dealing): on, inside a whole-cloud phase of two or
+// more ranks (a power of two: the dealt kernels test ownership as k & (world - 1)), with a transport, never under keyframe sharding.
+// Bound keyframe k belongs to rank k % deal_world; surfel i of the gathered cloud to rank (i / deal_chunk) % deal_world.  Only a call on
+// the buffer the phase's gather filled is dealt (a host that gathers without extracting leaves no stale partition for other buffers).
+inline bool lifecycle_dealt(const bahip_context* ctx, const bahip_surfels* surfels) {
+  return ctx->lifecycle_dealing && ctx->deal_world > 1 && (ctx->deal_world & (ctx->deal_world - 1)) == 0 && !kf_sharded(ctx) && is_sharded(ctx) &&
+         surfels != nullptr && surfels->data != nullptr && surfels->data == ctx->deal_data;
+}
+inline bool deal_owned(const bahip_context* ctx, int k) { return (k & (ctx->deal_world - 1)) == ctx->deal_rank; }
 #define REQUIRE_NO_KF_SHARDING(what) \
   REQUIRE(!kf_sharded(ctx), what " is not available under keyframe sharding (its per-surfel sums run over all keyframes in order): use surfel sharding")
 

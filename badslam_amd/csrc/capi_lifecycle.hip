@@ -175,6 +175,7 @@ static int merge_by_cell_lists(bahip_context* ctx, const std::vector<MergeBatchF
     HIP_TRY(hipStreamSynchronize(st));
     // members and member_cell packed behind each other for one exchange: [pairs] words, then [pairs] uint2 (pairs <= sweep)
     const size_t pairs = ((size_t)first[(size_t)num_frames] + 1) & ~(size_t)1;
+    if (!kf_sharded(ctx)) ctx->deal_stats[7] += first[(size_t)num_frames];   // (lifecycle dealing: the pairs whose members are exchanged)
     member_cell = members + pairs;
     HIP_TRY(hipMemsetAsync(members, 0, 3 * sizeof(uint32_t) * pairs, st));
     for (int j = 0; j < num_frames; ++j)
@@ -332,8 +333,9 @@ int bahip_merge_surfels_for_bound_keyframes(bahip_context* ctx, float merge_dist
   for (int j = 0; j < num_keyframes; ++j) REQUIRE(keyframe_indices[j] >= 0 && keyframe_indices[j] < ctx->num_kfs, "keyframe index out of range");
   if (merged_count_out) *merged_count_out = 0;
   const bool sharded = kf_sharded(ctx);
+  const bool dealt = lifecycle_dealt(ctx, surfels);   // (lifecycle dealing: the association and fill sweeps by owner, as under keyframe sharding)
   bool by_cells = false;
-  if ((g_merge_cells_enabled || sharded) && num_keyframes > 0 && surfels->surfels_size > 0) {
+  if ((g_merge_cells_enabled || sharded || dealt) && num_keyframes > 0 && surfels->surfels_size > 0) {
     const bool bounds_valid = ctx->lifecycle_bounds_tiles != 0 && ctx->lifecycle_bounds_data == surfels->data &&
                               (uint64_t)ctx->lifecycle_bounds_tiles * 64 <= surfels->surfels_size && !ctx->lifecycle_list_counts.empty();
     const uint32_t bounded_tiles = ctx->lifecycle_bounds_tiles;
@@ -354,14 +356,19 @@ int bahip_merge_surfels_for_bound_keyframes(bahip_context* ctx, float merge_dist
       table[j].list_count = ctx->lifecycle_list_counts[f];
       table[j].pair_offset = (uint32_t)positions;
       table[j].pad_ = 0;
-      owned[j] = kf_owned(ctx, keyframe_indices[j]) ? 1 : 0;
+      owned[j] = (dealt ? deal_owned(ctx, keyframe_indices[j]) : kf_owned(ctx, keyframe_indices[j])) ? 1 : 0;
       positions += (uint64_t)table[j].list_count + tail;
       max_positions = std::max(max_positions, table[j].list_count + tail);
     }
     REQUIRE(known || !sharded, "keyframe sharding: bahip_merge_surfels_for_bound_keyframes needs an open lifecycle batch that knows its keyframes "
                                "(bahip_lifecycle_batch_begin, bahip_lifecycle_batch_set_keyframes)");
-    if (known && merge_by_cell_lists(ctx, table, sharded ? &owned : nullptr, positions, max_positions, merge_dist_factor, surfels, sup[0], &by_cells)) return 1;
+    if (known && merge_by_cell_lists(ctx, table, (sharded || dealt) ? &owned : nullptr, positions, max_positions, merge_dist_factor, surfels, sup[0], &by_cells)) return 1;
     REQUIRE(by_cells || !sharded, "keyframe sharding: the merge batch is too large for its cell lists: split it");
+    if (by_cells && dealt) {
+      for (int j = 0; j < num_keyframes; ++j)
+        if (owned[j]) { ctx->deal_stats[2] += 1; ctx->deal_stats[3] += keyframe_indices[j] + 1; }
+      ctx->deal_stats[5] += 1;
+    }
   }
   if (!by_cells && num_keyframes > 0 && surfels->surfels_size > 0) {
     auto entry_of = [&](int j, KfEntry* e) { *e = ctx->host_kfs[keyframe_indices[j]]; return 0; };
@@ -678,6 +685,104 @@ static int create_batch_keyframe_sharded(bahip_context* ctx, const int* keyframe
   return 0;
 }
 
+// The up-front part of the creation chain dealt over a surfel partition (lifecycle dealing; every rank holds the gathered cloud and every
+// keyframe's images).  For the chained keyframes 0 .. n - 1 of `items` (the batch but its last keyframe), in the keyframe-sharded
+// kernels' form, each exchange an integer sum of zero-filled partials:
+//   owner of j: occupancy row j at the batch's begin, candidates row j, the candidates' raw words      -> exchange 1
+//   every rank: filter counts over the co-visible keyframes it owns (when filtering)                  -> exchange 2
+//   every rank: the filter's decision, the scan, the compact list's positions
+//   owner of j: the records of j's candidates, their cells                                            -> exchange 3 (when any)
+// Out: what launch_create_batch_prepare leaves for the chain -- occupancy rows of `cells` bytes, the compact list's cells and records, the
+// list position of every keyframe's first candidate.  The chain itself runs unchanged on every rank and reads the images it needs itself
+// (no exchange per keyframe).  *prepared = false: too large for one pass (nothing launched; the caller takes the replicated path).
+static int create_upfront_dealt(bahip_context* ctx, const std::vector<CreateBatchItem>& items, bool filter_counts, bool filter_new_surfels,
+                                int min_observation_count, const bahip_surfels* surfels, uint32_t bounded_tiles, uint8_t** occupancy_out,
+                                uint32_t** cand_cell_out, SurfelsView* records_out, std::vector<uint32_t>* first_out, bool* prepared) {
+  *prepared = false;
+  hipStream_t st = ctx->stream;
+  const size_t px = create_padded_count(ctx->in);
+  const size_t cells = (size_t)ctx->in.cf_width * (size_t)ctx->in.cf_height;
+  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t N = items.size(), columns = (N * cells + 63) & ~(size_t)63;
+  const uint32_t all_tiles = (surfels->surfels_size + 63u) / 64u, tail = all_tiles > bounded_tiles ? all_tiles - bounded_tiles : 0u;
+  // one block: occupancy, candidates, their raw words (one exchange: aligned sizes, zero padding), the filter counts, the scan, the compact
+  // list's cells followed by its records, the items, two words of scratch, the library's temporary
+  const size_t occupancy_bytes = align(N * cells), candidates_bytes = align(N * px), cand_px_bytes = align(sizeof(uint32_t) * N * cells),
+               counts_bytes = align(sizeof(uint32_t) * 2 * N * cells), scan_bytes = align(sizeof(uint32_t) * N * px),
+               list_bytes = align(sizeof(uint32_t) * columns) + align(sizeof(float) * columns * kSurfelAccum0),
+               items_bytes = align(sizeof(CreateBatchItem) * N), scan_temp_bytes = create_batch_scan_temp_bytes(N * px);
+  const size_t need = occupancy_bytes + candidates_bytes + cand_px_bytes + counts_bytes + scan_bytes + list_bytes + items_bytes + align(2 * sizeof(uint32_t)) +
+                      align(scan_temp_bytes);
+  if (!(need <= ((size_t)16 << 30) && sizeof(float) * columns * (kSurfelAccum0 + 1) < ((size_t)1 << 32) && N * px < ((size_t)1 << 31))) return 0;
+  if (need > ctx->create_batch_bytes) {
+    HIP_TRY(hipStreamSynchronize(st));
+    hipFree(ctx->dev_create_batch); ctx->dev_create_batch = nullptr; ctx->create_batch_bytes = 0;
+    HIP_TRY(hipMalloc(&ctx->dev_create_batch, need + need / 4));
+    ctx->create_batch_bytes = need + need / 4;
+  }
+  char* p = static_cast<char*>(ctx->dev_create_batch);
+  uint8_t* occupancy = reinterpret_cast<uint8_t*>(p); p += occupancy_bytes;
+  uint8_t* candidates = reinterpret_cast<uint8_t*>(p); p += candidates_bytes;
+  uint32_t* cand_px = reinterpret_cast<uint32_t*>(p); p += cand_px_bytes;
+  void* filter_counts_buf = p; p += counts_bytes;
+  uint32_t* scan = reinterpret_cast<uint32_t*>(p); p += scan_bytes;
+  uint32_t* cand_cell = reinterpret_cast<uint32_t*>(p); p += list_bytes;
+  CreateBatchItem* dev_items = reinterpret_cast<CreateBatchItem*>(p); p += items_bytes;
+  uint32_t* scratch2 = reinterpret_cast<uint32_t*>(p); p += align(2 * sizeof(uint32_t));
+  void* scan_temp = p;
+  HIP_TRY(hipMemcpyAsync(dev_items, items.data(), N * sizeof(CreateBatchItem), hipMemcpyHostToDevice, st));
+  // ---- exchange 1: what the owners compute from their images
+  const size_t span_a = occupancy_bytes + candidates_bytes + cand_px_bytes;
+  HIP_TRY(hipMemsetAsync(occupancy, 0, span_a, st));
+  const SurfelsView cloud_at_begin = make_view(surfels);
+  for (size_t j = 0; j < N; ++j)
+    if (deal_owned(ctx, items[j].kf_index)) {
+      launch_create_batch_item_candidates(st, ctx->in, ctx->dev_kfs, dev_items + j, items[j].list_count + tail, cloud_at_begin, ctx->dev_lifecycle_lists,
+                                          bounded_tiles, occupancy + j * cells, candidates + j * px, cand_px + j * cells, ctx->host_kfs[items[j].kf_index]);
+      ctx->deal_stats[0] += 1; ctx->deal_stats[1] += items[j].kf_index + 1;
+    }
+  CHECK_LAUNCH();
+  if (kf_exchange(ctx, occupancy, span_a, "the creation batch's candidates (lifecycle dealing)")) return 1;
+  // ---- exchange 2: the outlier filter's counts over each rank's co-visible keyframes; the decision on every rank
+  if (filter_new_surfels) {
+    HIP_TRY(hipMemsetAsync(filter_counts_buf, 0, counts_bytes, st));
+    if (filter_counts) {
+      launch_create_batch_filter_count(st, ctx->in, ctx->dev_kfs, dev_items, (int)N, ctx->dev_covis, ctx->dev_covis_T, candidates, cand_px, filter_counts_buf,
+                                       ctx->deal_rank, ctx->deal_world);
+      CHECK_LAUNCH();
+      if (kf_exchange(ctx, filter_counts_buf, counts_bytes, "the creation batch's filter counts (lifecycle dealing)")) return 1;
+    }
+    launch_create_batch_filter_decide(st, ctx->in, (int)N, filter_counts_buf, min_observation_count, candidates);
+    CHECK_LAUNCH();
+  }
+  // ---- the compact candidate list: first[j] = the list position of keyframe j's first candidate (the inclusive scan's row ends)
+  HIP_TRY(launch_create_batch_scan(st, ctx->in, (int)N, candidates, scan, scan_temp, scan_temp_bytes));
+  std::vector<uint32_t>& first = *first_out;
+  first.assign(N + 1, 0u);
+  HIP_TRY(hipMemcpy2DAsync(first.data() + 1, sizeof(uint32_t), scan + (px - 1), sizeof(uint32_t) * px, sizeof(uint32_t), N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));   // `items` is the caller's pageable vector; the chain's grids come from `first`
+  const size_t total = first[N], total_al = (total + 63) & ~(size_t)63;
+  // ---- exchange 3: the owners' records -- the list's cells, then kSurfelAccum0 rows of total_al columns
+  SurfelsView records;
+  records.data = reinterpret_cast<float*>(cand_cell + total_al); records.pitch = (uint32_t)(sizeof(float) * total_al); records.active = nullptr;
+  records.size = (uint32_t)total_al;
+  if (total) {
+    HIP_TRY(hipMemsetAsync(cand_cell, 0, sizeof(uint32_t) * total_al * (kSurfelAccum0 + 1), st));
+    for (size_t j = 0; j < N; ++j)
+      if (deal_owned(ctx, items[j].kf_index) && first[j + 1] > first[j])
+        launch_create_batch_item_records(st, ctx->in, ctx->dev_kfs, dev_items + j, candidates + j * px, scan + j * px, cand_cell, records, scratch2);
+    CHECK_LAUNCH();
+    if (kf_exchange(ctx, cand_cell, sizeof(uint32_t) * total_al * (kSurfelAccum0 + 1), "the creation batch's records (lifecycle dealing)")) return 1;
+  }
+  ctx->deal_stats[5] += 1;
+  ctx->deal_stats[6] += (long long)total;
+  *occupancy_out = occupancy;
+  *cand_cell_out = cand_cell;
+  *records_out = records;
+  *prepared = true;
+  return 0;
+}
+
 // A batch of keyframes creating surfels, one after the other as the reference does (each sees what the ones before it appended,
 // B/direct_ba_alternating.cc:389-425), but without the host in between: the cloud's size lives on the device for the duration of
 // the batch, the co-visibility lists and relative poses of all keyframes go up front in one copy, and the host reads the final size
@@ -781,7 +886,17 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
     const size_t columns = n * cells, scan_temp_bytes = known ? create_batch_scan_temp_bytes(n * px) : 0;
     const size_t need = align(occupancy_bytes) + align(candidates_bytes) + align(sizeof(uint32_t) * n * px) + align(sizeof(uint32_t) * columns) +
                         align(sizeof(float) * columns * kSurfelAccum0) + align(sizeof(CreateBatchItem) * n) + align(sizeof(uint32_t) * (n + 1)) + align(scan_temp_bytes);
-    if (known && need <= ((size_t)16 << 30) && sizeof(float) * columns < ((size_t)1 << 32) && n * px < ((size_t)1 << 31)) {   // (the scan counts in int)
+    const bool dealt = lifecycle_dealt(ctx, surfels);
+    uint8_t* occupancy = nullptr;
+    uint32_t* cand_cell = nullptr;
+    SurfelsView records;
+    std::vector<uint32_t> first(n + 1);
+    bool prepared = false;
+    if (known && dealt) {
+      // the up-front sweeps dealt by owner, the chain below as it is (lifecycle dealing: create_upfront_dealt)
+      if (create_upfront_dealt(ctx, items, filter_new_surfels != 0 && covis_offsets[n] > 0, filter_new_surfels != 0, min_observation_count, surfels,
+                               bounded_tiles, &occupancy, &cand_cell, &records, &first, &prepared)) return 1;
+    } else if (known && need <= ((size_t)16 << 30) && sizeof(float) * columns < ((size_t)1 << 32) && n * px < ((size_t)1 << 31)) {   // (the scan counts in int)
       if (need > ctx->create_batch_bytes) {
         HIP_TRY(hipStreamSynchronize(st));
         hipFree(ctx->dev_create_batch); ctx->dev_create_batch = nullptr; ctx->create_batch_bytes = 0;
@@ -789,11 +904,10 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
         ctx->create_batch_bytes = need + need / 4;
       }
       char* p = static_cast<char*>(ctx->dev_create_batch);
-      uint8_t* occupancy = reinterpret_cast<uint8_t*>(p); p += align(occupancy_bytes);
+      occupancy = reinterpret_cast<uint8_t*>(p); p += align(occupancy_bytes);
       uint8_t* candidates = reinterpret_cast<uint8_t*>(p); p += align(candidates_bytes);
       uint32_t* scan = reinterpret_cast<uint32_t*>(p); p += align(sizeof(uint32_t) * n * px);
-      uint32_t* cand_cell = reinterpret_cast<uint32_t*>(p); p += align(sizeof(uint32_t) * columns);
-      SurfelsView records;
+      cand_cell = reinterpret_cast<uint32_t*>(p); p += align(sizeof(uint32_t) * columns);
       records.data = reinterpret_cast<float*>(p); records.pitch = (uint32_t)(sizeof(float) * columns); records.active = nullptr; records.size = (uint32_t)columns;
       p += align(sizeof(float) * columns * kSurfelAccum0);
       CreateBatchItem* dev_items = reinterpret_cast<CreateBatchItem*>(p); p += align(sizeof(CreateBatchItem) * n);
@@ -806,9 +920,11 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
       HIP_TRY(launch_create_batch_prepare(st, ctx->in, ctx->dev_kfs, dev_items, (int)n, max_list, cloud_at_begin, ctx->dev_lifecycle_lists, bounded_tiles, occupancy,
                                           candidates, filter_new_surfels != 0, ctx->dev_covis, ctx->dev_covis_T, min_observation_count, scan, scan_temp,
                                           scan_temp_bytes, cand_cell, records, first_of_item));
-      std::vector<uint32_t> first(n + 1);
       HIP_TRY(hipMemcpyAsync(first.data(), first_of_item, sizeof(uint32_t) * (n + 1), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));   // `items` is pageable and goes out of scope; the chain's grids come from `first`
+      prepared = true;
+    }
+    if (prepared) {
       bahip_surfels whole = *surfels;
       whole.surfels_size = surfels->capacity;   // (the chain addresses rows by index; sizes are read on the device)
       const SurfelsView s = make_view(&whole);
@@ -887,6 +1003,28 @@ int bahip_delete_surfels_and_update_radii(bahip_context* ctx, int min_observatio
     HIP_TRY(hipMemcpyAsync(ctx->pinned_i, ctx->dev_counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *deleted_count_out = (uint32_t)ctx->pinned_i[0];
+    return 0;
+  }
+  if (lifecycle_dealt(ctx, surfels)) {
+    // lifecycle dealing (kernels_lifecycle_dealt.hip): each rank decides the surfels of its own chunks of the gathered cloud over all
+    // keyframes; per surfel the (x, radius^2) words the decision leaves, and the count, are summed over the ranks as int64
+    const SurfelsView v = make_view(surfels);
+    const size_t words = (size_t)v.size + 1;   // one int64 per surfel, then the count of newly deleted surfels
+    if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, 2 * words, 0, "the rows of the dealt deletion")) return 1;
+    void* packed = ctx->kf_partials;
+    uint32_t* count = reinterpret_cast<uint32_t*>(ctx->kf_partials) + 2 * (size_t)v.size;
+    HIP_TRY(hipMemsetAsync(packed, 0, 8 * words, ctx->stream));
+    launch_delete_chunks(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, v, (uint32_t)ctx->deal_rank, (uint32_t)ctx->deal_world, ctx->deal_chunk,
+                         min_observation_count, packed, count);
+    CHECK_LAUNCH();
+    if (kf_exchange(ctx, packed, 8 * words, "the deletion's rows (lifecycle dealing)")) return 1;
+    launch_delete_unpack(ctx->stream, v, packed);
+    CHECK_LAUNCH();
+    HIP_TRY(hipMemcpyAsync(ctx->pinned_i, count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *deleted_count_out = (uint32_t)ctx->pinned_i[0];
+    ctx->deal_stats[4] += dealt_surfel_count(v.size, (uint32_t)ctx->deal_rank, (uint32_t)ctx->deal_world, ctx->deal_chunk);
+    ctx->deal_stats[5] += 1;
     return 0;
   }
   HIP_TRY(hipMemsetAsync(ctx->dev_counter, 0, sizeof(int), ctx->stream));

@@ -107,7 +107,22 @@ int bahip_context_set_keyframe_sharding(bahip_context* ctx, int rank, int world)
   REQUIRE(world <= ctx->sum_classes, "keyframe sharding over 8 ranks needs the 8-class definition of the per-surfel sums: bahip_context_set_sum_classes(ctx, 8) "
                                      "first (on the single-GPU run it is compared with as well: the class count is part of the sums' definition)");
   REQUIRE(rank >= 0 && rank < world, "keyframe sharding: rank out of range");
+  REQUIRE(world == 1 || !ctx->lifecycle_dealing, "keyframe sharding deals its own lifecycle: bahip_context_set_lifecycle_dealing(ctx, 0) first");
   ctx->kf_rank = rank; ctx->kf_world = world;
+  return 0;
+}
+
+int bahip_context_set_lifecycle_dealing(bahip_context* ctx, int enabled) {
+  REQUIRE(ctx != nullptr, "bahip_context_set_lifecycle_dealing: NULL argument");
+  REQUIRE(!enabled || !kf_sharded(ctx), "lifecycle dealing is refused under keyframe sharding, which deals its lifecycle by keyframe already");
+  ctx->lifecycle_dealing = enabled ? 1 : 0;
+  return 0;
+}
+
+int bahip_debug_lifecycle_deal_stats(bahip_context* ctx, long long* stats_out, int reset) {
+  REQUIRE(ctx != nullptr, "bahip_debug_lifecycle_deal_stats: NULL argument");
+  if (stats_out) memcpy(stats_out, ctx->deal_stats, sizeof(ctx->deal_stats));
+  if (reset) memset(ctx->deal_stats, 0, sizeof(ctx->deal_stats));
   return 0;
 }
 
@@ -199,15 +214,18 @@ int bahip_gather_surfel_shards(bahip_context* ctx, const bahip_surfels* shard, u
   REQUIRE(world >= 1 && rank >= 0 && rank < world && chunk > 0 && chunk % 64 == 0, "bahip_gather_surfel_shards: bad partition (chunks are whole 64-surfel tiles)");
   REQUIRE(world <= 64, "bahip_gather_surfel_shards: at most 64 ranks");
   hipStream_t st = ctx->stream;
-  // every rank's (size, count): a sum over the ranks of a table that is zero except for the own row
-  long long table[128] = {0};
+  // every rank's (size, count): a sum over the ranks of a table that is zero except for the own row.  The table lives on the device for
+  // the context's lifetime and travels through the gather's page-locked stage both ways (no allocation, no free, one stream wait).
+  long long table[kGatherTableWords] = {0};
   table[2 * rank] = shard->surfels_size; table[2 * rank + 1] = shard_surfel_count;
-  DevMem dev_table;
-  HIP_TRY(hipMalloc(&dev_table.p, sizeof(table)));
-  HIP_TRY(hipMemcpyAsync(dev_table.p, table, sizeof(table), hipMemcpyHostToDevice, st));
-  if (reduce_over_ranks(ctx, dev_table.p, 2 * (size_t)world, BAHIP_SUM_I64)) return 1;
-  HIP_TRY(hipMemcpyAsync(table, dev_table.p, sizeof(table), hipMemcpyDeviceToHost, st));
+  if (!ctx->dev_gather_table) HIP_TRY(hipMalloc(&ctx->dev_gather_table, sizeof(table)));
+  if (stage_upload(&ctx->stage_gather, ctx->dev_gather_table, table, sizeof(table), st)) return 1;
+  if (reduce_over_ranks(ctx, ctx->dev_gather_table, 2 * (size_t)world, BAHIP_SUM_I64)) return 1;
+  // (stream order: the upload has read the stage before this copy writes it)
+  HIP_TRY(hipMemcpyAsync(ctx->stage_gather.pinned, ctx->dev_gather_table, sizeof(table), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  ctx->stage_gather.pending = false;
+  memcpy(table, ctx->stage_gather.pinned, sizeof(table));
   uint64_t total = 0, count = 0;
   for (int r = 0; r < world; ++r) { total += (uint64_t)table[2 * r]; count += (uint64_t)table[2 * r + 1]; }
   REQUIRE(is_sharded(ctx) || world == 1, "bahip_gather_surfel_shards: world > 1 needs a communicator or an all-reduce hook");
@@ -228,6 +246,8 @@ int bahip_gather_surfel_shards(bahip_context* ctx, const bahip_surfels* shard, u
   if (cv.active && reduce_over_ranks(ctx, cv.active, ((size_t)total + 7) / 8, BAHIP_SUM_I64)) return 1;
   if (cloud_surfels_size_out) *cloud_surfels_size_out = (uint32_t)total;
   if (cloud_surfel_count_out) *cloud_surfel_count_out = (uint32_t)count;
+  // a whole-cloud phase over this partition begins: what the lifecycle deals goes by it (bahip_context_set_lifecycle_dealing)
+  ctx->deal_rank = rank; ctx->deal_world = world; ctx->deal_chunk = chunk; ctx->deal_data = cloud->data;
   return 0;
 }
 
@@ -237,6 +257,7 @@ int bahip_extract_surfel_shard(bahip_context* ctx, const bahip_surfels* cloud, i
   const uint32_t mine = shard_size_of(cloud->surfels_size, rank, world, chunk);
   REQUIRE(mine <= shard->capacity, "bahip_extract_surfel_shard: the shard buffer is too small");
   shard->surfels_size = mine;
+  ctx->deal_rank = 0; ctx->deal_world = 1; ctx->deal_chunk = 0; ctx->deal_data = nullptr;   // the whole-cloud phase ends
   launch_cloud_to_shard(ctx->stream, make_view(cloud), make_view(shard), (uint32_t)rank, (uint32_t)world, chunk);
   CHECK_LAUNCH();
   if (shard_surfels_size_out) *shard_surfels_size_out = mine;

@@ -58,6 +58,7 @@ def _load():
         L.dba_set_keyframe_sharding.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_set_pcg_gauge_keyframe.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_windowed_pcg.argtypes = [C.c_void_p, C.c_int]
+        L.dba_set_distributed_lifecycle.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_ba_iteration_counts.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dba_backend_context.restype = C.c_void_p
@@ -315,6 +316,12 @@ class DirectBA:
 
     def set_pcg_gauge_keyframe(self, k):
         self.L.dba_set_pcg_gauge_keyframe(self.h, int(k))
+
+    def SetDistributedLifecycle(self, enabled):
+        """Under surfel sharding (default off): the surfel lifecycle's sweeps are dealt over the ranks -- creation and merging by keyframe
+        owner, deletion by surfel chunk -- with the bits of the replicated run.  Raises under keyframe sharding."""
+        if self.L.dba_set_distributed_lifecycle(self.h, int(bool(enabled))) != 0:
+            raise RuntimeError("SetDistributedLifecycle: refused under keyframe sharding, which deals its lifecycle by keyframe already")
 
     def SetWindowedPCG(self, enabled):
         """Windowed PCG scheme (default off): BundleAdjustment(use_pcg=True) honours a fixed active keyframe window and skips deleted

@@ -258,6 +258,7 @@ int dba_set_pcg_gauge_keyframe(dba_handle* h, int id) {
   return 0;
 }
 int dba_set_windowed_pcg(dba_handle* h, int enabled) { return h->ba->SetWindowedPCG(enabled != 0) ? 0 : 1; }
+int dba_set_distributed_lifecycle(dba_handle* h, int enabled) { return h->ba->SetDistributedLifecycle(enabled != 0) ? 0 : 1; }
 int dba_last_stats(dba_handle* h, int* pose_rounds, int* pose_steps, int* pcg_inner_steps) {
   if (pose_rounds) *pose_rounds = h->ba->last_pose_rounds();
   if (pose_steps) *pose_steps = h->ba->last_pose_steps();

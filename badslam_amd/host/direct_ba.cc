@@ -240,7 +240,21 @@ bool DirectBA::SetWindowedPCG(bool enabled) {
   return true;
 }
 
+bool DirectBA::SetDistributedLifecycle(bool enabled) {
+  if (enabled && keyframe_shard_world_ > 1) {
+    LOG(ERROR) << "SetDistributedLifecycle: keyframe sharding deals its lifecycle by keyframe already";
+    return false;
+  }
+  if (bahip_context_set_lifecycle_dealing(ctx_, enabled ? 1 : 0) != 0) {
+    LOG(ERROR) << "SetDistributedLifecycle: " << bahip_last_error();
+    return false;
+  }
+  distributed_lifecycle_ = enabled;
+  return true;
+}
+
 void DirectBA::SetKeyframeSharding(int rank, int world) {
+  CHECK(!distributed_lifecycle_ || world == 1) << "keyframe sharding deals its own lifecycle: SetDistributedLifecycle(false) first";
   CHECK(!windowed_pcg_ || world == 1) << "the windowed PCG scheme is not available under keyframe sharding: SetWindowedPCG(false) first";
   CHECK_EQ(shard_world_, 1) << "surfel and keyframe sharding exclude each other";
   BAHIP_CHECKED_CALL(bahip_context_set_keyframe_sharding(ctx_, rank, world));
@@ -368,9 +382,9 @@ void DirectBA::MergeForKeyframes(const vector<u32>& keyframe_ids) {
   }
   if (frames.empty()) return;
   LifecycleBatch batch(this);
-  if (keyframe_shard_world_ > 1) {
+  if (keyframe_shard_world_ > 1 || (distributed_lifecycle_ && shard_world_ > 1 && batched_creation_)) {
     // by bound index: a rank knows which keyframes it owns (the bound poses are the keyframes' current ones: every merge pass follows a
-    // binding of the scene)
+    // binding of the scene); the same deletions as the frame-based call below
     CHECK(batched_creation_) << "keyframe sharding merges through the batched call only";
     vector<int> bound;
     for (u32 id : keyframe_ids)

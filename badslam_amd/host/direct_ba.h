@@ -161,6 +161,13 @@ class DirectBA {
   // rank, runs unchanged, and takes the shard back out -- so a sharded BundleAdjustment with do_surfel_updates ends with the
   // bits of the unsharded one.  Needs SetAllReduce (or an RCCL communicator on the backend context) when world > 1.
   void SetSurfelSharding(int rank, int world, u32 chunk);
+  // Under surfel sharding (ours; default off): deal the surfel lifecycle's sweeps over the ranks instead of running them on every rank
+  // (bahip_context_set_lifecycle_dealing).  The creation batch's and the merge batches' per-keyframe sweeps run on the keyframe's owner
+  // (bound index % world), deletion on each rank's own surfel chunks; the results are exchanged and every rank ends with the same bits
+  // as with the mode off.  Merging then goes through the by-index batch call, so SetBatchedCreation(false) leaves it replicated.
+  // Refused (returns false) under keyframe sharding; does nothing at world 1.
+  bool SetDistributedLifecycle(bool enabled);
+  bool distributed_lifecycle() const { return distributed_lifecycle_; }
   // Multi-GPU KEYFRAME sharding (bahip_context_set_keyframe_sharding): this object holds ALL surfels; of the keyframes it needs
   // the images of those with (index among the non-deleted keyframes) % world == rank only (world = 1, 2, 4, or 8 after
   // SetSumClasses(8)).  Covers the
@@ -266,6 +273,7 @@ class DirectBA {
   vector<int> id_to_bound_;      // keyframe id -> bound list index (-1 for deleted keyframes)
   int pcg_gauge_keyframe_ = -1;
   bool windowed_pcg_ = false;
+  bool distributed_lifecycle_ = false;   // SetDistributedLifecycle
   int pcg_sum_classes_ = 1;        // (SetPCGSumClasses: the windowed scheme needs 1)
   int shard_rank_ = 0, shard_world_ = 1, whole_cloud_depth_ = 0;
   int keyframe_shard_world_ = 1;

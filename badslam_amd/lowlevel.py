@@ -178,6 +178,19 @@ class Scene:
                                                               cells.ctypes.data_as(C.POINTER(C.c_float)) if with_cells else None))
         return glob, cells
 
+    def set_lifecycle_dealing(self, enabled):
+        """Deal the lifecycle calls of a whole-cloud phase (between bahip_gather_surfel_shards over world >= 2 ranks and the extract)
+        over that surfel partition (bahip_context_set_lifecycle_dealing)."""
+        capi.check(self.lib.bahip_context_set_lifecycle_dealing(self.ctx.handle, int(bool(enabled))))
+
+    def lifecycle_deal_stats(self, reset=True):
+        """[creation keyframes swept, sum of their index + 1, merge keyframes swept, sum of their index + 1, deletion surfels swept,
+        dealt calls, creation candidates exchanged, merge pairs exchanged] of this rank since the last reset
+        (bahip_debug_lifecycle_deal_stats)."""
+        out = (C.c_longlong * 8)()
+        capi.check(self.lib.bahip_debug_lifecycle_deal_stats(self.ctx.handle, out, int(bool(reset))))
+        return [int(v) for v in out]
+
     def set_keyframe_sharding(self, rank, world):
         """Keyframe k lives on rank k % world (bahip_context_set_keyframe_sharding); bind_keyframes then hands over the
         images of this rank's keyframes only (null pointers for the others: the backend must not look at them)."""

@@ -94,6 +94,9 @@ int dba_set_pcg_gauge_keyframe(dba_handle* h, int keyframe_id);
 int dba_set_windowed_pcg(dba_handle* h, int enabled);
 /* DirectBA::SetSurfelSharding: this object holds rank `rank`'s chunk-cyclic shard of one surfel cloud (bahip_gather_surfel_shards) */
 int dba_set_surfel_sharding(dba_handle* h, int rank, int world, uint32_t chunk);
+/* DirectBA::SetDistributedLifecycle (ours, default off): under surfel sharding the lifecycle's sweeps are dealt over the ranks
+ * (bahip_context_set_lifecycle_dealing) with the same bits; returns 1 (refused) under keyframe sharding */
+int dba_set_distributed_lifecycle(dba_handle* h, int enabled);
 /* DirectBA::SetSumClasses: 4 (default) or 8 interleaved keyframe classes in the definition of the per-surfel sums
  * (bahip_context_set_sum_classes) */
 int dba_set_sum_classes(dba_handle* h, int classes);

@@ -149,6 +149,41 @@ int bahip_context_set_allreduce(bahip_context* ctx, bahip_allreduce_fn fn, void*
  * say which rank owns it) are refused in this mode.  A hook or an RCCL communicator must be installed when world > 1.  Surfel and
  * keyframe sharding exclude each other on one context. */
 int bahip_context_set_keyframe_sharding(bahip_context* ctx, int rank, int world);
+/* Dealing the surfel lifecycle over the ranks of a SURFEL partition (ours; off by default).  Under surfel sharding the
+ * lifecycle runs inside a whole-cloud phase: bahip_gather_surfel_shards gives every rank the whole cloud, and every rank holds every
+ * keyframe's images.  With the mode on, the lifecycle calls between a gather of world >= 2 ranks (a power of two) and the following
+ * bahip_extract_surfel_shard deal their sweeps over that partition -- bound keyframe k belongs to rank k % world, surfel i of the
+ * gathered cloud to rank (i / chunk) % world -- and exchange what they computed as integer sums (BAHIP_SUM_I64) of zero-filled
+ * partials or counts, so every rank ends with the bits of the replicated call.  Sizes at BASELINE configs[2] (640 x 480 pixels,
+ * 320 x 240 = 76 800 sparse cells, 3 M surfels), per call:
+ *   bahip_create_surfels_for_keyframes (a batch of n >= 2 keyframes inside a lifecycle batch that knows them): the keyframes but the
+ *     last are the chain's; their owners sweep the occupancy at the batch's begin, the candidates and their raw depth / normal words ->
+ *     ONE exchange of (n - 1) x (cells + padded pixels + 4 cells) bytes, each part rounded up to 256 (691 200 bytes per keyframe); the outlier filter's counts over
+ *     each rank's co-visible keyframes -> ONE exchange of (n - 1) x cells x 8 bytes (614 400 bytes per keyframe; only when filtering
+ *     with co-visibility lists); the owners' records -> ONE exchange of 36 bytes per candidate (none without candidates).  The chain
+ *     (create_chain_kernel) and the last keyframe then run on every rank as in the replicated call, with no exchange per keyframe, so
+ *     the caller's supporting planes end as the replicated call leaves them.  A batch of one keyframe, or one the lifecycle batch does
+ *     not know, is not dealt;
+ *   bahip_merge_surfels_for_bound_keyframes (inside a lifecycle batch that knows its keyframes): the owners' association and fill
+ *     sweeps -> TWO exchanges, the per-(keyframe, cell) counts (n x cells x 4 bytes: 307 200 bytes per keyframe) and the cells'
+ *     members (12 bytes per associated pair); the scan and the decisions stay on every rank.  bahip_merge_surfels_for_keyframes is
+ *     not dealt (a frame does not say which keyframe it is);
+ *   bahip_delete_surfels_and_update_radii: dealt by SURFEL chunk, not by keyframe -- each rank decides its own chunks over all
+ *     keyframes -> ONE exchange of 8 bytes per surfel + 8 (24 MB for 3 M surfels; keyframe dealing would take (2 + world) x 4 bytes
+ *     per surfel).  The data rows end as delete_update's; the scratch rows it fills are not written;
+ *   compaction and the spatial order read no image and run as they are.
+ * Only calls on the cloud the gather filled (the same surfels->data) are dealt: the gather and the extract must come in pairs.
+ * More bytes move than in the replicated call: on a 16-keyframe 640 x 480 drop-in call the mode moved 72 MB per rank, 12.8 MB
+ * without it (the merge members at 12 bytes per pair dominate).  Whether it pays depends on the links.
+ * With the mode off, or at world 1, every call takes the replicated path and its exchanges (none inside the phase).  Valid with or
+ * without a hook / communicator installed (a gather of world >= 2 needs one); refused under keyframe sharding, which deals its own
+ * lifecycle by keyframe (and bahip_context_set_keyframe_sharding with world > 1 is refused while the mode is on). */
+int bahip_context_set_lifecycle_dealing(bahip_context* ctx, int enabled);
+/* What this rank swept of the dealt lifecycle since the last reset: [0] creation keyframes whose up-front sweeps it ran, [1] the sum of
+ * (their bound index + 1), [2] merge keyframes whose association / fill sweeps it ran, [3] the sum of (their bound index + 1), [4]
+ * surfels whose deletion it decided, [5] calls that took the dealt path, [6] creation candidates whose records were exchanged, [7] merge
+ * (surfel, keyframe) pairs whose cell members were exchanged.  stats_out: 8 words. */
+int bahip_debug_lifecycle_deal_stats(bahip_context* ctx, long long* stats_out, int reset);
 /* The number of interleaved partial sums (keyframe classes) the per-surfel sums of the normals and geometry passes are DEFINED
  * over: 4 (default) or 8.  In exact arithmetic both are the reference's sum (B/kernel_opt_geometry.cu: keyframe after keyframe);
  * in binary32 they differ in the last bits like any reordering.  The oracle takes the same parameter (orc_set_sum_classes), and
@@ -735,7 +770,11 @@ int bahip_stage_work_units(bahip_context* ctx, int stage, long long* units_out);
  * rows 0 .. 7 and the active flags travel (one int64 all-reduce per row: bit patterns are preserved), the scratch rows do not.
  * Returns the cloud's size and surfel count (the sums over the ranks) and checks that the shard sizes are those of the
  * chunk-cyclic partition.  bahip_extract_surfel_shard: shard := this rank's surfels of a cloud of cloud->surfels_size; returns
- * the shard's size.  Without a communicator / hook (one GPU) both are plain copies. */
+ * the shard's size.  Without a communicator / hook (one GPU) both are plain copies.  The gather's (size, count) table is summed in a
+ * buffer the context keeps and travels through its page-locked stage (no allocation per call, one wait on the stream).  A gather over
+ * world >= 2 ranks opens the whole-cloud phase that bahip_context_set_lifecycle_dealing deals over; the extract closes it.  The two
+ * come in pairs: a host that gathers only to read the cloud should extract (or gather again) before it drives the lifecycle on other
+ * buffers -- calls on any buffer other than the gathered cloud are never dealt, but the phase stays open for that cloud. */
 int bahip_gather_surfel_shards(bahip_context* ctx, const bahip_surfels* shard, uint32_t shard_surfel_count, int rank, int world, uint32_t chunk,
                                bahip_surfels* cloud, uint32_t* cloud_surfels_size_out, uint32_t* cloud_surfel_count_out);
 int bahip_extract_surfel_shard(bahip_context* ctx, const bahip_surfels* cloud, int rank, int world, uint32_t chunk, bahip_surfels* shard,
