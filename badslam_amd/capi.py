@@ -79,6 +79,11 @@ class Cost(C.Structure):           # bahip_cost: the value of the BA objective (
                 ("depth_residuals", C.c_uint64), ("descriptor_pairs", C.c_uint64)]
 
 
+class PCGStepControl(C.Structure):   # bahip_pcg_step_control: step control of the PCG scheme (bahip_pcg_iteration_controlled)
+    _fields_ = [("lambda_initial", C.c_float), ("lambda_up", C.c_float), ("lambda_down", C.c_float),
+                ("lambda_min", C.c_float), ("lambda_max", C.c_float), ("max_trials", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol declared in include/badslam_hip.h
@@ -177,6 +182,12 @@ SIGNATURES = {
     "bahip_pcg_iteration_windowed": (C.c_int, [C.c_void_p, C.POINTER(PCGOptions), C.POINTER(Surfels), C.POINTER(Camera),
                                                C.POINTER(Camera), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bahip_pcg_window_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "bahip_context_set_pcg_damping": (C.c_int, [C.c_void_p, C.c_float]),
+    "bahip_context_get_pcg_damping": (C.c_float, [C.c_void_p]),
+    "bahip_pcg_iteration_controlled": (C.c_int, [C.c_void_p, C.POINTER(PCGOptions), C.POINTER(PCGStepControl), C.c_int, C.c_int,
+                                                 C.POINTER(Surfels), C.POINTER(C.c_float), C.POINTER(Camera), C.POINTER(Camera),
+                                                 C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                                 C.POINTER(Cost), C.POINTER(Cost), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bahip_pcg_begin": (C.c_int, [C.c_void_p, C.POINTER(PCGLayout), C.c_uint32]),
     "bahip_pcg_init": (C.c_int, [C.c_void_p, C.POINTER(PCGLayout), C.POINTER(Frame), C.POINTER(C.c_float), C.c_uint32, C.c_int,
                                  C.POINTER(Surfels), C.c_void_p, C.c_void_p]),

@@ -359,6 +359,18 @@ struct PcgClasses {
   int classes;
   int entries;
 };
+// What the snapshot / restore pair of a trial step covers (kernels_pcg_trial.hip: "SNAPSHOT / RESTORE").
+constexpr int kPcgTrialMaxRows = 8;   // the data rows of a surfel (kSurfelX .. kSurfelDescriptor2)
+struct PcgTrialShape {
+  uint32_t num_tiles;          // 64-surfel tiles saved: the tiles of tile_list, or tiles [0, num_tiles) when it is NULL
+  const uint32_t* tile_list;
+  uint32_t rows_mask;          // bit r: surfel row r is saved; rows_saved = its population count
+  uint32_t rows_saved;
+  uint32_t* kf_table;          // the keyframe table as words (kf_words may be 0)
+  uint32_t kf_words;
+  uint32_t* cfactor;           // the cfactor plane (cf_width x cf_height words, rows cf_pitch_bytes apart; 0 x 0: not saved)
+  uint32_t cf_pitch_bytes, cf_width, cf_height;
+};
 // The window of the windowed PCG sweeps (kernels_pcg_window.hip): the swept keyframes (bound indices, ascending) with the index of
 // their first pose unknown (0xffffffff: pose fixed), and the 64-surfel tiles that hold an active surfel.
 struct PcgWindow {

@@ -239,6 +239,19 @@ void launch_pcg_window_step1(hipStream_t st, const PcgLayout& L, const PcgExact&
                              const SurfelsView& s, const float* p, float* g, const void* ctl);
 void launch_pcg_window_update_surfels(hipStream_t st, const PcgLayout& L, const SurfelsView& s, const float* delta);
 
+// kernels_pcg_trial.hip: the per-unknown kernels under a damping factor (lambda == 0: the kernels above themselves), and the
+// snapshot / restore of what a PCG outer iteration writes (`snap`: pcg_trial_snapshot_words(t) words)
+void launch_pcg_damped_init2(hipStream_t st, const PcgLayout& L, const PcgExact& ex, float lambda, float a, const float* r, const float* M,
+                             float* delta, float* g, float* p);
+void launch_pcg_damped_eps_terms(hipStream_t st, const PcgLayout& L, const PcgExact& ex, float lambda, const float* M, const float* p);
+void launch_pcg_damped_step2(hipStream_t st, const PcgLayout& L, const PcgExact& ex, float lambda, float* r, const float* M, float* delta, float* g,
+                             const float* p, const float* alpha_n, const float* alpha_d, const void* ctl);
+void launch_pcg_damped_step3(hipStream_t st, const PcgLayout& L, const PcgExact& ex, float lambda, const float* M, const float* g, float* p,
+                             const float* alpha_n, const float* beta_n, const void* ctl);
+size_t pcg_trial_snapshot_words(const PcgTrialShape& t);
+void launch_pcg_trial_snapshot(hipStream_t st, const SurfelsView& s, const PcgTrialShape& t, uint32_t* snap);
+void launch_pcg_trial_restore(hipStream_t st, const SurfelsView& s, const PcgTrialShape& t, uint32_t* snap);
+
 // kernels_lifecycle.hip
 void launch_supporting_fill(hipStream_t st, const SupportingView& sup, int w, int h);
 void launch_lifecycle_bounds(hipStream_t st, const SurfelsView& s, uint32_t tiles, void* spheres);   // bounding spheres of tiles [0, tiles)

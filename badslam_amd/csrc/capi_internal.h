@@ -204,6 +204,9 @@ struct bahip_context {
   void* pcg_stage_ctl = nullptr;   // stage API (bahip_pcg_begin ...): a control block that never stops, the head size the
   uint32_t pcg_stage_head = 0;     // accumulators were set up for, and the bahip_pcg_step1 calls since the last step 2
   int pcg_stage_step1_calls = 0;
+  float pcg_damping = 0.f;         // lambda of the damped PCG system (bahip_context_set_pcg_damping; kernels_pcg_trial.hip)
+  uint32_t* pcg_trial = nullptr;   // bahip_pcg_iteration_controlled: [tile count | tile list] followed by the snapshot
+  size_t pcg_trial_capacity = 0;   // words
   int world = 0;                   // ranks of the RCCL communicator (0 = none)
   int kf_rank = 0, kf_world = 1;   // keyframe sharding (bahip_context_set_keyframe_sharding): keyframe k lives on rank k % kf_world (1, 2, 4 or 8)
   int arithmetic = 0;              // BAHIP_ARITHMETIC_EXACT / _FAST: flavour of the sweeps (bahip_context_set_arithmetic), mirrored in in.fast_math

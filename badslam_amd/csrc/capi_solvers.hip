@@ -353,7 +353,7 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
   if (sharded && reduce_over_ranks(ctx, ex.hot, x1_init, BAHIP_SUM_I64)) return 1;   // (slot kHotEpsLocal is still zero here)
   launch_pcg_resolve_init(st, L, ex, r_, M_);
   CHECK_LAUNCH();
-  launch_pcg_init2(st, L, ex, ctx->dp.a, r_, M_, delta, g_, p_);
+  launch_pcg_damped_init2(st, L, ex, ctx->pcg_damping, ctx->dp.a, r_, M_, delta, g_, p_);
   CHECK_LAUNCH();
   if (!count_replicated) HIP_TRY(hipMemsetAsync(dot_local, 0, sizeof(ExactCell) * kHotReplicas, st));
   if (sharded && reduce_over_ranks(ctx, x2_from, x2, BAHIP_SUM_I64)) return 1;
@@ -381,14 +381,14 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
     if (sharded && reduce_over_ranks(ctx, ex.hot, x1_step, BAHIP_SUM_I64)) return 1;   // g head, intrinsics entries, alpha_d terms
     launch_pcg_resolve_step1(st, L, ex, g_, sc + 1, eps_repeat, ctl);
     CHECK_LAUNCH();
-    launch_pcg_step2(st, L, ex, r_, M_, delta, g_, p_, sc + i_an, sc + 1, ctl);
+    launch_pcg_damped_step2(st, L, ex, ctx->pcg_damping, r_, M_, delta, g_, p_, sc + i_an, sc + 1, ctl);
     CHECK_LAUNCH();
     if (!count_replicated) HIP_TRY(hipMemsetAsync(dot_local, 0, sizeof(ExactCell) * kHotReplicas, st));
     if (sharded && reduce_over_ranks(ctx, x2_from, x2, BAHIP_SUM_I64)) return 1;
     launch_pcg_control(st, ex, ctl, sc + i_bn);
     CHECK_LAUNCH();
     if (step < opt->max_inner_iterations - 1) {
-      launch_pcg_step3(st, L, ex, g_, p_, sc + i_an, sc + i_bn, ctl);
+      launch_pcg_damped_step3(st, L, ex, ctx->pcg_damping, M_, g_, p_, sc + i_an, sc + i_bn, ctl);
       CHECK_LAUNCH();
     }
     if ((step + 1) % kStepsPerGroup == 0 || step == opt->max_inner_iterations - 1) {
@@ -582,7 +582,7 @@ int bahip_pcg_iteration_windowed(bahip_context* ctx, const bahip_pcg_options* op
   if (sharded && reduce_over_ranks(ctx, ex.hot, x1_init, BAHIP_SUM_I64)) return 1;
   launch_pcg_resolve_init(st, L, ex, r_, M_);
   CHECK_LAUNCH();
-  launch_pcg_init2(st, L, ex, ctx->dp.a, r_, M_, delta, g_, p_);
+  launch_pcg_damped_init2(st, L, ex, ctx->pcg_damping, ctx->dp.a, r_, M_, delta, g_, p_);
   CHECK_LAUNCH();
   if (sharded && reduce_over_ranks(ctx, x2_from, x2, BAHIP_SUM_I64)) return 1;
 
@@ -603,13 +603,13 @@ int bahip_pcg_iteration_windowed(bahip_context* ctx, const bahip_pcg_options* op
     if (sharded && reduce_over_ranks(ctx, ex.hot, x1_step, BAHIP_SUM_I64)) return 1;
     launch_pcg_resolve_step1(st, L, ex, g_, sc + 1, eps_repeat, ctl);
     CHECK_LAUNCH();
-    launch_pcg_step2(st, L, ex, r_, M_, delta, g_, p_, sc + i_an, sc + 1, ctl);
+    launch_pcg_damped_step2(st, L, ex, ctx->pcg_damping, r_, M_, delta, g_, p_, sc + i_an, sc + 1, ctl);
     CHECK_LAUNCH();
     if (sharded && reduce_over_ranks(ctx, x2_from, x2, BAHIP_SUM_I64)) return 1;
     launch_pcg_control(st, ex, ctl, sc + i_bn);
     CHECK_LAUNCH();
     if (step < opt->max_inner_iterations - 1) {
-      launch_pcg_step3(st, L, ex, g_, p_, sc + i_an, sc + i_bn, ctl);
+      launch_pcg_damped_step3(st, L, ex, ctx->pcg_damping, M_, g_, p_, sc + i_an, sc + i_bn, ctl);
       CHECK_LAUNCH();
     }
     if ((step + 1) % kStepsPerGroup == 0 || step == opt->max_inner_iterations - 1) {
@@ -760,7 +760,7 @@ int bahip_pcg_init2(bahip_context* ctx, const bahip_pcg_layout* layout, uint32_t
   if (stage_ready(ctx, L)) return 1;
   const PcgExact ex = pcg_exact_view(ctx->pcg_exact, ctx->pcg_stage_head);
   launch_pcg_resolve_init(ctx->stream, L, ex, pcg_r, pcg_M);
-  launch_pcg_init2(ctx->stream, L, ex, a, pcg_r, pcg_M, pcg_delta, pcg_g, pcg_p);
+  launch_pcg_damped_init2(ctx->stream, L, ex, ctx->pcg_damping, a, pcg_r, pcg_M, pcg_delta, pcg_g, pcg_p);
   launch_pcg_control_init(ctx->stream, ex, ctx->pcg_stage_ctl, pcg_alpha_n);
   CHECK_LAUNCH();
   ctx->pcg_stage_step1_calls = 0;
@@ -790,9 +790,9 @@ int bahip_pcg_step2(bahip_context* ctx, const bahip_pcg_layout* layout, uint32_t
   // produce p; here p is the caller's): whatever an earlier stage left in those two slots is dropped first
   HIP_TRY(hipMemsetAsync(ex.hot + (size_t)kHotEpsLocal * kHotReplicas, 0, sizeof(ExactCell) * kHotReplicas, ctx->stream));
   HIP_TRY(hipMemsetAsync(ex.hot_tail + (size_t)(kHotEpsHead - kHotExchanged1) * kHotReplicas, 0, sizeof(ExactCell) * kHotReplicas, ctx->stream));
-  launch_pcg_eps_terms(ctx->stream, L, ex, pcg_p);
+  launch_pcg_damped_eps_terms(ctx->stream, L, ex, ctx->pcg_damping, pcg_M, pcg_p);
   launch_pcg_resolve_step1(ctx->stream, L, ex, pcg_g, pcg_alpha_d, (double)ctx->pcg_stage_step1_calls, ctx->pcg_stage_ctl);
-  launch_pcg_step2(ctx->stream, L, ex, pcg_r, pcg_M, pcg_delta, pcg_g, pcg_p, pcg_alpha_n, pcg_alpha_d, ctx->pcg_stage_ctl);
+  launch_pcg_damped_step2(ctx->stream, L, ex, ctx->pcg_damping, pcg_r, pcg_M, pcg_delta, pcg_g, pcg_p, pcg_alpha_n, pcg_alpha_d, ctx->pcg_stage_ctl);
   launch_pcg_control(ctx->stream, ex, ctx->pcg_stage_ctl, pcg_beta_n);
   // the stage API never stops on its own: clear what the control kernel decided
   HIP_TRY(hipMemsetAsync(ctx->pcg_stage_ctl, 0, 64, ctx->stream));
@@ -805,6 +805,8 @@ int bahip_pcg_step3(bahip_context* ctx, const bahip_pcg_layout* layout, uint32_t
                     const float* pcg_alpha_n, const float* pcg_beta_n) {
   const PcgLayout L = stage_layout(layout, surfels_size);
   if (stage_ready(ctx, L)) return 1;
+  // (no damping here: p does not depend on it, and the epsilon terms this kernel leaves are dropped by the next bahip_pcg_step2, which
+  // adds the damped ones from the p it is given)
   launch_pcg_step3(ctx->stream, L, pcg_exact_view(ctx->pcg_exact, ctx->pcg_stage_head), pcg_g, pcg_p, pcg_alpha_n, pcg_beta_n, ctx->pcg_stage_ctl);
   CHECK_LAUNCH();
   return 0;

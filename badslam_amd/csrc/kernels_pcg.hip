@@ -38,9 +38,6 @@
 
 namespace bahip {
 
-constexpr int kPcgBlock = 256;     // per-unknown vector kernels
-constexpr float kDiagEpsilon = 1e-8f;   // B/kernel_pcg.cu:44
-constexpr float kAPriorWeight = 10.f;   // B/kernel_pcg.cu:48
 
 __device__ __forceinline__ uint32_t kf_pose_index(const PcgLayout& L, int k) {
   // B/direct_ba_pcg.cc:329-337
@@ -51,10 +48,6 @@ __device__ __forceinline__ uint32_t kf_pose_index(const PcgLayout& L, int k) {
 __device__ __forceinline__ bool kf_pose_is_unknown(const PcgLayout& L, int k) {
   return L.optimize_poses && (L.single_keyframe >= 0 || k != L.gauge);
 }
-__device__ __forceinline__ float prior_at(const PcgLayout& L, uint32_t u) {
-  return (u == L.a_index) ? (kAPriorWeight * kAPriorWeight) : 0.f;
-}
-__device__ __forceinline__ bool is_local(const PcgLayout& L, uint32_t u) { return u >= L.head_lo && u < L.head_hi; }
 // Slot (0..8) of a global intrinsics unknown among the replicated accumulators, or -1.
 __device__ __forceinline__ int intrinsics_slot(const PcgLayout& L, uint32_t u) {
   if (L.optimize_depth_intrinsics && u >= L.depth_intr_start && u < L.depth_intr_start + 5u) return (int)(u - L.depth_intr_start);
@@ -388,40 +381,7 @@ pcg_class_combine_kernel(PcgLayout L, PcgClasses pc, uint32_t surfels, float* __
   }
 }
 
-// ---- exact dot products in the per-unknown kernels -----------------------------------------------------------------------------
-// A thread's terms over the local (surfel) unknowns go into a private column of limbs in workgroup memory (the limb index is
-// data dependent); terms of dense-head unknowns -- few -- go straight to the head's replicated slot with atomics.  At the end
-// the workgroup folds its columns and adds 9 limbs per sum to one of the 64 replicas.
-template <int kSets>
-struct BlockExact {
-  long long limbs[kSets][kExactLimbs][kPcgBlock];
-};
-template <int kSets>
-__device__ __forceinline__ void block_exact_clear(BlockExact<kSets>& b) {
-#pragma unroll
-  for (int set = 0; set < kSets; ++set)
-#pragma unroll
-    for (int j = 0; j < kExactLimbs; ++j) b.limbs[set][j][threadIdx.x] = 0;
-}
-template <int kSets>
-__device__ __forceinline__ void block_exact_add(BlockExact<kSets>& b, int set, float v, unsigned* invalid) {
-  exact_lds_add(&b.limbs[set][0][0], kPcgBlock, (int)threadIdx.x, v, invalid);
-}
-template <int kSets>
-__device__ __forceinline__ void block_exact_flush(BlockExact<kSets>& b, const PcgExact& ex, const int (&slots)[kSets]) {
-  __syncthreads();
-  const int replica = (int)(blockIdx.x & (kHotReplicas - 1));
-  const int part = threadIdx.x & 15;
-  for (int row = threadIdx.x >> 4; row < kSets * kExactLimbs; row += kPcgBlock >> 4) {   // 16 threads fold one row of 256 columns
-    const long long* line = &b.limbs[0][0][0] + (size_t)row * kPcgBlock;
-    long long sum = 0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) sum += line[c * 16 + part];
-    for (int off = 8; off; off >>= 1) sum += __shfl_xor(sum, off);
-    if (part == 0 && sum != 0) limb_atomic_add(&hot_cell(ex, slots[row / kExactLimbs], replica)->limb[row % kExactLimbs], sum);
-  }
-}
-
+// (the exact dot products of the per-unknown kernels: pcg_device.h, BlockExact)
 // PCGInit2 (B/kernel_pcg.cu:565-600); also the epsilon terms of the first step's alpha_d (they depend on p alone)
 __global__ void __launch_bounds__(kPcgBlock)
 pcg_init2_kernel(PcgLayout L, PcgExact ex, float a, const float* __restrict__ r_, const float* __restrict__ M_, float* __restrict__ delta,
@@ -852,8 +812,6 @@ void launch_exact_sum_debug(hipStream_t st, const PcgExact& ex, const float* val
 namespace bahip {
 // ---- launchers -----------------------------------------------------------------------------------------------
 static inline unsigned gU(uint32_t n) { return (n + kPcgBlock - 1) / kPcgBlock; }
-// The per-unknown kernels run a grid-stride loop over at most kPcgReduceBlocks workgroups: each ends in 9 atomics per sum.
-constexpr unsigned kPcgReduceBlocks = 1024;
 static inline unsigned gR(uint32_t n) { return gU(n) < kPcgReduceBlocks ? gU(n) : kPcgReduceBlocks; }
 
 // whole XCD chunks, as in kernels_surfel.hip (xcd_chunked_tile)

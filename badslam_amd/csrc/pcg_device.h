@@ -26,6 +26,51 @@ struct PcgControl {
 };
 static_assert(sizeof(PcgControl) == 24, "PcgControl lives behind the scalars of the PCG buffer");
 
+// ---- what the per-unknown kernels share (kernels_pcg.hip and the damped ones of kernels_pcg_trial.hip) ----
+constexpr int kPcgBlock = 256;     // per-unknown vector kernels
+// The per-unknown kernels run a grid-stride loop over at most kPcgReduceBlocks workgroups: each ends in 9 atomics per sum.
+constexpr unsigned kPcgReduceBlocks = 1024;
+constexpr float kDiagEpsilon = 1e-8f;   // B/kernel_pcg.cu:44
+constexpr float kAPriorWeight = 10.f;   // B/kernel_pcg.cu:48
+__device__ __forceinline__ float prior_at(const PcgLayout& L, uint32_t u) {
+  return (u == L.a_index) ? (kAPriorWeight * kAPriorWeight) : 0.f;
+}
+__device__ __forceinline__ bool is_local(const PcgLayout& L, uint32_t u) { return u >= L.head_lo && u < L.head_hi; }
+
+// ---- exact dot products in the per-unknown kernels -----------------------------------------------------------------------------
+// A thread's terms over the local (surfel) unknowns go into a private column of limbs in workgroup memory (the limb index is
+// data dependent); terms of dense-head unknowns -- few -- go straight to the head's replicated slot with atomics.  At the end
+// the workgroup folds its columns and adds 9 limbs per sum to one of the 64 replicas.
+template <int kSets>
+struct BlockExact {
+  long long limbs[kSets][kExactLimbs][kPcgBlock];
+};
+template <int kSets>
+__device__ __forceinline__ void block_exact_clear(BlockExact<kSets>& b) {
+#pragma unroll
+  for (int set = 0; set < kSets; ++set)
+#pragma unroll
+    for (int j = 0; j < kExactLimbs; ++j) b.limbs[set][j][threadIdx.x] = 0;
+}
+template <int kSets>
+__device__ __forceinline__ void block_exact_add(BlockExact<kSets>& b, int set, float v, unsigned* invalid) {
+  exact_lds_add(&b.limbs[set][0][0], kPcgBlock, (int)threadIdx.x, v, invalid);
+}
+template <int kSets>
+__device__ __forceinline__ void block_exact_flush(BlockExact<kSets>& b, const PcgExact& ex, const int (&slots)[kSets]) {
+  __syncthreads();
+  const int replica = (int)(blockIdx.x & (kHotReplicas - 1));
+  const int part = threadIdx.x & 15;
+  for (int row = threadIdx.x >> 4; row < kSets * kExactLimbs; row += kPcgBlock >> 4) {   // 16 threads fold one row of 256 columns
+    const long long* line = &b.limbs[0][0][0] + (size_t)row * kPcgBlock;
+    long long sum = 0;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) sum += line[c * 16 + part];
+    for (int off = 8; off; off >>= 1) sum += __shfl_xor(sum, off);
+    if (part == 0 && sum != 0) limb_atomic_add(&hot_cell(ex, slots[row / kExactLimbs], replica)->limb[row % kExactLimbs], sum);
+  }
+}
+
 }  // namespace bahip
 
 BAHIP_FLAVOURED_BEGIN

@@ -58,6 +58,8 @@ def _load():
         L.dba_set_keyframe_sharding.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_set_pcg_gauge_keyframe.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_windowed_pcg.argtypes = [C.c_void_p, C.c_int]
+        L.dba_set_pcg_step_control.argtypes = [C.c_void_p, C.c_int] + [C.c_float] * 5 + [C.c_int]
+        L.dba_pcg_step_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dba_set_distributed_lifecycle.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_ba_iteration_counts.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -322,6 +324,29 @@ class DirectBA:
         owner, deletion by surfel chunk -- with the bits of the replicated run.  Raises under keyframe sharding."""
         if self.L.dba_set_distributed_lifecycle(self.h, int(bool(enabled))) != 0:
             raise RuntimeError("SetDistributedLifecycle: refused under keyframe sharding, which deals its lifecycle by keyframe already")
+
+    def SetPCGStepControl(self, control=None, **fields):
+        """Step control of the PCG scheme (default off): BundleAdjustment(use_pcg=True) takes Marquardt-damped steps and keeps one only
+        if ComputeCost's scalar falls strictly; a rejected step is undone bit for bit.  control: None / False = off, True = the defaults,
+        or a dict; fields: lambda_initial, lambda_up, lambda_down, lambda_min, lambda_max, max_trials.  Raises under keyframe sharding
+        and for values out of range."""
+        if control is None or control is False:
+            if self.L.dba_set_pcg_step_control(self.h, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0) != 0:
+                raise RuntimeError("SetPCGStepControl: could not be switched off")
+            return
+        v = dict(lambda_initial=1e-3, lambda_up=10.0, lambda_down=0.33, lambda_min=0.0, lambda_max=1e6, max_trials=6)
+        v.update(control if isinstance(control, dict) else {})
+        v.update(fields)
+        if self.L.dba_set_pcg_step_control(self.h, 1, v["lambda_initial"], v["lambda_up"], v["lambda_down"], v["lambda_min"],
+                                           v["lambda_max"], int(v["max_trials"])) != 0:
+            raise RuntimeError("SetPCGStepControl: refused under keyframe sharding, or a value is out of range")
+
+    def pcg_step_stats(self):
+        """(last_pcg_lambda, last_pcg_trials, last_pcg_rejected_steps): the damping factor the next outer iteration starts with, and the
+        trial steps / undone trial steps of the last BundleAdjustment call."""
+        lam, trials, rejected = C.c_float(), C.c_int(), C.c_int()
+        self.L.dba_pcg_step_stats(self.h, C.byref(lam), C.byref(trials), C.byref(rejected))
+        return lam.value, trials.value, rejected.value
 
     def SetWindowedPCG(self, enabled):
         """Windowed PCG scheme (default off): BundleAdjustment(use_pcg=True) honours a fixed active keyframe window and skips deleted

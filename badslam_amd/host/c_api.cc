@@ -258,6 +258,20 @@ int dba_set_pcg_gauge_keyframe(dba_handle* h, int id) {
   return 0;
 }
 int dba_set_windowed_pcg(dba_handle* h, int enabled) { return h->ba->SetWindowedPCG(enabled != 0) ? 0 : 1; }
+int dba_set_pcg_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_down, float lambda_min,
+                             float lambda_max, int max_trials) {
+  if (!enabled) return h->ba->SetPCGStepControl(nullptr) ? 0 : 1;
+  vis::DirectBA::PCGStepControl control;
+  control.lambda_initial = lambda_initial; control.lambda_up = lambda_up; control.lambda_down = lambda_down;
+  control.lambda_min = lambda_min; control.lambda_max = lambda_max; control.max_trials = max_trials;
+  return h->ba->SetPCGStepControl(&control) ? 0 : 1;
+}
+int dba_pcg_step_stats(dba_handle* h, float* lambda, int* trials, int* rejected_steps) {
+  if (lambda) *lambda = h->ba->last_pcg_lambda();
+  if (trials) *trials = h->ba->last_pcg_trials();
+  if (rejected_steps) *rejected_steps = h->ba->last_pcg_rejected_steps();
+  return 0;
+}
 int dba_set_distributed_lifecycle(dba_handle* h, int enabled) { return h->ba->SetDistributedLifecycle(enabled != 0) ? 0 : 1; }
 int dba_last_stats(dba_handle* h, int* pose_rounds, int* pose_steps, int* pcg_inner_steps) {
   if (pose_rounds) *pose_rounds = h->ba->last_pose_rounds();

@@ -240,6 +240,26 @@ bool DirectBA::SetWindowedPCG(bool enabled) {
   return true;
 }
 
+bool DirectBA::SetPCGStepControl(const PCGStepControl* control) {
+  if (!control) {
+    pcg_step_control_on_ = false;
+    return true;
+  }
+  if (keyframe_shard_world_ > 1) {
+    LOG(ERROR) << "SetPCGStepControl: step control of the PCG scheme is not available under keyframe sharding";
+    return false;
+  }
+  if (!(control->max_trials >= 1 && control->lambda_up >= 1.f && control->lambda_down > 0.f && control->lambda_down <= 1.f &&
+        control->lambda_min >= 0.f && control->lambda_min <= control->lambda_max && control->lambda_initial >= 0.f)) {
+    LOG(ERROR) << "SetPCGStepControl: needs max_trials >= 1, lambda_up >= 1, 0 < lambda_down <= 1, 0 <= lambda_min <= lambda_max, lambda_initial >= 0";
+    return false;
+  }
+  pcg_step_control_ = *control;
+  pcg_step_control_on_ = true;
+  pcg_lambda_ = control->lambda_initial;
+  return true;
+}
+
 bool DirectBA::SetDistributedLifecycle(bool enabled) {
   if (enabled && keyframe_shard_world_ > 1) {
     LOG(ERROR) << "SetDistributedLifecycle: keyframe sharding deals its lifecycle by keyframe already";
@@ -256,6 +276,7 @@ bool DirectBA::SetDistributedLifecycle(bool enabled) {
 void DirectBA::SetKeyframeSharding(int rank, int world) {
   CHECK(!distributed_lifecycle_ || world == 1) << "keyframe sharding deals its own lifecycle: SetDistributedLifecycle(false) first";
   CHECK(!windowed_pcg_ || world == 1) << "the windowed PCG scheme is not available under keyframe sharding: SetWindowedPCG(false) first";
+  CHECK(!pcg_step_control_on_ || world == 1) << "step control of the PCG scheme is not available under keyframe sharding: SetPCGStepControl(nullptr) first";
   CHECK_EQ(shard_world_, 1) << "surfel and keyframe sharding exclude each other";
   BAHIP_CHECKED_CALL(bahip_context_set_keyframe_sharding(ctx_, rank, world));
   keyframe_shard_world_ = world;
@@ -480,7 +501,7 @@ void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsi
     LOG(WARNING) << "optimize_color_intrinsics set to true, but use_descriptor_residuals_ set to false. Color intrinsics will not be optimized.";
     optimize_color_intrinsics = false;
   }
-  last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = 0;
+  last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = last_pcg_trials_ = last_pcg_rejected_steps_ = 0;
   if (keyframe_shard_world_ > 1)
     CHECK(batched_creation_ || (!do_surfel_updates && !increase_ba_iteration_count))
         << "keyframe sharding runs the surfel lifecycle through the batched calls only (SetBatchedCreation(true))";
@@ -911,6 +932,8 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
     }
   };
 
+  bahip_cost carried_cost{};   // step control: the cost the previous outer iteration of this call left
+  bool have_carried_cost = false;
   for (int iteration = 0; iteration < max_iterations; ++iteration) {
     if (progress_function && !progress_function(iteration)) break;
     if (num_iterations_done) ++*num_iterations_done;
@@ -955,7 +978,8 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
     } else {
       BAHIP_CHECKED_CALL(bahip_memset_async(stream, active_surfels_->ToCUDA().address(), 1, surfels_size_));
     }
-    if (optimize_geometry) {
+    const bool controlled = pcg_step_control_on_;
+    if (optimize_geometry && !controlled) {   // (under step control the normals update runs inside the trial and is undone with it)
       const bahip_surfels s = SurfelsStruct();
       BAHIP_CHECKED_CALL(bahip_update_surfel_normals(ctx_, &s));
     }
@@ -976,10 +1000,31 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
     float out_a = depth_params_.a;
     int inner_steps = 0, num_converged = 0;
     const bahip_surfels s = SurfelsStruct();
-    if (use_window) BAHIP_CHECKED_CALL(bahip_pcg_iteration_windowed(ctx_, &opt, &s, &out_color, &out_depth, &out_a, &inner_steps, &num_converged));
-    else BAHIP_CHECKED_CALL(bahip_pcg_iteration(ctx_, &opt, &s, &out_color, &out_depth, &out_a, &inner_steps, &num_converged));
+    bool step_accepted = true;
+    if (controlled) {
+      const bahip_pcg_step_control control{pcg_step_control_.lambda_initial, pcg_step_control_.lambda_up, pcg_step_control_.lambda_down,
+                                           pcg_step_control_.lambda_min, pcg_step_control_.lambda_max, pcg_step_control_.max_trials};
+      bahip_cost cost_before = carried_cost, cost_after;
+      int trials = 0, accepted = 0;
+      // (the previous outer iteration's cost_after is this one's cost_before unless something changed the state in between: surfel
+      // creation and merging do)
+      BAHIP_CHECKED_CALL(bahip_pcg_iteration_controlled(ctx_, &opt, &control, use_window ? 1 : 0, optimize_geometry ? 1 : 0, &s, &pcg_lambda_,
+                                                        &out_color, &out_depth, &out_a, &inner_steps, &num_converged,
+                                                        (have_carried_cost && !do_surfel_updates) ? 1 : 0, &cost_before, &cost_after, &trials,
+                                                        &accepted));
+      carried_cost = cost_after;
+      have_carried_cost = true;
+      last_pcg_trials_ += trials;
+      last_pcg_rejected_steps_ += trials - accepted;
+      step_accepted = accepted != 0;
+    } else if (use_window) {
+      BAHIP_CHECKED_CALL(bahip_pcg_iteration_windowed(ctx_, &opt, &s, &out_color, &out_depth, &out_a, &inner_steps, &num_converged));
+    } else {
+      BAHIP_CHECKED_CALL(bahip_pcg_iteration(ctx_, &opt, &s, &out_color, &out_depth, &out_a, &inner_steps, &num_converged));
+    }
     last_pcg_inner_steps_ += inner_steps;
     num_converged += (int)keyframes_.size() - (int)bound_ids_.size();   // deleted keyframes count as converged
+    if (!step_accepted) num_converged = (int)keyframes_.size();         // no step lowers the cost: converged for the stopping rule
     if (optimize_poses) {
       const int K = (int)bound_ids_.size();
       vector<float> poses(7 * (size_t)K);

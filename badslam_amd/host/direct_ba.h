@@ -152,6 +152,21 @@ class DirectBA {
   // false) under keyframe sharding and after SetPCGSumClasses(c > 1).
   bool SetWindowedPCG(bool enabled);
   bool windowed_pcg() const { return windowed_pcg_; }
+  // Step control of the PCG scheme (ours; default off = NULL: every update is applied, as the reference does).  On: every outer
+  // iteration of BundleAdjustment(use_pcg) is bahip_pcg_iteration_controlled -- Marquardt-damped steps (lambda * diag of the
+  // Gauss-Newton matrix) that are kept only if ComputeCost's scalar falls strictly, and undone bit for bit otherwise.  lambda starts
+  // at lambda_initial when the control is set and is carried across outer iterations and across calls.  An outer iteration without
+  // an accepted trial ends the call as converged.  The normals update of each outer iteration runs inside the trial.  Refused
+  // (returns false) under keyframe sharding.  The defaults: DESIGN.md section 3.
+  struct PCGStepControl {
+    float lambda_initial = 1e-3f, lambda_up = 10.f, lambda_down = 0.33f, lambda_min = 0.f, lambda_max = 1e6f;
+    int max_trials = 6;
+  };
+  bool SetPCGStepControl(const PCGStepControl* control);
+  bool pcg_step_control() const { return pcg_step_control_on_; }
+  float last_pcg_lambda() const { return pcg_lambda_; }                        // the factor the next outer iteration will start with
+  int last_pcg_trials() const { return last_pcg_trials_; }                     // trial steps of the last BundleAdjustment() call
+  int last_pcg_rejected_steps() const { return last_pcg_rejected_steps_; }     // ... and those of them that were undone
   // Multi-GPU surfel sharding: sums of the per-keyframe normal equations go through this hook
   // (see include/badslam_hip.h, bahip_allreduce_fn).
   void SetAllReduce(bahip_allreduce_fn fn, void* user) { BAHIP_CHECKED_CALL(bahip_context_set_allreduce(ctx_, fn, user)); }
@@ -273,6 +288,10 @@ class DirectBA {
   vector<int> id_to_bound_;      // keyframe id -> bound list index (-1 for deleted keyframes)
   int pcg_gauge_keyframe_ = -1;
   bool windowed_pcg_ = false;
+  bool pcg_step_control_on_ = false;
+  PCGStepControl pcg_step_control_;
+  float pcg_lambda_ = 0.f;
+  int last_pcg_trials_ = 0, last_pcg_rejected_steps_ = 0;
   bool distributed_lifecycle_ = false;   // SetDistributedLifecycle
   int pcg_sum_classes_ = 1;        // (SetPCGSumClasses: the windowed scheme needs 1)
   int shard_rank_ = 0, shard_world_ = 1, whole_cloud_depth_ = 0;

@@ -427,6 +427,47 @@ class Scene:
             self.set_intrinsics()
         return steps.value, conv.value
 
+    def set_pcg_damping(self, lam):
+        """The damping factor of the PCG system (bahip_context_set_pcg_damping); 0 = off."""
+        capi.check(self.lib.bahip_context_set_pcg_damping(self.ctx.handle, float(lam)))
+
+    def pcg_iteration_controlled(self, lam, control, optimize_poses=True, optimize_geometry=True, optimize_depth_intrinsics=False,
+                                 optimize_color_intrinsics=False, use_depth=True, use_desc=True, max_inner_iterations=30,
+                                 gauge_keyframe=0, windowed=False, update_normals=False, cost_before=None):
+        """One controlled outer iteration (bahip_pcg_iteration_controlled) with damping `lam`; `control` = (lambda_up, lambda_down,
+        lambda_min, lambda_max, max_trials); cost_before: a capi.Cost of the current state, or None to have it evaluated.  Adopts the
+        poses / intrinsics the call leaves.  Returns a dict: lam, accepted, trials, steps, converged, cost_before, cost_after (dicts
+        like evaluate_cost's) and cost_after_struct (to pass on as the next call's cost_before)."""
+        opt = capi.PCGOptions(int(optimize_poses), int(optimize_geometry), int(optimize_depth_intrinsics),
+                              int(optimize_color_intrinsics), int(use_depth), int(use_desc), int(max_inner_iterations),
+                              int(gauge_keyframe))
+        up, down, lo, hi, trials = control
+        ctl = capi.PCGStepControl(float(lam), float(up), float(down), float(lo), float(hi), int(trials))
+        cc, dc, a = capi.Camera(), capi.Camera(), C.c_float()
+        steps, conv, ran, accepted = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        lam_io = C.c_float(float(lam))
+        before = capi.Cost() if cost_before is None else cost_before
+        after = capi.Cost()
+        s = self.surfels_struct()
+        capi.check(self.lib.bahip_pcg_iteration_controlled(self.ctx.handle, C.byref(opt), C.byref(ctl), int(windowed), int(update_normals),
+                                                           C.byref(s), C.byref(lam_io), C.byref(cc), C.byref(dc), C.byref(a),
+                                                           C.byref(steps), C.byref(conv), int(cost_before is not None),
+                                                           C.byref(before), C.byref(after), C.byref(ran), C.byref(accepted)))
+        K = len(self.keyframes)
+        if optimize_poses and K:
+            poses = (C.c_float * (7 * K))()
+            capi.check(self.lib.bahip_get_keyframe_poses(self.ctx.handle, poses, K))
+            arr = np.array(list(poses), dtype=np.float32).reshape(K, 7)
+            for k, kf in enumerate(self.keyframes):
+                kf["pose"] = arr[k].copy()
+        if optimize_color_intrinsics:
+            self.color_cam = cc
+        if optimize_depth_intrinsics:
+            self.depth_cam = dc
+            self.dp.a = a.value
+        return {"lam": float(lam_io.value), "accepted": bool(accepted.value), "trials": ran.value, "steps": steps.value,
+                "converged": conv.value, "cost_before": cost_dict(before), "cost_after": cost_dict(after), "cost_after_struct": after}
+
     def read_pcg_vector(self, which, count, offset=0):
         out = np.zeros(count, np.float32)
         capi.check(self.lib.bahip_debug_read_pcg_vector(self.ctx.handle, int(which), int(offset), int(count),

@@ -92,6 +92,13 @@ int dba_set_pcg_gauge_keyframe(dba_handle* h, int keyframe_id);
 /* DirectBA::SetWindowedPCG (ours, default off): BundleAdjustment(use_pcg) honours a fixed active keyframe window and skips deleted
  * keyframes; returns 1 (refused) under keyframe sharding and with more than one PCG sum class */
 int dba_set_windowed_pcg(dba_handle* h, int enabled);
+/* DirectBA::SetPCGStepControl (ours, default off): BundleAdjustment(use_pcg) takes damped steps that are kept only if the objective
+ * falls (bahip_pcg_iteration_controlled; the fields of bahip_pcg_step_control).  enabled = 0: off.  Returns 1 (refused) under keyframe
+ * sharding and for values out of range.  dba_pcg_step_stats: the damping factor the next outer iteration starts with, and the trial
+ * steps / undone trial steps of the last BundleAdjustment call. */
+int dba_set_pcg_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_down, float lambda_min,
+                             float lambda_max, int max_trials);
+int dba_pcg_step_stats(dba_handle* h, float* lambda, int* trials, int* rejected_steps);
 /* DirectBA::SetSurfelSharding: this object holds rank `rank`'s chunk-cyclic shard of one surfel cloud (bahip_gather_surfel_shards) */
 int dba_set_surfel_sharding(dba_handle* h, int rank, int world, uint32_t chunk);
 /* DirectBA::SetDistributedLifecycle (ours, default off): under surfel sharding the lifecycle's sweeps are dealt over the ranks

@@ -604,6 +604,48 @@ int bahip_evaluate_frame_cost(bahip_context* ctx, int use_depth, int use_desc, c
  * per launch 1 .. 256, tile_order 0 = buffer order, 1 = the sweeps' heavy-first order when there is one; 0 / -1 = the default. */
 int bahip_debug_set_cost_shape(int waves, int workgroups, int slice, int tile_order);
 
+/* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
+ * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
+ * e = 1e-8 + prior(u) as before and t = lambda * M[u] (one binary32 product), the preconditioner divides by ((M[u] + 1e-8) + prior(u))
+ * + t and the matrix-free product adds (e + t) * p on the diagonal.  It holds for bahip_pcg_iteration, bahip_pcg_iteration_windowed
+ * and the stage entry points (bahip_pcg_init2, bahip_pcg_step2; bahip_pcg_step3 needs none: its p does not depend on it), which stay
+ * one system.  lambda = 0 launches the undamped kernels: every bit as before, in both arithmetic flavours.  Rows with M = 0 (gauge,
+ * fixed poses, inactive surfels) stay untouched. */
+int bahip_context_set_pcg_damping(bahip_context* ctx, float lambda);
+float bahip_context_get_pcg_damping(bahip_context* ctx);
+typedef struct bahip_pcg_step_control {
+  float lambda_initial;           /* first damping factor (for the caller's *lambda_inout; not read here) */
+  float lambda_up, lambda_down;   /* factor after a rejected / an accepted step (up >= 1, 0 < down <= 1) */
+  float lambda_min, lambda_max;   /* 0 <= min <= max, finite */
+  int max_trials;                 /* trial steps per outer iteration, >= 1 */
+} bahip_pcg_step_control;
+/* One outer iteration that does not raise the objective:
+ *  1. *cost_before = bahip_evaluate_cost of the current state -- or, with have_cost_before != 0, taken as the caller gives it (the
+ *     previous call's *cost_after, if nothing touched the state in between);
+ *  2. everything an iteration may write is saved (surfel rows x, y, z, the normal row, the descriptor rows with descriptor residuals
+ *     -- under a window the 64-surfel tiles with an active surfel only --, the keyframe table, the cfactor plane, the context's
+ *     intrinsics and a), then one trial: bahip_update_surfel_normals when update_normals != 0 (the call the reference's driver makes
+ *     ahead of each outer iteration, here inside the trial so that it is undone with it), bahip_pcg_iteration (windowed != 0:
+ *     bahip_pcg_iteration_windowed) with damping *lambda_inout, the new intrinsics put into the context (bahip_set_intrinsics), and
+ *     *cost_after = bahip_evaluate_cost;
+ *  3. with f(c) = (c.depth + c.descriptor_1) + c.descriptor_2 in binary64: the trial is accepted iff f(*cost_after) is finite and
+ *     f(*cost_after) < f(*cost_before).  Then lambda <- max(lambda * lambda_down, lambda_min) (binary32) and the call returns;
+ *  4. else the saved words are written back -- every bit as before the call --, lambda <- min(lambda * lambda_up, lambda_max), and
+ *     the next trial runs, at most max_trials.  Without an accepted trial: *accepted_out = 0, *cost_after = *cost_before, the
+ *     out_* intrinsics are the context's, and *num_converged_out is what the last trial reported.
+ * *trials_out: trials run; *inner_steps_out: inner steps of all of them.  Unlike bahip_pcg_iteration, an accepted step leaves the
+ * new intrinsics in the context.  The context's own damping factor is not changed.
+ * The objective counts associated pairs only, so a step can lower it by losing associations: compare depth_residuals and
+ * descriptor_pairs of the two costs, which is what they are returned for.  No correction is made for it.
+ * Sharding: the decision is taken from the total of bahip_evaluate_cost, which has the same bits on every rank, so every rank takes
+ * the same branch; surfel sharding gives the accept / reject sequence, lambda and bits of one GPU.  Keyframe sharding: refused
+ * (error text, context usable), windowed or not.  An error inside a trial restores the state first.  Synchronises. */
+int bahip_pcg_iteration_controlled(bahip_context* ctx, const bahip_pcg_options* opt, const bahip_pcg_step_control* control, int windowed,
+                                   int update_normals, const bahip_surfels* surfels, float* lambda_inout, bahip_camera* out_color_camera,
+                                   bahip_camera* out_depth_camera, float* out_a, int* inner_steps_out, int* num_converged_out,
+                                   int have_cost_before, bahip_cost* cost_before, bahip_cost* cost_after, int* trials_out,
+                                   int* accepted_out);
+
 /* ---- test hook --------------------------------------------------------------------------------------
  * Per-pair evaluation with the production device functions (association, the three raw residuals,
  * weights, pose Jacobians, image gradients) for `count` surfel indices against one frame; 40 floats
