@@ -79,6 +79,11 @@ class Cost(C.Structure):           # bahip_cost: the value of the BA objective (
                 ("depth_residuals", C.c_uint64), ("descriptor_pairs", C.c_uint64)]
 
 
+class PoseStepControl(C.Structure):   # bahip_pose_step_control: step control of the pose phase (bahip_estimate_keyframe_poses_controlled)
+    _fields_ = [("lambda_up", C.c_float), ("lambda_down", C.c_float), ("lambda_min", C.c_float), ("lambda_max", C.c_float),
+                ("max_trials", C.c_int)]
+
+
 class PCGStepControl(C.Structure):   # bahip_pcg_step_control: step control of the PCG scheme (bahip_pcg_iteration_controlled)
     _fields_ = [("lambda_initial", C.c_float), ("lambda_up", C.c_float), ("lambda_down", C.c_float),
                 ("lambda_min", C.c_float), ("lambda_max", C.c_float), ("max_trials", C.c_int)]
@@ -200,6 +205,11 @@ SIGNATURES = {
     "bahip_pcg_step3": (C.c_int, [C.c_void_p, C.POINTER(PCGLayout), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bahip_update_surfels_from_pcg_delta": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.c_int, C.c_uint32, C.c_void_p]),
     "bahip_update_cfactors_from_pcg_delta": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bahip_estimate_keyframe_poses_controlled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(PoseStepControl), C.POINTER(Surfels), C.c_int,
+                                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(Cost),
+                                                           C.POINTER(Cost), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bahip_debug_pose_step_damped": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float)]),
     "bahip_evaluate_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Surfels), C.POINTER(Cost), C.POINTER(Cost)]),
     "bahip_evaluate_frame_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                             C.POINTER(Cost)]),

@@ -450,4 +450,45 @@ void launch_cost(hipStream_t stream, bool use_depth, bool use_desc, const Intrin
 // zeroed words of scratch
 void launch_cost_resolve(hipStream_t stream, const long long* rows, int num, long long* total, bahip_cost* out);
 
+// kernels_pose_trial.hip: the pose phase under step control.  The record the controlled solve keeps per work item: the limbs of the
+// normal equations and the cost at the accepted pose (PoseWork::T), the cost the phase began with, the candidate the next sweep
+// evaluates (its frame_T_global is PoseWork::F), the damping factor and the counters.
+struct PoseTrialRecord {
+  HbFixed Hb[kHbStride];
+  bahip_cost cost, cost_before;
+  float T_candidate[7];
+  float lambda;
+  int32_t candidate_converged;     // the step to the candidate passed the convergence test on x
+  int32_t consecutive_rejected;
+  int32_t trials, rejected;        // candidates evaluated / rejected so far
+  int32_t evaluated, pad_;         // round 0 has run for this item: it is a work item of the phase (its keyframe was not kInactive)
+};
+static_assert(sizeof(PoseTrialRecord) % 8 == 0, "the records sit in a buffer of 64-bit words");
+// control words of a controlled phase: [0], [1] = entries of the two lists of items still iterating (round r appends to list r & 1, the
+// sweep of round r + 1 reads it), [kPoseTrialInvalid] = the sticky flag of the plain phase's kPoseCounterInvalid
+constexpr int kPoseTrialInvalid = 2, kPoseTrialWords = 4;
+namespace exact {
+int launch_pose_trial_sweep(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, const void* work,
+                            int num_work, const int* listed, int num_items, const SurfelsView& s, HbFixed* Hb, long long* cost_rows,
+                            void* tile_bounds, bool stored_bounds, const uint32_t* sched);
+void set_pose_trial_shape(int waves, int parts_shift);
+}
+namespace fast {
+int launch_pose_trial_sweep(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, const void* work,
+                            int num_work, const int* listed, int num_items, const SurfelsView& s, HbFixed* Hb, long long* cost_rows,
+                            void* tile_bounds, bool stored_bounds, const uint32_t* sched);
+void set_pose_trial_shape(int waves, int parts_shift);
+}
+// The fused sweep: Hb[w] += the normal equations and cost_rows[w] += the cost row (kCostWords) of every item's pose PoseWork::F, for the
+// items listed[0 .. num_items) (NULL: the work items 0 .. num_items) that are not skipped.  stored_bounds as launch_pose_accumulate.
+// Returns a hipError_t (the opt-in for a large LDS table can be refused).
+int launch_pose_trial_sweep(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, const void* work,
+                            int num_work, const int* listed, int num_items, const SurfelsView& s, HbFixed* Hb, long long* cost_rows,
+                            void* tile_bounds, bool stored_bounds, const uint32_t* sched);
+void launch_pose_trial_solve(hipStream_t stream, void* work, int num_work, PoseTrialRecord* records, HbFixed* Hb, long long* cost_rows, KfEntry* frames,
+                             const bahip_pose_step_control& control, int update_activation, int round, const float* lambda_in, int* ctl,
+                             int* list_next);
+void set_pose_trial_shape(int waves, int parts_shift);   // test hook: wavefronts per workgroup (0: 16), 2^shift wavefronts share a tile's items (-1: from the grid size)
+void launch_pose_step_damped_debug(hipStream_t stream, const float* in, float* out);
+
 }  // namespace bahip

@@ -286,7 +286,7 @@ void bahip_context_destroy(bahip_context* ctx) {
   hipFree(ctx->dev_covis); hipFree(ctx->dev_covis_T); hipFree(ctx->dev_covis_csr); hipFree(ctx->dev_tile_bounds); hipFree(ctx->dev_lifecycle_bounds); hipFree(ctx->dev_lifecycle_frames); hipFree(ctx->dev_lifecycle_cursors); hipFree(ctx->dev_lifecycle_lists); hipFree(ctx->dev_window);
   hipFree(ctx->intr_bin_cursors); hipFree(ctx->intr_bin_records); hipHostFree(ctx->intr_bin_counts_host);
   if (ctx->intr_aux_stream) { hipStreamDestroy(ctx->intr_aux_stream); for (hipEvent_t e : ctx->intr_events) if (e) hipEventDestroy(e); }
-  hipFree(ctx->intr_scratch); hipFree(ctx->pcg_buf); hipFree(ctx->pcg_exact); hipFree(ctx->pcg_stage_ctl); hipFree(ctx->kf_partials); hipFree(ctx->pcg_window); hipFree(ctx->pcg_trial); hipFree(ctx->dev_gather_table);
+  hipFree(ctx->intr_scratch); hipFree(ctx->pcg_buf); hipFree(ctx->pcg_exact); hipFree(ctx->pcg_stage_ctl); hipFree(ctx->kf_partials); hipFree(ctx->pcg_window); hipFree(ctx->pcg_trial); hipFree(ctx->pose_trial); hipFree(ctx->dev_gather_table);
   for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) hipFree(ctx->merge_planes[b]);
   hipFree(ctx->dev_tile_cost); hipFree(ctx->dev_tile_order);
   hipFree(ctx->dev_loop_ctl);

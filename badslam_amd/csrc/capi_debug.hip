@@ -56,6 +56,7 @@ int bahip_debug_set_pose_lds_shape(int waves, int parts_shift) {
   if (waves < 0 || waves > 16 || parts_shift < -1 || parts_shift > 3) return fail("bahip_debug_set_pose_lds_shape: waves 0 .. 16, parts_shift -1 .. 3", __FILE__, __LINE__, hipSuccess);
   set_pose_lds_waves(waves);
   set_pose_lds_parts_shift(parts_shift);
+  set_pose_trial_shape(waves, parts_shift);   // the fused sweep of the controlled phase has the persistent form only
   return 0;
 }
 int bahip_debug_set_intrinsics_reduce_form(int form) {
@@ -197,6 +198,22 @@ int bahip_debug_pose_step(bahip_context* ctx, const float* H21_b6, const float* 
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   hipFree(d_in); hipFree(d_out);
   if (e != hipSuccess) return fail("bahip_debug_pose_step", __FILE__, __LINE__, e);
+  return 0;
+}
+
+int bahip_debug_pose_step_damped(bahip_context* ctx, const float* H21_b6, const float* global_T_frame, float lambda, float* out_25) {
+  DevMem d_in, d_out;
+  HIP_TRY(hipMalloc(&d_in.p, 35 * sizeof(float)));
+  HIP_TRY(hipMalloc(&d_out.p, 25 * sizeof(float)));
+  float in[35];
+  memcpy(in, H21_b6, 27 * sizeof(float));
+  memcpy(in + 27, global_T_frame, 7 * sizeof(float));
+  in[34] = lambda;
+  HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(in), hipMemcpyHostToDevice, ctx->stream));
+  launch_pose_step_damped_debug(ctx->stream, d_in.as<float>(), d_out.as<float>());
+  CHECK_LAUNCH();
+  HIP_TRY(hipMemcpyAsync(out_25, d_out.p, 25 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 

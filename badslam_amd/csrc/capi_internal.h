@@ -7,6 +7,8 @@
 //   capi_solvers.hip    the intrinsics step and the PCG scheme (whole iteration and stage by stage)
 //   capi_debug.hip      test hooks and experiment switches
 //   capi_cost.hip       the value of the BA objective (bahip_evaluate_cost, bahip_evaluate_frame_cost)
+//   capi_pcg_trial.hip  step control of the PCG scheme
+//   capi_pose_trial.hip step control of the pose phase of the alternating scheme
 #pragma once
 
 #include <dlfcn.h>
@@ -207,6 +209,8 @@ struct bahip_context {
   float pcg_damping = 0.f;         // lambda of the damped PCG system (bahip_context_set_pcg_damping; kernels_pcg_trial.hip)
   uint32_t* pcg_trial = nullptr;   // bahip_pcg_iteration_controlled: [tile count | tile list] followed by the snapshot
   size_t pcg_trial_capacity = 0;   // words
+  long long* pose_trial = nullptr; // bahip_estimate_keyframe_poses_controlled: [Hb | cost rows] (what the ranks exchange), records, lambdas, lists, control words
+  size_t pose_trial_capacity = 0;  // int64 words
   int world = 0;                   // ranks of the RCCL communicator (0 = none)
   int kf_rank = 0, kf_world = 1;   // keyframe sharding (bahip_context_set_keyframe_sharding): keyframe k lives on rank k % kf_world (1, 2, 4 or 8)
   int arithmetic = 0;              // BAHIP_ARITHMETIC_EXACT / _FAST: flavour of the sweeps (bahip_context_set_arithmetic), mirrored in in.fast_math

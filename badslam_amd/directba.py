@@ -60,6 +60,8 @@ def _load():
         L.dba_set_windowed_pcg.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_pcg_step_control.argtypes = [C.c_void_p, C.c_int] + [C.c_float] * 5 + [C.c_int]
         L.dba_pcg_step_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.dba_set_pose_step_control.argtypes = [C.c_void_p, C.c_int] + [C.c_float] * 5 + [C.c_int]
+        L.dba_get_pose_step_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float)]
         L.dba_set_distributed_lifecycle.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_ba_iteration_counts.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -340,6 +342,29 @@ class DirectBA:
         if self.L.dba_set_pcg_step_control(self.h, 1, v["lambda_initial"], v["lambda_up"], v["lambda_down"], v["lambda_min"],
                                            v["lambda_max"], int(v["max_trials"])) != 0:
             raise RuntimeError("SetPCGStepControl: refused under keyframe sharding, or a value is out of range")
+
+    def SetPoseStepControl(self, control=None, **fields):
+        """Step control of the pose phase of the alternating scheme (default off): per keyframe, a Marquardt-damped Gauss-Newton step is
+        kept only if that keyframe's cost falls strictly.  control: None / False = off, True = the defaults, or a dict; fields:
+        lambda_initial, lambda_up, lambda_down, lambda_min, lambda_max, max_trials.  Raises under keyframe sharding and for values out of
+        range."""
+        if control is None or control is False:
+            if self.L.dba_set_pose_step_control(self.h, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0) != 0:
+                raise RuntimeError("SetPoseStepControl: could not be switched off")
+            return
+        v = dict(lambda_initial=1e-3, lambda_up=10.0, lambda_down=0.33, lambda_min=0.0, lambda_max=1e6, max_trials=4)
+        v.update(control if isinstance(control, dict) else {})
+        v.update(fields)
+        if self.L.dba_set_pose_step_control(self.h, 1, v["lambda_initial"], v["lambda_up"], v["lambda_down"], v["lambda_min"],
+                                            v["lambda_max"], int(v["max_trials"])) != 0:
+            raise RuntimeError("SetPoseStepControl: refused under keyframe sharding, or a value is out of range")
+
+    def pose_step_stats(self, keyframe_id=0):
+        """(last_pose_trials, last_pose_rejected_steps, lambda of keyframe_id): candidates evaluated / rejected by the pose phases of the
+        last BundleAdjustment call, and the damping factor that keyframe's next pose phase starts with."""
+        trials, rejected, lam = C.c_int(), C.c_int(), C.c_float()
+        self.L.dba_get_pose_step_stats(self.h, C.byref(trials), C.byref(rejected), int(keyframe_id), C.byref(lam))
+        return trials.value, rejected.value, lam.value
 
     def pcg_step_stats(self):
         """(last_pcg_lambda, last_pcg_trials, last_pcg_rejected_steps): the damping factor the next outer iteration starts with, and the

@@ -272,6 +272,20 @@ int dba_pcg_step_stats(dba_handle* h, float* lambda, int* trials, int* rejected_
   if (rejected_steps) *rejected_steps = h->ba->last_pcg_rejected_steps();
   return 0;
 }
+int dba_set_pose_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_down, float lambda_min,
+                              float lambda_max, int max_trials) {
+  if (!enabled) return h->ba->SetPoseStepControl(nullptr) ? 0 : 1;
+  vis::DirectBA::PoseStepControl control;
+  control.lambda_initial = lambda_initial; control.lambda_up = lambda_up; control.lambda_down = lambda_down;
+  control.lambda_min = lambda_min; control.lambda_max = lambda_max; control.max_trials = max_trials;
+  return h->ba->SetPoseStepControl(&control) ? 0 : 1;
+}
+int dba_get_pose_step_stats(dba_handle* h, int* trials, int* rejected_steps, int keyframe_id, float* lambda) {
+  if (trials) *trials = h->ba->last_pose_trials();
+  if (rejected_steps) *rejected_steps = h->ba->last_pose_rejected_steps();
+  if (lambda) *lambda = h->ba->pose_lambda(keyframe_id);
+  return 0;
+}
 int dba_set_distributed_lifecycle(dba_handle* h, int enabled) { return h->ba->SetDistributedLifecycle(enabled != 0) ? 0 : 1; }
 int dba_last_stats(dba_handle* h, int* pose_rounds, int* pose_steps, int* pcg_inner_steps) {
   if (pose_rounds) *pose_rounds = h->ba->last_pose_rounds();

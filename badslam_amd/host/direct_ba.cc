@@ -260,6 +260,28 @@ bool DirectBA::SetPCGStepControl(const PCGStepControl* control) {
   return true;
 }
 
+bool DirectBA::SetPoseStepControl(const PoseStepControl* control) {
+  if (!control) {
+    pose_step_control_on_ = false;
+    return true;
+  }
+  if (keyframe_shard_world_ > 1) {
+    LOG(ERROR) << "SetPoseStepControl: step control of the pose phase is not available under keyframe sharding";
+    return false;
+  }
+  // (the checks of bahip_estimate_keyframe_poses_controlled, which would otherwise refuse in the middle of BundleAdjustment)
+  if (!(control->max_trials >= 1 && std::isfinite(control->lambda_up) && control->lambda_up >= 1.f && control->lambda_down > 0.f &&
+        control->lambda_down <= 1.f && control->lambda_min >= 0.f && std::isfinite(control->lambda_max) &&
+        control->lambda_min <= control->lambda_max && std::isfinite(control->lambda_initial) && control->lambda_initial >= 0.f)) {
+    LOG(ERROR) << "SetPoseStepControl: needs max_trials >= 1, finite lambda_up >= 1, 0 < lambda_down <= 1, 0 <= lambda_min <= finite lambda_max, "
+                  "finite lambda_initial >= 0";
+    return false;
+  }
+  pose_step_control_ = *control;
+  pose_step_control_on_ = true;
+  return true;
+}
+
 bool DirectBA::SetDistributedLifecycle(bool enabled) {
   if (enabled && keyframe_shard_world_ > 1) {
     LOG(ERROR) << "SetDistributedLifecycle: keyframe sharding deals its lifecycle by keyframe already";
@@ -277,6 +299,7 @@ void DirectBA::SetKeyframeSharding(int rank, int world) {
   CHECK(!distributed_lifecycle_ || world == 1) << "keyframe sharding deals its own lifecycle: SetDistributedLifecycle(false) first";
   CHECK(!windowed_pcg_ || world == 1) << "the windowed PCG scheme is not available under keyframe sharding: SetWindowedPCG(false) first";
   CHECK(!pcg_step_control_on_ || world == 1) << "step control of the PCG scheme is not available under keyframe sharding: SetPCGStepControl(nullptr) first";
+  CHECK(!pose_step_control_on_ || world == 1) << "step control of the pose phase is not available under keyframe sharding: SetPoseStepControl(nullptr) first";
   CHECK_EQ(shard_world_, 1) << "surfel and keyframe sharding exclude each other";
   BAHIP_CHECKED_CALL(bahip_context_set_keyframe_sharding(ctx_, rank, world));
   keyframe_shard_world_ = world;
@@ -501,7 +524,7 @@ void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsi
     LOG(WARNING) << "optimize_color_intrinsics set to true, but use_descriptor_residuals_ set to false. Color intrinsics will not be optimized.";
     optimize_color_intrinsics = false;
   }
-  last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = last_pcg_trials_ = last_pcg_rejected_steps_ = 0;
+  last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = last_pcg_trials_ = last_pcg_rejected_steps_ = last_pose_trials_ = last_pose_rejected_steps_ = 0;
   if (keyframe_shard_world_ > 1)
     CHECK(batched_creation_ || (!do_surfel_updates && !increase_ba_iteration_count))
         << "keyframe sharding runs the surfel lifecycle through the batched calls only (SetBatchedCreation(true))";
@@ -626,7 +649,8 @@ void DirectBA::BundleAdjustmentAlternating(hipStream_t stream, bool optimize_dep
             (int)optimize_poses, (int)optimize_geometry, (int)do_surfel_updates, (int)optimize_depth_intrinsics, (int)optimize_color_intrinsics,
             progress_function ? 1 : 0, timer ? 1 : 0, timings_stream_ ? 1 : 0, keyframe_shard_world_, (int)full_window, max_iterations);
   if (optimize_poses && optimize_geometry && !do_surfel_updates && !optimize_depth_intrinsics && !optimize_color_intrinsics &&
-      !progress_function && !timer && !timings_stream_ && keyframe_shard_world_ == 1 && full_window && max_iterations > 0) {
+      !progress_function && !timer && !timings_stream_ && keyframe_shard_world_ == 1 && full_window && max_iterations > 0 &&
+      !pose_step_control_on_ /* the controlled pose phase is a stage call: the iterations go through the loop below */) {
     if (fixed_active_keyframe_set) {
       Lock();
       set_window_activation();
@@ -795,9 +819,26 @@ void DirectBA::BundleAdjustmentAlternating(hipStream_t stream, bool optimize_dep
       vector<int> its(K), conv(K);
       int rounds = 0, converged_bound = 0;
       const bahip_surfels s = SurfelsStruct();
-      BAHIP_CHECKED_CALL(bahip_estimate_keyframe_poses_and_update_activation(ctx_, use_depth_residuals_, use_descriptor_residuals_, &s,
-                                                                             poses->data(), its.data(), conv.data(), moved->data(),
-                                                                             &rounds, &converged_bound));
+      if (pose_step_control_on_) {
+        // per keyframe id: the damping factor its last pose phase left (a new keyframe: lambda_initial)
+        const bahip_pose_step_control control{pose_step_control_.lambda_up, pose_step_control_.lambda_down, pose_step_control_.lambda_min,
+                                              pose_step_control_.lambda_max, pose_step_control_.max_trials};
+        vector<float> lambdas(std::max(K, 1));
+        vector<int> trials(std::max(K, 1)), rejected(std::max(K, 1));
+        for (int b = 0; b < K; ++b) lambdas[b] = pose_lambda(bound_ids_[b]);
+        BAHIP_CHECKED_CALL(bahip_estimate_keyframe_poses_controlled(ctx_, use_depth_residuals_, use_descriptor_residuals_, &control, &s, /*update_activation*/ 1,
+                                                                    lambdas.data(), poses->data(), its.data(), conv.data(), moved->data(), trials.data(),
+                                                                    rejected.data(), nullptr, nullptr, &rounds, &converged_bound));
+        for (int b = 0; b < K; ++b) {
+          pose_lambdas_[bound_ids_[b]] = lambdas[b];
+          last_pose_trials_ += trials[b];
+          last_pose_rejected_steps_ += rejected[b];
+        }
+      } else {
+        BAHIP_CHECKED_CALL(bahip_estimate_keyframe_poses_and_update_activation(ctx_, use_depth_residuals_, use_descriptor_residuals_, &s,
+                                                                               poses->data(), its.data(), conv.data(), moved->data(),
+                                                                               &rounds, &converged_bound));
+      }
       pending.push_back([this, poses, moved]() {
         for (const shared_ptr<Keyframe>& keyframe : keyframes_) {
           if (!keyframe || keyframe->activation() == Keyframe::Activation::kInactive) continue;

@@ -167,6 +167,23 @@ class DirectBA {
   float last_pcg_lambda() const { return pcg_lambda_; }                        // the factor the next outer iteration will start with
   int last_pcg_trials() const { return last_pcg_trials_; }                     // trial steps of the last BundleAdjustment() call
   int last_pcg_rejected_steps() const { return last_pcg_rejected_steps_; }     // ... and those of them that were undone
+  // Step control of the pose phase of the alternating scheme (ours; default off = NULL: every Gauss-Newton step is taken, as the
+  // reference does).  On: BundleAdjustment(!use_pcg) drives its iterations through the stage entry points (the device-driven loop is
+  // not used) and its pose phase is bahip_estimate_keyframe_poses_controlled -- per keyframe, a Marquardt-damped step is kept only if
+  // that keyframe's cost falls strictly.  The damping factor is kept per keyframe id across iterations and across calls; a keyframe
+  // seen for the first time starts at lambda_initial.  Refused (returns false) under keyframe sharding.
+  struct PoseStepControl {
+    float lambda_initial = 1e-3f, lambda_up = 10.f, lambda_down = 0.33f, lambda_min = 0.f, lambda_max = 1e6f;
+    int max_trials = 4;
+  };
+  bool SetPoseStepControl(const PoseStepControl* control);
+  bool pose_step_control() const { return pose_step_control_on_; }
+  int last_pose_trials() const { return last_pose_trials_; }                   // candidates evaluated in the last BundleAdjustment() call
+  int last_pose_rejected_steps() const { return last_pose_rejected_steps_; }   // ... and those of them that were rejected
+  float pose_lambda(int keyframe_id) const {                                   // the factor keyframe_id's next pose phase starts with
+    const auto it = pose_lambdas_.find(keyframe_id);
+    return it == pose_lambdas_.end() ? pose_step_control_.lambda_initial : it->second;
+  }
   // Multi-GPU surfel sharding: sums of the per-keyframe normal equations go through this hook
   // (see include/badslam_hip.h, bahip_allreduce_fn).
   void SetAllReduce(bahip_allreduce_fn fn, void* user) { BAHIP_CHECKED_CALL(bahip_context_set_allreduce(ctx_, fn, user)); }
@@ -292,6 +309,10 @@ class DirectBA {
   PCGStepControl pcg_step_control_;
   float pcg_lambda_ = 0.f;
   int last_pcg_trials_ = 0, last_pcg_rejected_steps_ = 0;
+  bool pose_step_control_on_ = false;
+  PoseStepControl pose_step_control_;
+  std::unordered_map<int, float> pose_lambdas_;   // keyframe id -> damping factor
+  int last_pose_trials_ = 0, last_pose_rejected_steps_ = 0;
   bool distributed_lifecycle_ = false;   // SetDistributedLifecycle
   int pcg_sum_classes_ = 1;        // (SetPCGSumClasses: the windowed scheme needs 1)
   int shard_rank_ = 0, shard_world_ = 1, whole_cloud_depth_ = 0;

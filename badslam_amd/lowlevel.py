@@ -374,6 +374,31 @@ class Scene:
                                                           C.byref(rounds)))
         return (np.array(list(poses), dtype=np.float64).reshape(K, 7), np.array(list(its)), np.array(list(conv)), rounds.value)
 
+    def estimate_keyframe_poses_controlled(self, lambdas, control, use_depth=True, use_desc=True, update_activation=False):
+        """The pose phase under step control (bahip_estimate_keyframe_poses_controlled): `lambdas` = the damping factor per bound keyframe,
+        `control` = (lambda_up, lambda_down, lambda_min, lambda_max, max_trials).  Adopts the poses the call leaves.  Returns a dict of
+        arrays in bound order -- poses (binary32, K x 7), lambdas, iterations, converged, moved, trials, rejected -- the lists
+        cost_before / cost_after (dicts like evaluate_cost's), and rounds, num_converged."""
+        K = len(self.keyframes)
+        up, down, lo, hi, trials = control
+        ctl = capi.PoseStepControl(float(up), float(down), float(lo), float(hi), int(trials))
+        lam = (C.c_float * max(1, K))(*[float(v) for v in lambdas])
+        poses = (C.c_float * (7 * max(1, K)))()
+        its, conv, moved, ran, rejected = ((C.c_int * max(1, K))() for _ in range(5))
+        before, after = (capi.Cost * max(1, K))(), (capi.Cost * max(1, K))()
+        rounds, num_converged = C.c_int(), C.c_int()
+        s = self.surfels_struct()
+        capi.check(self.lib.bahip_estimate_keyframe_poses_controlled(self.ctx.handle, int(use_depth), int(use_desc), C.byref(ctl), C.byref(s),
+                                                                     int(update_activation), lam, poses, its, conv, moved, ran, rejected,
+                                                                     before, after, C.byref(rounds), C.byref(num_converged)))
+        arr = np.array(list(poses), dtype=np.float32).reshape(-1, 7)[:K]
+        for k, kf in enumerate(self.keyframes):
+            kf["pose"] = arr[k].copy()
+        ints = lambda a: np.array(list(a), dtype=np.int64)[:K]
+        return {"poses": arr, "lambdas": np.array(list(lam), dtype=np.float32)[:K], "iterations": ints(its), "converged": ints(conv),
+                "moved": ints(moved), "trials": ints(ran), "rejected": ints(rejected), "cost_before": [cost_dict(c) for c in before[:K]],
+                "cost_after": [cost_dict(c) for c in after[:K]], "rounds": rounds.value, "num_converged": num_converged.value}
+
     def update_surfel_normals(self):
         s = self.surfels_struct()
         capi.check(self.lib.bahip_update_surfel_normals(self.ctx.handle, C.byref(s)))

@@ -99,6 +99,14 @@ int dba_set_windowed_pcg(dba_handle* h, int enabled);
 int dba_set_pcg_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_down, float lambda_min,
                              float lambda_max, int max_trials);
 int dba_pcg_step_stats(dba_handle* h, float* lambda, int* trials, int* rejected_steps);
+/* DirectBA::SetPoseStepControl (ours, default off): the pose phase of BundleAdjustment(!use_pcg) keeps a damped Gauss-Newton step of a
+ * keyframe only if that keyframe's cost falls (bahip_estimate_keyframe_poses_controlled; lambda_initial is where a keyframe seen for the
+ * first time starts, the other fields are bahip_pose_step_control's).  enabled = 0: off.  Returns 1 (refused) under keyframe sharding and
+ * for values out of range.  dba_get_pose_step_stats: candidates evaluated / rejected in the last BundleAdjustment call, and the damping
+ * factor keyframe_id's next pose phase starts with. */
+int dba_set_pose_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_down, float lambda_min,
+                              float lambda_max, int max_trials);
+int dba_get_pose_step_stats(dba_handle* h, int* trials, int* rejected_steps, int keyframe_id, float* lambda);
 /* DirectBA::SetSurfelSharding: this object holds rank `rank`'s chunk-cyclic shard of one surfel cloud (bahip_gather_surfel_shards) */
 int dba_set_surfel_sharding(dba_handle* h, int rank, int world, uint32_t chunk);
 /* DirectBA::SetDistributedLifecycle (ours, default off): under surfel sharding the lifecycle's sweeps are dealt over the ranks

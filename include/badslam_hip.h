@@ -646,6 +646,41 @@ int bahip_pcg_iteration_controlled(bahip_context* ctx, const bahip_pcg_options* 
                                    int have_cost_before, bahip_cost* cost_before, bahip_cost* cost_after, int* trials_out,
                                    int* accepted_out);
 
+/* ---- step control for the pose phase of the alternating scheme (ours: the reference takes every Gauss-Newton step;
+ * kernels_pose_trial.hip) ---------------------------------------------------------------------------------------
+ * Work items: every bound keyframe that is not kInactive.  Per item: the pose T, a damping factor lambda (binary32, >= 0), the
+ * objective c at T and the normal equations (H, b) at T.  The objective of an item is f = (depth + descriptor_1) + descriptor_2 in
+ * binary64 of its per-keyframe entry exactly as bahip_evaluate_cost(..., per_keyframe) reports it with that pose in the table.  The
+ * damped step is the plain phase's solve with diagonal entry i replaced by (double)H_ii + (double)lambda * (double)H_ii; lambda = 0
+ * gives every bit of the plain step.  Round 0 evaluates (H, b, c) at T; every later round computes T' = T * exp(-x(lambda)) from the
+ * stored (H, b), evaluates (H', b', c') at T' in ONE fused sweep, and accepts iff f(c') is finite and f(c') < f(c).  Accepted: T, H,
+ * b, c <- T', H', b', c', lambda <- max(lambda * lambda_down, lambda_min); the item is done (converged) if x passed the convergence
+ * test, done (not converged) after BAHIP_MAX_POSE_ITERATIONS accepted steps.  Rejected: T, H, b, c stay word for word, lambda <-
+ * min(lambda * lambda_up, lambda_max); done (not converged) after max_trials consecutive rejections.  The argument checks are those
+ * of bahip_pcg_step_control. */
+typedef struct bahip_pose_step_control {
+  float lambda_up, lambda_down;   /* factor after a rejected / an accepted step (up >= 1, 0 < down <= 1) */
+  float lambda_min, lambda_max;   /* 0 <= min <= max, finite */
+  int max_trials;                 /* consecutive rejected candidates after which an item gives up, >= 1 */
+} bahip_pose_step_control;
+/* The pose phase under that control.  Arrays have num_keyframes entries in bound order; every output may be NULL.  lambda_inout: the
+ * damping factor of every keyframe, in and out (finite, >= 0).  iterations_done: accepted steps; trials_out: candidates evaluated;
+ * rejected_out: candidates rejected; cost_before_out / cost_after_out: the keyframe's cost at its pose before / after the call, the
+ * bits of bahip_evaluate_cost's per-keyframe entry.  update_activation != 0: moved[] and the table's activations follow the rule of
+ * bahip_estimate_keyframe_poses_and_update_activation on the pose before and after the call, and *num_converged_out counts as there.
+ * A kInactive keyframe: pose and lambda untouched, both costs zeros, converged = 1.  A keyframe without an accepted step keeps every
+ * word of its pose, in the table and in global_T_frame_out.  *rounds_out: sweeps made (round 0 included).
+ * Surfel sharding: the cost rows travel as int64 with the normal equations (one exchange per round); every rank takes the same
+ * decisions and ends with the same bits.  Keyframe sharding: refused (error text, context usable).  A non-finite or out-of-range
+ * total of the normal equations fails the call as in the plain phase.  The host waits once per round. */
+int bahip_estimate_keyframe_poses_controlled(bahip_context* ctx, int use_depth_residuals, int use_descriptor_residuals,
+                                             const bahip_pose_step_control* control, const bahip_surfels* surfels, int update_activation,
+                                             float* lambda_inout, float* global_T_frame_out, int* iterations_done, int* converged, int* moved,
+                                             int* trials_out, int* rejected_out, bahip_cost* cost_before_out, bahip_cost* cost_after_out,
+                                             int* rounds_out, int* num_converged_out);
+/* bahip_debug_pose_step with the damped diagonal (lambda = 0: its 25 words bit for bit). */
+int bahip_debug_pose_step_damped(bahip_context* ctx, const float* H21_b6, const float* global_T_frame, float lambda, float* out_25);
+
 /* ---- test hook --------------------------------------------------------------------------------------
  * Per-pair evaluation with the production device functions (association, the three raw residuals,
  * weights, pose Jacobians, image gradients) for `count` surfel indices against one frame; 40 floats
