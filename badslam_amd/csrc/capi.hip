@@ -58,22 +58,16 @@ void fill_pose(KfEntry* e, const float* global_T_frame) {
 }
 
 int planes_alloc(int width, int height, int cwidth, int cheight, bahip_frame_planes** out) {
-  bahip_frame_planes* p = new bahip_frame_planes();
+  std::unique_ptr<bahip_frame_planes> p(new bahip_frame_planes());
   p->width = width; p->height = height; p->cwidth = cwidth; p->cheight = cheight;
   const size_t gwords = (size_t)plane_tiles_x(width) * plane_tiles_y(height) * 32;
   const size_t fwords = (size_t)plane_tiles_x(cwidth + 2) * plane_tiles_y(cheight + 2) * 32;
-  if (hipMalloc(&p->geom, gwords * sizeof(uint32_t)) != hipSuccess || hipMalloc(&p->lumafp, fwords * sizeof(uint32_t)) != hipSuccess) {
-    hipFree(p->geom); hipFree(p->lumafp); delete p;
+  if (p->geom.reserve(gwords, 0, "frame planes") || p->lumafp.reserve(fwords, 0, "frame planes"))
     return fail("hipMalloc of frame planes failed", __FILE__, __LINE__);
-  }
-  *out = p;
+  *out = p.release();
   return 0;
 }
-void planes_free(bahip_frame_planes* p) {
-  if (!p) return;
-  hipFree(p->geom); hipFree(p->lumafp);
-  delete p;
-}
+void planes_free(bahip_frame_planes* p) { delete p; }
 
 KfEntry raw_entry(const bahip_frame& f) {
   KfEntry e{};
@@ -85,19 +79,23 @@ KfEntry raw_entry(const bahip_frame& f) {
 
 // Frame table entry for `f`.  The sweeps read the tiled BA planes; a caller that maintains them (Keyframe does) passes
 // them in f.planes, otherwise they are packed here, on the context stream, into library-owned planes (`slot` of `pool`).
-static int make_entry_in(bahip_context* ctx, std::vector<bahip_frame_planes*>& pool, const bahip_frame& f, size_t slot, KfEntry* out) {
+static int make_entry_in(bahip_context* ctx, std::vector<std::unique_ptr<bahip_frame_planes>>& pool, const bahip_frame& f, size_t slot, KfEntry* out) {
   KfEntry e = raw_entry(f);
   const bahip_frame_planes* p = f.planes;
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics must precede any call that takes frames");
   const int w = ctx->in.width, h = ctx->in.height, cw = ctx->in.cwidth, ch = ctx->in.cheight;
   if (!p) {
-    if (pool.size() <= slot) pool.resize(slot + 1, nullptr);
-    bahip_frame_planes*& mine = pool[slot];
-    if (mine && (mine->width != w || mine->height != h || mine->cwidth != cw || mine->cheight != ch)) { planes_free(mine); mine = nullptr; }
-    if (!mine && planes_alloc(w, h, cw, ch, &mine)) return 1;
+    if (pool.size() <= slot) pool.resize(slot + 1);
+    std::unique_ptr<bahip_frame_planes>& mine = pool[slot];
+    if (mine && (mine->width != w || mine->height != h || mine->cwidth != cw || mine->cheight != ch)) mine.reset();
+    if (!mine) {
+      bahip_frame_planes* fresh = nullptr;
+      if (planes_alloc(w, h, cw, ch, &fresh)) return 1;
+      mine.reset(fresh);
+    }
     launch_pack_planes(ctx->stream, e, w, h, cw, ch, mine->geom, mine->lumafp);
     CHECK_LAUNCH();
-    p = mine;
+    p = mine.get();
   }
   REQUIRE(p->width == w && p->height == h && p->cwidth == cw && p->cheight == ch, "frame planes do not match the camera image sizes");
   e.geom = p->geom; e.lumafp = p->lumafp;
@@ -117,46 +115,33 @@ SurfelsView make_view(const bahip_surfels* s) {
   return v;
 }
 
-// Grow-on-demand for library-owned scratch: the new block is allocated FIRST and swapped in on success, so a failed grow
-// leaves pointer and capacity as they were (no dangling pointer behind an unchanged capacity, no double free at destroy).
+// Grow-on-demand for library-owned scratch is Buffer::reserve (capi_buffers.h): the new block is allocated FIRST and swapped in on
+// success, so a failed grow leaves the buffer as it was.  Buffers that must grow TOGETHER OR NOT AT ALL are reserved as fresh locals
+// and moved into the context once every allocation has succeeded (a local that is not moved frees itself).
 
 int ensure_work(bahip_context* ctx, int n) {
   if (n <= ctx->work_capacity) return 0;
   const int cap = n + 64;
-  // allocate first, swap on success: a failed grow leaves the context as it was
-  PoseWork* work = nullptr; HbFixed* hb = nullptr; PoseWork* pinned = nullptr;
+  DeviceBuffer<PoseWork> work; DeviceBuffer<HbFixed> hb; PinnedBuffer<PoseWork> pinned(kHostVisible);
   const size_t records = pose_work_records((size_t)cap);
-  if (hipMalloc(&work, sizeof(PoseWork) * records) != hipSuccess || hipMalloc(&hb, sizeof(HbFixed) * kHbStride * cap) != hipSuccess ||
-      hipHostMalloc(&pinned, sizeof(PoseWork) * records, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-    hipFree(work); hipFree(hb); if (pinned) hipHostFree(pinned);
+  if (work.reserve(records, 0, "the pose work items") || hb.reserve((size_t)kHbStride * cap, 0, "the pose work items") ||
+      pinned.reserve(records, 0, "the pose work items"))
     return fail("allocation of the pose work items failed", __FILE__, __LINE__);
-  }
-  hipFree(ctx->dev_work); hipFree(ctx->dev_Hb);
-  if (ctx->pinned_work) hipHostFree(ctx->pinned_work);
-  ctx->dev_work = work; ctx->dev_Hb = hb; ctx->pinned_work = pinned;
+  ctx->dev_work = std::move(work); ctx->dev_Hb = std::move(hb); ctx->pinned_work = std::move(pinned);
   ctx->work_capacity = cap;
   return 0;
 }
 
 int ensure_px(bahip_context* ctx, size_t px, size_t scan_n) {
-  if (px > ctx->px_capacity) {
-    uint8_t* flags = nullptr; uint32_t* indices = nullptr;
-    if (hipMalloc(&flags, px) != hipSuccess || hipMalloc(&indices, px * sizeof(uint32_t)) != hipSuccess) {
-      hipFree(flags); hipFree(indices);
+  if (px > ctx->dev_flags.size()) {   // (flags and indices always hold the same number of pixels)
+    DeviceBuffer<uint8_t> flags; DeviceBuffer<uint32_t> indices;
+    if (flags.reserve(px, 0, "the new-surfel flags") || indices.reserve(px, 0, "the new-surfel indices"))
       return fail("allocation of the new-surfel flag / index vectors failed", __FILE__, __LINE__);
-    }
-    hipFree(ctx->dev_flags); hipFree(ctx->dev_indices);
-    ctx->dev_flags = flags; ctx->dev_indices = indices;
-    ctx->px_capacity = px;
+    ctx->dev_flags = std::move(flags); ctx->dev_indices = std::move(indices);
   }
   const size_t need = scan_temp_bytes(scan_n);
-  if (need > ctx->scan_temp_bytes) {
-    void* temp = nullptr;
-    if (hipMalloc(&temp, need) != hipSuccess) return fail("allocation of the scan scratch failed", __FILE__, __LINE__);
-    hipFree(ctx->scan_temp);
-    ctx->scan_temp = temp;
-    ctx->scan_temp_bytes = need;
-  }
+  if (need > ctx->scan_temp.size() && ctx->scan_temp.reserve(need, 0, "the scan scratch"))
+    return fail("allocation of the scan scratch failed", __FILE__, __LINE__);
   return 0;
 }
 
@@ -186,30 +171,19 @@ void timer_end(bahip_context* ctx, int stage) {
 
 int ensure_tile_bounds(bahip_context* ctx, uint32_t surfels) {
   const size_t need = pose_tile_bounds_bytes(surfels);
-  if (need <= ctx->tile_bounds_bytes) return 0;
-  void* grown = nullptr;
-  HIP_TRY(hipMalloc(&grown, need + need / 4));
-  hipFree(ctx->dev_tile_bounds);
-  ctx->dev_tile_bounds = grown;
-  ctx->tile_bounds_bytes = need + need / 4;
-  return 0;
+  if (need <= ctx->dev_tile_bounds.size()) return 0;
+  return ctx->dev_tile_bounds.reserve(need, need / 4, "the tile bounds of the pose sweep");
 }
 
 int g_tile_order_enabled = bahip_env_int("BAHIP_TILE_ORDER", 1);
 int ensure_tile_schedule(bahip_context* ctx, uint32_t padded_tiles) {
   if (padded_tiles <= ctx->tile_schedule_capacity) return 0;
   const size_t cap = (size_t)padded_tiles + padded_tiles / 4;
-  uint32_t* cost = nullptr; uint32_t* order = nullptr;
-  if (hipMalloc(&cost, sizeof(uint32_t) * cap) != hipSuccess || hipMalloc(&order, sizeof(uint32_t) * tile_schedule_words((uint32_t)cap)) != hipSuccess) {
-    hipFree(cost); hipFree(order);
+  DeviceBuffer<uint32_t> cost, order;
+  if (cost.reserve(cap, 0, "the tile census") || order.reserve(tile_schedule_words((uint32_t)cap), 0, "the tile schedule"))
     return fail("allocation of the tile schedule failed", __FILE__, __LINE__);
-  }
-  if (hipMemsetAsync(cost, 0, sizeof(uint32_t) * cap, ctx->stream) != hipSuccess) {
-    hipFree(cost); hipFree(order);
-    return fail("clearing the tile census failed", __FILE__, __LINE__);
-  }
-  hipFree(ctx->dev_tile_cost); hipFree(ctx->dev_tile_order);
-  ctx->dev_tile_cost = cost; ctx->dev_tile_order = order;
+  if (hipMemsetAsync(cost, 0, sizeof(uint32_t) * cap, ctx->stream) != hipSuccess) return fail("clearing the tile census failed", __FILE__, __LINE__);
+  ctx->dev_tile_cost = std::move(cost); ctx->dev_tile_order = std::move(order);
   ctx->tile_schedule_capacity = cap;
   ctx->tile_order_tiles = 0;
   return 0;
@@ -242,17 +216,14 @@ int bahip_context_create(bahip_context** out, void* hip_stream) {
   if (const char* e = getenv("BAHIP_ARITHMETIC")) ctx->arithmetic = (strcmp(e, "fast") == 0 || strcmp(e, "1") == 0) ? BAHIP_ARITHMETIC_FAST : BAHIP_ARITHMETIC_EXACT;
   ctx->in.fast_math = ctx->arithmetic;
   if (const char* e = getenv("BAHIP_INTR_SLICES")) ctx->intr_slices_forced = std::min(std::max(atoi(e), 0), kIntrMaxSlices);   // experiments: slices of the intrinsics sweep
-  const bool ok = hipMalloc(&ctx->dev_counter, 16 * sizeof(int)) == hipSuccess && hipMemset(ctx->dev_counter, 0, 16 * sizeof(int)) == hipSuccess &&
-                  hipHostMalloc(&ctx->pinned_i, 16 * sizeof(int)) == hipSuccess &&
-                  hipHostMalloc(&ctx->pinned_f, 128 * sizeof(float)) == hipSuccess &&
-                  hipMalloc(&ctx->dev_tile_counters, 16 * sizeof(uint32_t)) == hipSuccess &&
-                  hipMemset(ctx->dev_tile_counters, 0, 16 * sizeof(uint32_t)) == hipSuccess &&
-                  hipMalloc(&ctx->dev_frame1, sizeof(KfEntry)) == hipSuccess &&
-                  hipMalloc(&ctx->dev_work1, sizeof(PoseWork) * pose_work_records(1)) == hipSuccess &&
-                  hipHostMalloc(&ctx->pinned_work1, sizeof(PoseWork) * (1 + kPoseTailRecords), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
-                  hipMalloc(&ctx->dev_Hb1, sizeof(HbFixed) * kHbStride) == hipSuccess;
+  const char* what = "the context scratch";
+  const bool ok = !ctx->dev_counter.reserve(16, 0, what) && hipMemset(ctx->dev_counter, 0, 16 * sizeof(int)) == hipSuccess &&
+                  !ctx->pinned_i.reserve(16, 0, what) && !ctx->pinned_f.reserve(128, 0, what) &&
+                  !ctx->dev_tile_counters.reserve(16, 0, what) && hipMemset(ctx->dev_tile_counters, 0, 16 * sizeof(uint32_t)) == hipSuccess &&
+                  !ctx->dev_frame1.reserve(1, 0, what) && !ctx->dev_work1.reserve(pose_work_records(1), 0, what) &&
+                  !ctx->pinned_work1.reserve(1 + kPoseTailRecords, 0, what) && !ctx->dev_Hb1.reserve(kHbStride, 0, what);
   if (!ok) {
-    bahip_context_destroy(ctx);   // frees whatever was allocated (hipFree(nullptr) is a no-op)
+    bahip_context_destroy(ctx);   // (the buffers that were allocated go with the context)
     return fail("bahip_context_create: allocation of the context scratch failed", __FILE__, __LINE__);
   }
   *out = ctx;
@@ -271,29 +242,10 @@ void bahip_context_destroy(bahip_context* ctx) {
     bahip::pose_timeline_dump((std::string(dir) + "/pose_timeline.bin").c_str());
   }
 #endif
-  if (ctx->pinned_work) hipHostFree(ctx->pinned_work);
-  hipFree(ctx->dev_kfs); hipFree(ctx->dev_work); hipFree(ctx->dev_Hb); hipFree(ctx->dev_cost);
-  hipFree(ctx->dev_frame1); hipFree(ctx->dev_work1); hipFree(ctx->dev_Hb1); hipFree(ctx->dev_tile_counters);
-  hipFree(ctx->dev_counter);
-  if (ctx->pinned_i) hipHostFree(ctx->pinned_i);
-  if (ctx->pinned_f) hipHostFree(ctx->pinned_f);
-  if (ctx->pinned_work1) hipHostFree(ctx->pinned_work1);
-  stage_free(&ctx->stage_kfs); stage_free(&ctx->stage_covis); stage_free(&ctx->stage_window); stage_free(&ctx->stage_gather);
-  hipFree(ctx->dev_flags); hipFree(ctx->dev_indices); hipFree(ctx->scan_temp);
-  hipFree(ctx->dev_merge_batch);
-  hipFree(ctx->dev_sort_scratch);
-  hipFree(ctx->dev_create_batch);
-  hipFree(ctx->dev_covis); hipFree(ctx->dev_covis_T); hipFree(ctx->dev_covis_csr); hipFree(ctx->dev_tile_bounds); hipFree(ctx->dev_lifecycle_bounds); hipFree(ctx->dev_lifecycle_frames); hipFree(ctx->dev_lifecycle_cursors); hipFree(ctx->dev_lifecycle_lists); hipFree(ctx->dev_window);
-  hipFree(ctx->intr_bin_cursors); hipFree(ctx->intr_bin_records); hipHostFree(ctx->intr_bin_counts_host);
+  // what has an order; the memory (every buffer and plane is a member that owns its block: capi_buffers.h) goes with the context
   if (ctx->intr_aux_stream) { hipStreamDestroy(ctx->intr_aux_stream); for (hipEvent_t e : ctx->intr_events) if (e) hipEventDestroy(e); }
-  hipFree(ctx->intr_scratch); hipFree(ctx->pcg_buf); hipFree(ctx->pcg_exact); hipFree(ctx->pcg_stage_ctl); hipFree(ctx->kf_partials); hipFree(ctx->pcg_window); hipFree(ctx->pcg_trial); hipFree(ctx->pose_trial); hipFree(ctx->dev_gather_table);
-  for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) hipFree(ctx->merge_planes[b]);
-  hipFree(ctx->dev_tile_cost); hipFree(ctx->dev_tile_order);
-  hipFree(ctx->dev_loop_ctl);
-  if (ctx->host_loop_ctl) hipHostFree(ctx->host_loop_ctl);
+  stage_free(&ctx->stage_kfs); stage_free(&ctx->stage_covis); stage_free(&ctx->stage_window); stage_free(&ctx->stage_gather);
   rccl_destroy_communicator(ctx);
-  for (bahip_frame_planes* p : ctx->auto_planes) planes_free(p);
-  for (bahip_frame_planes* p : ctx->batch_planes) planes_free(p);
   for (auto& t : ctx->timers) for (auto e : t.ev) hipEventDestroy(e);
   delete ctx;
 }
@@ -535,15 +487,9 @@ int stage_upload(UploadStage* stage, void* dev_dst, const void* src, size_t byte
   }
   const size_t total = bytes + bytes2;
   if (total == 0) return 0;
-  if (total > stage->capacity) {
-    void* grown = nullptr;
-    HIP_TRY(hipHostMalloc(&grown, total + total / 4 + 4096));
-    if (stage->pinned) hipHostFree(stage->pinned);
-    stage->pinned = grown;
-    stage->capacity = total + total / 4 + 4096;
-  }
+  if (total > stage->pinned.size() && stage->pinned.reserve(total, total / 4 + 4096, "an upload stage")) return 1;
   if (!stage->done) HIP_TRY(hipEventCreateWithFlags(&stage->done, hipEventDisableTiming));
-  char* p = static_cast<char*>(stage->pinned);
+  char* p = stage->pinned;
   if (bytes) { memcpy(p, src, bytes); HIP_TRY(hipMemcpyAsync(dev_dst, p, bytes, hipMemcpyHostToDevice, stream)); }
   if (bytes2) { memcpy(p + bytes, src2, bytes2); HIP_TRY(hipMemcpyAsync(dev_dst2, p + bytes, bytes2, hipMemcpyHostToDevice, stream)); }
   HIP_TRY(hipEventRecord(stage->done, stream));
@@ -552,8 +498,8 @@ int stage_upload(UploadStage* stage, void* dev_dst, const void* src, size_t byte
 }
 void stage_free(UploadStage* stage) {
   if (stage->done) { hipEventSynchronize(stage->done); hipEventDestroy(stage->done); }
-  if (stage->pinned) hipHostFree(stage->pinned);
-  *stage = UploadStage{};
+  stage->pinned.release();
+  stage->done = nullptr; stage->pending = false;
 }
 extern "C" {
 
@@ -567,11 +513,7 @@ int bahip_set_keyframes(bahip_context* ctx, const bahip_keyframe* keyframes, int
     e.activation = keyframes[k].activation;
     ctx->host_kfs[k] = e;
   }
-  if (num_keyframes > ctx->kfs_capacity) {
-    size_t cap = (size_t)ctx->kfs_capacity;
-    if (grow_device(&ctx->dev_kfs, &cap, (size_t)num_keyframes, 64, "the keyframe table")) return 1;
-    ctx->kfs_capacity = (int)cap;
-  }
+  if ((size_t)num_keyframes > ctx->dev_kfs.size() && ctx->dev_kfs.reserve((size_t)num_keyframes, 64, "the keyframe table")) return 1;
   ctx->num_kfs = num_keyframes;
   ctx->have_covisibility = false;   // lists refer to the previous binding
   ctx->window.clear();

@@ -156,7 +156,7 @@ int geometry_keyframe_sharded(bahip_context* ctx, bool use_depth, bool use_desc,
   // class c (the keyframes k with k % classes == c) lives on rank c % world: world divides classes, both powers of two
   const int classes = ctx->sum_classes;
   const size_t normals_floats = (size_t)classes * nn * stride, position_floats = (size_t)classes * np * stride;
-  if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, normals_floats + position_floats, 0, "the class partials of the geometry step")) return 1;
+  if (ctx->kf_partials.reserve(normals_floats + position_floats, 0, "the class partials of the geometry step")) return 1;
   uint32_t owned = 0;
   for (int c = 0; c < classes; ++c) if ((c & (ctx->kf_world - 1)) == ctx->kf_rank) owned |= 1u << c;
   const ClassPartials cpn{ctx->kf_partials, (uint32_t)stride, owned}, cpp{ctx->kf_partials + normals_floats, (uint32_t)stride, owned};
@@ -184,8 +184,8 @@ int bahip_update_surfel_activation(bahip_context* ctx, const bahip_surfels* surf
     REQUIRE(is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator");
     if (surfels_size == 0) return 0;
     const size_t words = ((size_t)surfels_size + 63) & ~(size_t)63;
-    if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, words, 0, "the activation hit words")) return 1;
-    uint32_t* hits = reinterpret_cast<uint32_t*>(ctx->kf_partials);
+    if (ctx->kf_partials.reserve(words, 0, "the activation hit words")) return 1;
+    uint32_t* hits = reinterpret_cast<uint32_t*>(ctx->kf_partials.get());
     HIP_TRY(hipMemsetAsync(hits, 0, sizeof(uint32_t) * words, ctx->stream));
     timer_begin(ctx, 0, true);
     launch_activation_hits(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels), surfels_size, ctx->kf_rank, ctx->kf_world, hits);
@@ -222,7 +222,7 @@ int bahip_update_surfel_normals(bahip_context* ctx, const bahip_surfels* surfels
     const SurfelsView v = make_view(surfels);
     if (v.size == 0) return 0;
     const size_t stride = ((size_t)v.size + 63) & ~(size_t)63, floats = (size_t)ctx->sum_classes * kNormalsSums * stride;
-    if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, floats, 0, "the class partials of the normals update")) return 1;
+    if (ctx->kf_partials.reserve(floats, 0, "the class partials of the normals update")) return 1;
     const ClassPartials cp{ctx->kf_partials, (uint32_t)stride, owned_classes(ctx, ctx->sum_classes)};
     HIP_TRY(hipMemsetAsync(ctx->kf_partials, 0, sizeof(float) * floats, ctx->stream));
     launch_normals_phase(ctx->stream, 1, ctx->in, ctx->dev_kfs, ctx->num_kfs, v, cp);
@@ -296,7 +296,7 @@ int bahip_accumulate_pose_estimation_coeffs(bahip_context* ctx, int use_depth, i
   CHECK_LAUNCH();
   // (keyframe sharding: every rank holds all surfels, a single frame's equations are complete on each)
   if (!kf_sharded(ctx) && reduce_over_ranks(ctx, ctx->dev_Hb1, kHbStride, BAHIP_SUM_I64)) return 1;
-  HbFixed* fixed = reinterpret_cast<HbFixed*>(ctx->pinned_f);   // 56 x 8 bytes of the 128-float pinned buffer
+  HbFixed* fixed = reinterpret_cast<HbFixed*>(ctx->pinned_f.get());   // 56 x 8 bytes of the 128-float pinned buffer
   HIP_TRY(hipMemcpyAsync(fixed, ctx->dev_Hb1, sizeof(HbFixed) * kHbStride, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   // the sweep's "not representable" flag travels in the row's unused 28th coefficient (kernels_pose.hip: pose_invalid_word), summed
@@ -429,11 +429,9 @@ int bahip_alternating_iterations(bahip_context* ctx, const bahip_alternating_opt
   REQUIRE(opt->activation_surfels_size <= surfels->surfels_size, "activation range exceeds surfels_size");
   if (ensure_work(ctx, K)) return 1;
   if (!ctx->dev_loop_ctl || !ctx->host_loop_ctl) {   // both or neither: a call that got only the first must not leave it behind
-    if (!ctx->dev_loop_ctl) HIP_TRY(hipMalloc(&ctx->dev_loop_ctl, sizeof(int) * kLoopWords));
-    if (hipHostMalloc(&ctx->host_loop_ctl, sizeof(int) * (kLoopWords + kLoopLogSlots), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-      ctx->host_loop_ctl = nullptr;
-      hipFree(ctx->dev_loop_ctl);
-      ctx->dev_loop_ctl = nullptr;
+    if (ctx->dev_loop_ctl.reserve(kLoopWords, 0, "the loop control words")) return 1;
+    if (ctx->host_loop_ctl.reserve(kLoopWords + kLoopLogSlots, 0, "the loop control words")) {
+      ctx->dev_loop_ctl.release();
       return fail("hipHostMalloc of the loop control words failed", __FILE__, __LINE__);
     }
   }
@@ -634,13 +632,7 @@ int bahip_set_covisibility(bahip_context* ctx, const int* offsets, const int* in
   ctx->covis_offsets.assign(offsets, offsets + K + 1);
   ctx->covis_indices.assign(indices, indices + total);
   const size_t need = (size_t)K + 1 + (size_t)total;
-  if (need > ctx->covis_csr_capacity) {
-    int* grown = nullptr;
-    HIP_TRY(hipMalloc(&grown, sizeof(int) * (need + 1024)));
-    hipFree(ctx->dev_covis_csr);   // only the CSR buffer is re-grown here (tile bounds and window have their own grow paths)
-    ctx->dev_covis_csr = grown;
-    ctx->covis_csr_capacity = need + 1024;
-  }
+  if (ctx->dev_covis_csr.reserve(need, 1024, "the co-visibility lists")) return 1;
   if (stage_upload(&ctx->stage_covis, ctx->dev_covis_csr, ctx->covis_offsets.data(), sizeof(int) * (size_t)(K + 1), ctx->stream,
                    ctx->covis_indices.data(), sizeof(int) * (size_t)total, ctx->dev_covis_csr + K + 1)) return 1;   // (no host wait: capi_internal.h)
   ctx->have_covisibility = true;
@@ -650,13 +642,7 @@ int bahip_set_covisibility(bahip_context* ctx, const int* offsets, const int* in
 int bahip_set_activation_window(bahip_context* ctx, const uint8_t* in_window, int num_keyframes) {
   REQUIRE(num_keyframes == ctx->num_kfs && (in_window != nullptr || num_keyframes == 0), "bahip_set_activation_window: one flag per bound keyframe");
   ctx->window.assign(in_window, in_window + (in_window ? num_keyframes : 0));
-  if ((size_t)num_keyframes > ctx->window_capacity) {
-    uint8_t* grown = nullptr;
-    HIP_TRY(hipMalloc(&grown, (size_t)num_keyframes + 256));
-    hipFree(ctx->dev_window);
-    ctx->dev_window = grown;
-    ctx->window_capacity = (size_t)num_keyframes + 256;
-  }
+  if ((size_t)num_keyframes > ctx->dev_window.size() && ctx->dev_window.reserve((size_t)num_keyframes, 256, "the activation window")) return 1;
   if (num_keyframes && stage_upload(&ctx->stage_window, ctx->dev_window, ctx->window.data(), (size_t)num_keyframes, ctx->stream)) return 1;
   return 0;
 }

@@ -28,7 +28,7 @@ int cost_eval(bahip_context* ctx, bool use_depth, bool use_desc, const KfEntry* 
               const bahip_surfels* surfels, std::vector<bahip_cost>* out) {
   static_assert(sizeof(bahip_cost) == 5 * sizeof(long long), "bahip_cost is resolved into 5 words");
   const size_t row_words = (size_t)num * kCostWords, words = row_words + kCostWords + 5 * ((size_t)num + 1);
-  if (grow_device(&ctx->dev_cost, &ctx->cost_capacity, words, 0, "the cost rows")) return 1;
+  if (ctx->dev_cost.reserve(words, 0, "the cost rows")) return 1;
   long long* rows = ctx->dev_cost;
   long long* total = rows + row_words;
   bahip_cost* resolved = reinterpret_cast<bahip_cost*>(total + kCostWords);

@@ -4,7 +4,15 @@
 using namespace bahip;
 using namespace bahip_capi;
 
+static const char* const kHookScratch = "the scratch of a test hook";
+
 extern "C" {
+int bahip_debug_live_allocations(long long* count_out, long long* bytes_out) {
+  if (count_out) *count_out = g_live_allocations.load();
+  if (bytes_out) *bytes_out = g_live_bytes.load();
+  return 0;
+}
+
 // ---- test hook ------------------------------------------------------------------------------------------------------
 int bahip_debug_evaluate_pairs(bahip_context* ctx, const bahip_frame* frame, const float frame_T_global[12],
                                const bahip_surfels* surfels, const uint32_t* surfel_indices_host, int count, float* out_host) {
@@ -13,29 +21,26 @@ int bahip_debug_evaluate_pairs(bahip_context* ctx, const bahip_frame* frame, con
   KfEntry e;
   if (make_entry(ctx, *frame, 0, &e)) return 1;
   memcpy(e.pose.F, frame_T_global, 12 * sizeof(float));
-  DevMem idx, out;
-  HIP_TRY(hipMalloc(&idx.p, sizeof(uint32_t) * count));
-  HIP_TRY(hipMalloc(&out.p, sizeof(float) * 40 * count));
-  HIP_TRY(hipMemcpy(idx.p, surfel_indices_host, sizeof(uint32_t) * count, hipMemcpyHostToDevice));
-  launch_evaluate_pairs(ctx->stream, ctx->in, e, make_view(surfels), idx.as<uint32_t>(), count, out.as<float>());
+  DeviceBuffer<uint32_t> idx; DeviceBuffer<float> out;
+  if (idx.reserve(count, 0, kHookScratch) || out.reserve(40 * (size_t)count, 0, kHookScratch)) return 1;
+  HIP_TRY(hipMemcpy(idx, surfel_indices_host, sizeof(uint32_t) * count, hipMemcpyHostToDevice));
+  launch_evaluate_pairs(ctx->stream, ctx->in, e, make_view(surfels), idx, count, out);
   CHECK_LAUNCH();
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  HIP_TRY(hipMemcpy(out_host, out.p, sizeof(float) * 40 * count, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_host, out, sizeof(float) * 40 * count, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int bahip_debug_exact_sum(bahip_context* ctx, const float* values_host, size_t count, int mode, double* out_host) {
   REQUIRE(out_host != nullptr && (values_host != nullptr || count == 0) && (mode == 0 || mode == 1), "bahip_debug_exact_sum: bad arguments");
-  DevMem values, cells, out;
-  HIP_TRY(hipMalloc(&values.p, sizeof(float) * (count ? count : 1)));
-  HIP_TRY(hipMalloc(&cells.p, sizeof(ExactCell) * pcg_exact_cells(0)));
-  HIP_TRY(hipMalloc(&out.p, sizeof(double)));
-  if (count) HIP_TRY(hipMemcpy(values.p, values_host, sizeof(float) * count, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemsetAsync(cells.p, 0, sizeof(ExactCell) * pcg_exact_cells(0), ctx->stream));
-  launch_exact_sum_debug(ctx->stream, pcg_exact_view(cells.p, 0), values.as<float>(), count, mode, out.as<double>());
+  DeviceBuffer<float> values; DeviceBuffer<ExactCell> cells; DeviceBuffer<double> out;
+  if (values.reserve(count ? count : 1, 0, kHookScratch) || cells.reserve(pcg_exact_cells(0), 0, kHookScratch) || out.reserve(1, 0, kHookScratch)) return 1;
+  if (count) HIP_TRY(hipMemcpy(values, values_host, sizeof(float) * count, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(cells, 0, sizeof(ExactCell) * pcg_exact_cells(0), ctx->stream));
+  launch_exact_sum_debug(ctx->stream, pcg_exact_view(cells, 0), values, count, mode, out);
   CHECK_LAUNCH();
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  HIP_TRY(hipMemcpy(out_host, out.p, sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_host, out, sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -131,114 +136,105 @@ int bahip_debug_geometry_hybrid_launches(long long* launches_out) { if (launches
 
 int bahip_debug_jacobian(bahip_context* ctx, int kind, const float* in, int n_in, float* out, int n_out) {
   REQUIRE(kind >= 0 && kind <= 4 && n_in > 0 && n_in <= 16 && n_out > 0 && n_out <= 8, "bahip_debug_jacobian: bad arguments");
-  DevMem d_in, d_out;
-  HIP_TRY(hipMalloc(&d_in.p, 16 * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_out.p, 8 * sizeof(float)));
-  HIP_TRY(hipMemcpyAsync(d_in.p, in, n_in * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  launch_jacobian_debug(ctx->stream, kind, d_in.as<float>(), d_out.as<float>());
+  DeviceBuffer<float> d_in, d_out;
+  if (d_in.reserve(16, 0, kHookScratch) || d_out.reserve(8, 0, kHookScratch)) return 1;
+  HIP_TRY(hipMemcpyAsync(d_in, in, n_in * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  launch_jacobian_debug(ctx->stream, kind, d_in, d_out);
   CHECK_LAUNCH();
-  HIP_TRY(hipMemcpyAsync(out, d_out.p, n_out * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 int bahip_debug_read_pattern(bahip_context* ctx, size_t bytes, int pattern, int repeats) {
   REQUIRE(bytes >= 4096 && (pattern == 0 || pattern == 1) && repeats >= 1, "bahip_debug_read_pattern: bad arguments");
-  uint32_t* buf = nullptr;
-  HIP_TRY(hipMalloc(&buf, bytes + 4));
-  hipError_t e = hipMemsetAsync(buf, 0, bytes + 4, ctx->stream);
-  for (int r = 0; r < repeats && e == hipSuccess; ++r) {
-    launch_read_pattern(ctx->stream, buf, bytes / 4, pattern, buf + bytes / 4);
-    e = hipGetLastError();
+  DeviceBuffer<void> buf;   // (bytes + 4: the last word takes the result)
+  if (buf.reserve(bytes + 4, 0, kHookScratch)) return 1;
+  uint32_t* words = static_cast<uint32_t*>(buf.get());
+  HIP_TRY(hipMemsetAsync(words, 0, bytes + 4, ctx->stream));
+  for (int r = 0; r < repeats; ++r) {
+    launch_read_pattern(ctx->stream, words, bytes / 4, pattern, words + bytes / 4);
+    CHECK_LAUNCH();
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(buf);
-  if (e != hipSuccess) return fail("bahip_debug_read_pattern", __FILE__, __LINE__, e);
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 int bahip_debug_exact_math(bahip_context* ctx, int kind, const float* in, float* out, size_t n) {
   REQUIRE(kind >= 0 && kind <= 5, "bahip_debug_exact_math: kind must be 0 (reciprocal), 1 (square root), 2 (sin), 3 (cos), 4 (atan) or 5 (exp)");
   if (n == 0) return 0;
-  float *d_in = nullptr, *d_out = nullptr;
-  HIP_TRY(hipMalloc(&d_in, n * sizeof(float)));
-  if (hipMalloc(&d_out, n * sizeof(float)) != hipSuccess) { hipFree(d_in); return fail("hipMalloc failed", __FILE__, __LINE__); }
-  hipError_t e = hipMemcpyAsync(d_in, in, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) { launch_exact_math_debug(ctx->stream, kind, d_in, d_out, n); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d_in); hipFree(d_out);
-  if (e != hipSuccess) return fail("bahip_debug_exact_math", __FILE__, __LINE__, e);
+  DeviceBuffer<float> d_in, d_out;
+  if (d_in.reserve(n, 0, kHookScratch) || d_out.reserve(n, 0, kHookScratch)) return 1;
+  HIP_TRY(hipMemcpyAsync(d_in, in, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  launch_exact_math_debug(ctx->stream, kind, d_in, d_out, n);
+  CHECK_LAUNCH();
+  HIP_TRY(hipMemcpyAsync(out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 int bahip_debug_pose_limbs(bahip_context* ctx, const float* values_host, size_t count, long long* out_host) {
   if (count == 0) return 0;
-  DevMem in, out;
-  HIP_TRY(hipMalloc(&in.p, sizeof(float) * count));
-  HIP_TRY(hipMalloc(&out.p, sizeof(long long) * 3 * count));
-  HIP_TRY(hipMemcpy(in.p, values_host, sizeof(float) * count, hipMemcpyHostToDevice));
-  launch_pose_limbs_debug(ctx->stream, in.as<float>(), out.as<long long>(), count);
+  DeviceBuffer<float> in; DeviceBuffer<long long> out;
+  if (in.reserve(count, 0, kHookScratch) || out.reserve(3 * count, 0, kHookScratch)) return 1;
+  HIP_TRY(hipMemcpy(in, values_host, sizeof(float) * count, hipMemcpyHostToDevice));
+  launch_pose_limbs_debug(ctx->stream, in, out, count);
   CHECK_LAUNCH();
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  HIP_TRY(hipMemcpy(out_host, out.p, sizeof(long long) * 3 * count, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_host, out, sizeof(long long) * 3 * count, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int bahip_debug_pose_step(bahip_context* ctx, const float* H21_b6, const float* global_T_frame, float* out_25) {
-  float *d_in = nullptr, *d_out = nullptr;
-  HIP_TRY(hipMalloc(&d_in, 34 * sizeof(float)));
-  if (hipMalloc(&d_out, 25 * sizeof(float)) != hipSuccess) { hipFree(d_in); return fail("hipMalloc failed", __FILE__, __LINE__); }
+  DeviceBuffer<float> d_in, d_out;
+  if (d_in.reserve(34, 0, kHookScratch) || d_out.reserve(25, 0, kHookScratch)) return 1;
   float in[34];
   memcpy(in, H21_b6, 27 * sizeof(float));
   memcpy(in + 27, global_T_frame, 7 * sizeof(float));
-  hipError_t e = hipMemcpyAsync(d_in, in, sizeof(in), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) { launch_pose_step_debug(ctx->stream, d_in, d_out); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipMemcpyAsync(out_25, d_out, 25 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(d_in); hipFree(d_out);
-  if (e != hipSuccess) return fail("bahip_debug_pose_step", __FILE__, __LINE__, e);
+  HIP_TRY(hipMemcpyAsync(d_in, in, sizeof(in), hipMemcpyHostToDevice, ctx->stream));
+  launch_pose_step_debug(ctx->stream, d_in, d_out);
+  CHECK_LAUNCH();
+  HIP_TRY(hipMemcpyAsync(out_25, d_out, 25 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 int bahip_debug_pose_step_damped(bahip_context* ctx, const float* H21_b6, const float* global_T_frame, float lambda, float* out_25) {
-  DevMem d_in, d_out;
-  HIP_TRY(hipMalloc(&d_in.p, 35 * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_out.p, 25 * sizeof(float)));
+  DeviceBuffer<float> d_in, d_out;
+  if (d_in.reserve(35, 0, kHookScratch) || d_out.reserve(25, 0, kHookScratch)) return 1;
   float in[35];
   memcpy(in, H21_b6, 27 * sizeof(float));
   memcpy(in + 27, global_T_frame, 7 * sizeof(float));
   in[34] = lambda;
-  HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(in), hipMemcpyHostToDevice, ctx->stream));
-  launch_pose_step_damped_debug(ctx->stream, d_in.as<float>(), d_out.as<float>());
+  HIP_TRY(hipMemcpyAsync(d_in, in, sizeof(in), hipMemcpyHostToDevice, ctx->stream));
+  launch_pose_step_damped_debug(ctx->stream, d_in, d_out);
   CHECK_LAUNCH();
-  HIP_TRY(hipMemcpyAsync(out_25, d_out.p, 25 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(out_25, d_out, 25 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 int bahip_debug_wave_reduce(bahip_context* ctx, const float* in_64x28, float* out_80) {
-  DevMem d_in, d_out;
-  HIP_TRY(hipMalloc(&d_in.p, 64 * 28 * sizeof(float)));
-  HIP_TRY(hipMalloc(&d_out.p, 80 * sizeof(float)));
-  HIP_TRY(hipMemcpyAsync(d_in.p, in_64x28, 64 * 28 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipMemsetAsync(d_out.p, 0xff, 80 * sizeof(float), ctx->stream));
-  launch_wave_reduce_debug(ctx->stream, d_in.as<float>(), d_out.as<float>());
+  DeviceBuffer<float> d_in, d_out;
+  if (d_in.reserve(64 * 28, 0, kHookScratch) || d_out.reserve(80, 0, kHookScratch)) return 1;
+  HIP_TRY(hipMemcpyAsync(d_in, in_64x28, 64 * 28 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemsetAsync(d_out, 0xff, 80 * sizeof(float), ctx->stream));
+  launch_wave_reduce_debug(ctx->stream, d_in, d_out);
   CHECK_LAUNCH();
-  HIP_TRY(hipMemcpyAsync(out_80, d_out.p, 80 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(out_80, d_out, 80 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 int bahip_debug_count_pairs(bahip_context* ctx, const bahip_surfels* surfels, uint64_t* counts_out) {
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
-  DevMem d;
-  HIP_TRY(hipMalloc(&d.p, 4 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(d.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
-  launch_count_pairs(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels), d.as<unsigned long long>());
+  DeviceBuffer<unsigned long long> d;
+  if (d.reserve(4, 0, kHookScratch)) return 1;
+  HIP_TRY(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  launch_count_pairs(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels), d);
   CHECK_LAUNCH();
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  HIP_TRY(hipMemcpy(counts_out, d.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(counts_out, d, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;
 }
 

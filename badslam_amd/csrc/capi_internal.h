@@ -9,6 +9,9 @@
 //   capi_cost.hip       the value of the BA objective (bahip_evaluate_cost, bahip_evaluate_frame_cost)
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
+// Ownership: every block of device or page-locked memory the boundary allocates for itself is a DeviceBuffer / PinnedBuffer
+// (capi_buffers.h) -- a member of bahip_context, of bahip_frame_planes or of an UploadStage, or a local of a test hook -- and is freed
+// with its owner; a unit grows one with reserve().  Only memory handed to the caller (bahip_malloc_pitch, bahip_host_alloc) is raw.
 #pragma once
 
 #include <dlfcn.h>
@@ -18,20 +21,20 @@
 
 #include <atomic>
 #include <chrono>
+#include <memory>
 #include <thread>
 
 #include <string>
 #include <vector>
 
 #include "ba_launch.h"
+#include "capi_buffers.h"
 #include "exact_sum.h"
 #include "ldlt.h"
 #include "se3_device.h"
 
 namespace bahip_capi {
 using namespace bahip;
-
-extern thread_local std::string g_last_error;   // bahip_last_error() (capi.hip)
 
 int fail(const char* what, const char* file, int line, hipError_t e = hipSuccess);   // sets the error text, returns 1
 
@@ -46,13 +49,6 @@ int fail(const char* what, const char* file, int line, hipError_t e = hipSuccess
   } while (0)
 #define CHECK_LAUNCH() HIP_TRY(hipGetLastError())
 
-// Scratch of the test hooks: freed on every return path.
-struct DevMem {
-  void* p = nullptr;
-  ~DevMem() { if (p) hipFree(p); }
-  template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-
 struct StageTimer {
   std::vector<hipEvent_t> ev;   // pairs (start, stop)
   std::vector<char> skip;       // per pair: not a launch that did work (queued ahead in vain): left out of sums and counts
@@ -62,14 +58,15 @@ struct StageTimer {
 
 
 }  // namespace bahip_capi
-using bahip_capi::DevMem;
+using bahip_capi::DeviceBuffer;
+using bahip_capi::PinnedBuffer;
+using bahip_capi::kHostVisible;
 using bahip_capi::StageTimer;
 using namespace bahip;
 
 // Tiled BA planes of one frame (ba_device.h).  Opaque to the C API.
 struct bahip_frame_planes {
-  uint32_t* geom = nullptr;
-  uint32_t* lumafp = nullptr;
+  DeviceBuffer<uint32_t> geom, lumafp;
   int width = 0, height = 0, cwidth = 0, cheight = 0;
 };
 
@@ -77,8 +74,7 @@ struct bahip_frame_planes {
 // hipMemcpyAsync; the event says when the buffer may be overwritten (checked -- normally long over -- by the next upload through the
 // same stage).  Scene binding used to synchronise the stream three times per BundleAdjustment call for its three tables.
 struct UploadStage {
-  void* pinned = nullptr;
-  size_t capacity = 0;
+  PinnedBuffer<char> pinned;
   hipEvent_t done = nullptr;
   bool pending = false;
 };
@@ -92,7 +88,7 @@ constexpr int kIntrMaxSlices = 16;   // slices of the intrinsics sweep (capi_sol
 struct bahip_context {
   UploadStage stage_kfs, stage_covis, stage_window;
   UploadStage stage_gather;        // bahip_gather_surfel_shards: the (size, count) table goes up and comes back through its page-locked buffer
-  long long* dev_gather_table = nullptr;   // ... and is summed here (kGatherTableWords int64, allocated once)
+  DeviceBuffer<long long> dev_gather_table;   // ... and is summed here (kGatherTableWords int64, allocated once)
   hipStream_t stream = nullptr;
   bool have_intrinsics = false;
   bahip_camera color_cam{}, depth_cam{};
@@ -100,90 +96,76 @@ struct bahip_context {
   Intrinsics in{};
 
   std::vector<KfEntry> host_kfs;
-  KfEntry* dev_kfs = nullptr;
-  int kfs_capacity = 0;
+  DeviceBuffer<KfEntry> dev_kfs;
   int num_kfs = 0;
 
-  PoseWork* dev_work = nullptr;
-  HbFixed* dev_Hb = nullptr;      // pose normal equations in fixed point (ba_device.h: HbFixed)
-  int work_capacity = 0;
-  KfEntry* dev_frame1 = nullptr;   // single-frame table for EstimateFramePose / AccumulatePoseEstimationCoeffs
-  PoseWork* dev_work1 = nullptr;
-  PoseWork* pinned_work1 = nullptr;
-  HbFixed* dev_Hb1 = nullptr;
-  uint32_t* dev_tile_counters = nullptr;   // persistent pose sweep: two sets of 8 tile counters (kernels_pose.hip)
+  DeviceBuffer<PoseWork> dev_work;
+  DeviceBuffer<HbFixed> dev_Hb;   // pose normal equations in fixed point (ba_device.h: HbFixed)
+  int work_capacity = 0;          // keyframes dev_work, dev_Hb and pinned_work are laid out for (ensure_work)
+  DeviceBuffer<KfEntry> dev_frame1;   // single-frame table for EstimateFramePose / AccumulatePoseEstimationCoeffs
+  DeviceBuffer<PoseWork> dev_work1;
+  PinnedBuffer<PoseWork> pinned_work1{kHostVisible};
+  DeviceBuffer<HbFixed> dev_Hb1;
+  DeviceBuffer<uint32_t> dev_tile_counters;   // persistent pose sweep: two sets of 8 tile counters (kernels_pose.hip)
   int pose_parity = 0;                     // the set the next persistent launch draws from
 
-  int* dev_counter = nullptr;      // [0] generic counter, [1..2] min/max depth bits
-  int* pinned_i = nullptr;         // 16 ints
-  float* pinned_f = nullptr;       // 128 floats
+  DeviceBuffer<int> dev_counter;   // [0] generic counter, [1..2] min/max depth bits
+  PinnedBuffer<int> pinned_i;      // 16 ints
+  PinnedBuffer<float> pinned_f;    // 128 floats
 
-  uint8_t* dev_flags = nullptr;    // W*H new-surfel flags
-  uint32_t* dev_indices = nullptr; // W*H scan output
-  size_t px_capacity = 0;
-  void* scan_temp = nullptr;
-  size_t scan_temp_bytes = 0;
-  int* dev_covis = nullptr;
-  float* dev_covis_T = nullptr;
-  int covis_capacity = 0;
+  DeviceBuffer<uint8_t> dev_flags;     // W*H new-surfel flags
+  DeviceBuffer<uint32_t> dev_indices;  // W*H scan output
+  DeviceBuffer<void> scan_temp;
+  DeviceBuffer<int> dev_covis;
+  DeviceBuffer<float> dev_covis_T;     // 12 floats per entry of dev_covis
   // co-visibility lists of the bound keyframes (CSR over bound indices), for the device-side activation state machine
   std::vector<int> covis_offsets, covis_indices;
-  int* dev_covis_csr = nullptr;    // offsets (K + 1) followed by the indices
-  size_t covis_csr_capacity = 0;
+  DeviceBuffer<int> dev_covis_csr; // offsets (K + 1) followed by the indices
   bool capacity_exceeded = false;  // last bahip_create_surfels_for_keyframe did not fit (bahip_context_take_capacity_exceeded)
   bool have_covisibility = false;
   std::vector<uint8_t> window;     // per bound keyframe: inside the fixed active window (bahip_set_activation_window)
-  uint8_t* dev_window = nullptr;
-  size_t window_capacity = 0;
-  PoseWork* pinned_work = nullptr;   // read-back of the pose work items + their counter records (page-locked)
+  DeviceBuffer<uint8_t> dev_window;
+  PinnedBuffer<PoseWork> pinned_work{kHostVisible};   // read-back of the pose work items + their counter records (page-locked)
   // a creation batch as a chain of one launch per keyframe (bahip_create_surfels_for_keyframes; kernels_lifecycle.hip: create_chain_kernel):
   // per keyframe of the batch the bytes "cell occupied" and "pixel would create a surfel", and the batch's item table
-  void* dev_merge_batch = nullptr;    // bahip_merge_surfels_for_keyframes by cell lists: frame table, counts, offsets, pair cells, members, scan temporary
-  size_t merge_batch_bytes = 0;
-  void* dev_sort_scratch = nullptr;   // bahip_sort_surfels_spatially: keys, indices, a dense copy of the data rows, the library's temporary
-  size_t sort_scratch_bytes = 0;
-  void* dev_create_batch = nullptr;   // occupancy, candidates, their scan, the compact candidate list with its records, the item table
-  size_t create_batch_bytes = 0;
-  uint32_t* merge_planes[BAHIP_MERGE_BUFFER_COUNT] = {};   // the second set of supporting planes of a pipelined merge batch (bahip_merge_surfels_for_keyframes)
-  size_t merge_planes_bytes = 0;
+  DeviceBuffer<void> dev_merge_batch;    // bahip_merge_surfels_for_keyframes by cell lists: frame table, counts, offsets, pair cells, members, scan temporary
+  DeviceBuffer<void> dev_sort_scratch;   // bahip_sort_surfels_spatially: keys, indices, a dense copy of the data rows, the library's temporary
+  DeviceBuffer<void> dev_create_batch;   // occupancy, candidates, their scan, the compact candidate list with its records, the item table
+  DeviceBuffer<uint32_t> merge_planes[BAHIP_MERGE_BUFFER_COUNT];   // the second set of supporting planes of a pipelined merge batch (bahip_merge_surfels_for_keyframes)
   const void* supporting_planes_empty = nullptr;   // the supporting planes (by their first plane) that the last merge call left empty
   bool row_major_creation = false;   // new surfels of a keyframe appended in row-major pixel order (the reference's) instead of tile-major
   bool poll_disabled = false;        // the host copy of the pose counters is not updated by the kernel on this system: synchronise instead
   // lifecycle batch (bahip_lifecycle_batch_begin): bounding spheres of the cloud's whole tiles, for the per-keyframe sweeps of a batch
-  void* dev_lifecycle_bounds = nullptr;
+  DeviceBuffer<void> dev_lifecycle_bounds;
   size_t lifecycle_bounds_capacity = 0;   // tiles
   uint32_t lifecycle_bounds_tiles = 0;    // 0: no batch open
   const void* lifecycle_bounds_data = nullptr;   // the surfel buffer they describe
   // ... and, when the batch knows its frames (bahip_lifecycle_batch_set_frames), which of those tiles each frame can see
   std::vector<float> lifecycle_frames;           // 12 floats per frame: frame_T_global as given
   std::vector<uint32_t> lifecycle_list_offsets, lifecycle_list_counts;
-  float* dev_lifecycle_frames = nullptr;
-  uint32_t* dev_lifecycle_cursors = nullptr;     // [2 * capacity]: cursors, offsets
-  size_t lifecycle_frames_capacity = 0;
-  uint32_t* dev_lifecycle_lists = nullptr;
-  size_t lifecycle_lists_capacity = 0;
-  void* dev_tile_bounds = nullptr;   // bounding sphere per 64-surfel tile, written by the first pose round of a phase
-  size_t tile_bounds_bytes = 0;
+  DeviceBuffer<float> dev_lifecycle_frames;
+  DeviceBuffer<uint32_t> dev_lifecycle_cursors;  // [2 * frames]: cursors, offsets
+  DeviceBuffer<uint32_t> dev_lifecycle_lists;
+  DeviceBuffer<void> dev_tile_bounds;   // bounding sphere per 64-surfel tile, written by the first pose round of a phase
   // heavy work first (wave_cull.h: scheduled_tile): candidates per tile counted by the first pose round of a phase over the
   // keyframe table (or by the PCG init sweep), and the schedule built from them, valid for grids of tile_order_tiles (padded)
   // tiles (0: none yet)
-  uint32_t* dev_tile_cost = nullptr;
-  uint32_t* dev_tile_order = nullptr;
+  DeviceBuffer<uint32_t> dev_tile_cost, dev_tile_order;
   size_t tile_schedule_capacity = 0;   // tiles
   uint32_t tile_order_tiles = 0;
   int phases_since_schedule = 0;       // the schedule is rebuilt when the grid changes and every kSchedulePhases-th phase
   uint32_t tile_order_unavailable_tiles = 0;   // a grid the order kernel cannot schedule (too many runs): no census for it again
   bool tile_order_unavailable_for(uint32_t padded_tiles) const { return padded_tiles != 0 && tile_order_unavailable_tiles == padded_tiles; }
-  int* dev_loop_ctl = nullptr;     // device-driven BA loop (bahip_alternating_iterations): kLoopWords control words ...
-  int* host_loop_ctl = nullptr;    // ... their mapped host copy, followed by kLoopLogSlots words of per-round log
+  DeviceBuffer<int> dev_loop_ctl;  // device-driven BA loop (bahip_alternating_iterations): kLoopWords control words ...
+  PinnedBuffer<int> host_loop_ctl{kHostVisible};   // ... their mapped host copy, followed by kLoopLogSlots words of per-round log
   int rounds_hint_table = 1, rounds_hint_frame = 1;   // Gauss-Newton rounds the previous pose phase took (keyframe table / single frame)
 
-  float* intr_scratch = nullptr;   // intrinsics step: (64 + 8 S) doubles, then (64 + 8 S) floats + Schur partials
+  DeviceBuffer<void> intr_scratch; // intrinsics step: (64 + 8 S) doubles, then (64 + 8 S) floats + Schur partials
   int intr_capacity = 0;
   // append buffers of the intrinsics sweep's per-cell records (ba_launch.h: IntrBins), sized from the previous call's counts
-  uint32_t* intr_bin_cursors = nullptr;   // device, intr_bin_count words
-  uint32_t* intr_bin_records = nullptr;
-  uint32_t* intr_bin_counts_host = nullptr;   // pinned copy of the cursors after the sweep
+  DeviceBuffer<uint32_t> intr_bin_cursors;   // device, intr_bin_count words
+  DeviceBuffer<uint32_t> intr_bin_records;
+  PinnedBuffer<uint32_t> intr_bin_counts_host;   // pinned copy of the cursors after the sweep
   int intr_bin_count = 0;
   int intr_bin_sets = 0;                  // buffer sets allocated: 2 when the sweep runs in slices (one is reduced while the other fills)
   int intr_bin_rows = 0;                  // rows of counts (one per slice) the last call left in intr_bin_counts_host
@@ -195,22 +177,18 @@ struct bahip_context {
   int intr_bin_forced = -1;
   int intr_bin_last_overflow = 0;         // did the last call have records that did not fit?               // bahip_debug_set_intrinsics_bin_capacity: >= 0 fixes the capacity (0: no binning)
 
-  float* pcg_buf = nullptr;        // PCG vectors r, M, delta, g, p (5 * pcg_capacity floats) + 16 scalars
+  DeviceBuffer<float> pcg_buf;     // PCG vectors r, M, delta, g, p (5 * pcg_capacity floats) + 16 scalars
   size_t pcg_capacity = 0;
-  void* pcg_exact = nullptr;       // exact accumulators of the PCG solve (ExactCell[pcg_exact_capacity]; kernels_pcg.hip)
-  uint32_t* pcg_window = nullptr;  // windowed PCG (kernels_pcg_window.hip): [tile count | keyframe list | pose indices | tile list]
-  size_t pcg_window_capacity = 0;  // words
+  DeviceBuffer<ExactCell> pcg_exact;   // exact accumulators of the PCG solve (kernels_pcg.hip)
+  DeviceBuffer<uint32_t> pcg_window;   // windowed PCG (kernels_pcg_window.hip): [tile count | keyframe list | pose indices | tile list]
   uint32_t pcg_window_last_tiles = 0;   // tiles and swept keyframes of the last windowed call (bahip_pcg_window_size)
   int pcg_window_last_kfs = 0;
-  size_t pcg_exact_capacity = 0;
-  void* pcg_stage_ctl = nullptr;   // stage API (bahip_pcg_begin ...): a control block that never stops, the head size the
+  DeviceBuffer<void> pcg_stage_ctl;   // stage API (bahip_pcg_begin ...): a control block that never stops, the head size the
   uint32_t pcg_stage_head = 0;     // accumulators were set up for, and the bahip_pcg_step1 calls since the last step 2
   int pcg_stage_step1_calls = 0;
   float pcg_damping = 0.f;         // lambda of the damped PCG system (bahip_context_set_pcg_damping; kernels_pcg_trial.hip)
-  uint32_t* pcg_trial = nullptr;   // bahip_pcg_iteration_controlled: [tile count | tile list] followed by the snapshot
-  size_t pcg_trial_capacity = 0;   // words
-  long long* pose_trial = nullptr; // bahip_estimate_keyframe_poses_controlled: [Hb | cost rows] (what the ranks exchange), records, lambdas, lists, control words
-  size_t pose_trial_capacity = 0;  // int64 words
+  DeviceBuffer<uint32_t> pcg_trial;    // bahip_pcg_iteration_controlled: [tile count | tile list] followed by the snapshot
+  DeviceBuffer<long long> pose_trial;  // bahip_estimate_keyframe_poses_controlled: [Hb | cost rows] (what the ranks exchange), records, lambdas, lists, control words
   int world = 0;                   // ranks of the RCCL communicator (0 = none)
   int kf_rank = 0, kf_world = 1;   // keyframe sharding (bahip_context_set_keyframe_sharding): keyframe k lives on rank k % kf_world (1, 2, 4 or 8)
   int arithmetic = 0;              // BAHIP_ARITHMETIC_EXACT / _FAST: flavour of the sweeps (bahip_context_set_arithmetic), mirrored in in.fast_math
@@ -218,10 +196,8 @@ struct bahip_context {
   int intrinsics_sum_classes = 1;  // keyframe classes of the intrinsics step's global sums: 1, 2, 4 or 8 (bahip_context_set_intrinsics_sum_classes)
   int pcg_sum_classes = 1;         // keyframe classes of the surfel block of the PCG scheme's r, M and g: 1, 2, 4 or 8 (bahip_context_set_pcg_sum_classes)
   int intr_sums_cells = -1;        // sparse cells of the accumulators the last intrinsics step left in intr_scratch (-1: none; bahip_debug_read_intrinsics_sums)
-  float* kf_partials = nullptr;    // class partials of the geometry step (normals, then position) / hit words of the activation
-  size_t kf_partials_capacity = 0; // floats
-  long long* dev_cost = nullptr;   // rows of the cost sweep (kernels_cost.hip): kCostWords int64 per keyframe
-  size_t cost_capacity = 0;        // int64 words
+  DeviceBuffer<float> kf_partials; // class partials of the geometry step (normals, then position) / hit words of the activation
+  DeviceBuffer<long long> dev_cost;   // rows of the cost sweep (kernels_cost.hip): kCostWords int64 per keyframe
   // dealing the lifecycle under surfel sharding (bahip_context_set_lifecycle_dealing): the switch, and the surfel partition of the
   // whole-cloud phase in progress -- set by bahip_gather_surfel_shards, cleared by bahip_extract_surfel_shard (deal_world 1: none) --
   // with the gathered cloud it belongs to: lifecycle calls on any other buffer are not dealt
@@ -235,10 +211,10 @@ struct bahip_context {
 
   // planes packed by the library itself for frames handed over without bahip_frame.planes:
   // slot 0 = the single frame of the per-frame entry points, slot 1 + k = bound keyframe k
-  std::vector<bahip_frame_planes*> auto_planes;
+  std::vector<std::unique_ptr<bahip_frame_planes>> auto_planes;
   // and for frame j of a merge batch by cell lists (at most 64 frames): a pool of its own, so that a batch in any order never
   // writes into the planes a bound keyframe's table entry points at
-  std::vector<bahip_frame_planes*> batch_planes;
+  std::vector<std::unique_ptr<bahip_frame_planes>> batch_planes;
 
   bahip_allreduce_fn allreduce = nullptr;
   void* allreduce_user = nullptr;
@@ -260,22 +236,6 @@ KfEntry raw_entry(const bahip_frame& f);
 int make_entry(bahip_context* ctx, const bahip_frame& f, size_t slot, KfEntry* out);
 int make_batch_entry(bahip_context* ctx, const bahip_frame& f, size_t j, KfEntry* out);
 SurfelsView make_view(const bahip_surfels* s);
-template <typename T>
-int grow_device(T** ptr, size_t* capacity, size_t need, size_t slack, const char* what) {
-  if (need <= *capacity && *ptr) return 0;
-  T* grown = nullptr;
-  const size_t cap = need + slack;
-  if (hipMalloc(&grown, sizeof(T) * cap) != hipSuccess) {
-    char buf[160];
-    snprintf(buf, sizeof(buf), "hipMalloc of %zu bytes for %s failed", sizeof(T) * cap, what);
-    g_last_error = buf;
-    return 1;
-  }
-  hipFree(*ptr);
-  *ptr = grown;
-  *capacity = cap;
-  return 0;
-}
 int ensure_work(bahip_context* ctx, int n);
 int ensure_px(bahip_context* ctx, size_t px, size_t scan_n);
 inline bool timer_on(const bahip_context* ctx, int stage) { return ctx->profiling && (ctx->profiling != 3 || stage == 2); }

@@ -76,7 +76,7 @@ static int determine_supporting_impl(bahip_context* ctx, int merge, float merge_
     uint32_t* cell_of = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)(kSurfelAccum0 + 1) * surfels->pitch_bytes);
     if (merged_count_out) {
       HIP_TRY(hipMemsetAsync(ctx->dev_counter, 0, sizeof(int), ctx->stream));
-      launch_merge(ctx->stream, ctx->in, e, s, sup, cell_merge_dist_sq, kCosNormalCompat, flags, cell_of, backend_owns_planes, reinterpret_cast<uint32_t*>(ctx->dev_counter), cull);
+      launch_merge(ctx->stream, ctx->in, e, s, sup, cell_merge_dist_sq, kCosNormalCompat, flags, cell_of, backend_owns_planes, reinterpret_cast<uint32_t*>(ctx->dev_counter.get()), cull);
       CHECK_LAUNCH();
       HIP_TRY(hipMemcpyAsync(ctx->pinned_i, ctx->dev_counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -84,7 +84,7 @@ static int determine_supporting_impl(bahip_context* ctx, int merge, float merge_
     } else {
       // deferred count: a batch of keyframes merges without a read-back and a stream synchronisation per keyframe; the total
       // waits in dev_counter[3] for bahip_take_merged_count
-      launch_merge(ctx->stream, ctx->in, e, s, sup, cell_merge_dist_sq, kCosNormalCompat, flags, cell_of, backend_owns_planes, reinterpret_cast<uint32_t*>(ctx->dev_counter) + 3, cull);
+      launch_merge(ctx->stream, ctx->in, e, s, sup, cell_merge_dist_sq, kCosNormalCompat, flags, cell_of, backend_owns_planes, reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 3, cull);
       CHECK_LAUNCH();
     }
     if (backend_owns_planes) ctx->supporting_planes_empty = sup.b[0];
@@ -113,6 +113,24 @@ static int kf_exchange(bahip_context* ctx, void* buffer, size_t bytes, const cha
     return fail((std::string("keyframe sharding: the exchange of ") + what + " failed: " + g_last_error).c_str(), __FILE__, __LINE__);
   return 0;
 }
+
+// The scratch of the outlier filter of a creation call: `n` co-visible keyframe indices and their 3x4 transforms (both or neither).
+static int ensure_covis(bahip_context* ctx, int n) {
+  if ((size_t)n <= ctx->dev_covis.size()) return 0;
+  DeviceBuffer<int> idx; DeviceBuffer<float> T;
+  const size_t cap = (size_t)n + 64;
+  if (idx.reserve(cap, 0, "the co-visibility indices") || T.reserve(12 * cap, 0, "the co-visibility transforms"))
+    return fail("allocation of the co-visibility scratch failed", __FILE__, __LINE__);
+  ctx->dev_covis = std::move(idx); ctx->dev_covis_T = std::move(T);
+  return 0;
+}
+
+// The one block a creation batch lays its tables out in (up to 16 GB: the old block goes before the new one comes).
+static int ensure_create_batch(bahip_context* ctx, size_t need) {
+  if (need <= ctx->dev_create_batch.size()) return 0;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return ctx->dev_create_batch.reserve(need, need / 4, "the tables of a creation batch", true);
+}
 #define REQUIRE_KF_TRANSPORT() \
   REQUIRE(!kf_sharded(ctx) || is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator")
 
@@ -139,13 +157,11 @@ static int merge_by_cell_lists(bahip_context* ctx, const std::vector<MergeBatchF
                word_bytes = align(sizeof(uint32_t) * sweep), first_bytes = align(sizeof(uint32_t) * ((size_t)num_frames + 1)),
                temp_bytes = align(merge_batch_scan_temp_bytes(entries));
   const size_t need = table_bytes + 2 * entry_bytes + 3 * word_bytes + 2 * word_bytes + first_bytes + temp_bytes;
-  if (need > ctx->merge_batch_bytes) {
+  if (need > ctx->dev_merge_batch.size()) {
     HIP_TRY(hipStreamSynchronize(st));
-    hipFree(ctx->dev_merge_batch); ctx->dev_merge_batch = nullptr; ctx->merge_batch_bytes = 0;
-    HIP_TRY(hipMalloc(&ctx->dev_merge_batch, need + need / 4));
-    ctx->merge_batch_bytes = need + need / 4;
+    if (ctx->dev_merge_batch.reserve(need, need / 4, "the cell lists of a merge batch", true)) return 1;
   }
-  char* p = static_cast<char*>(ctx->dev_merge_batch);
+  char* p = static_cast<char*>(ctx->dev_merge_batch.get());
   MergeBatchFrame* dev_table = reinterpret_cast<MergeBatchFrame*>(p); p += table_bytes;
   uint32_t* counts = reinterpret_cast<uint32_t*>(p); p += entry_bytes;
   uint32_t* offsets = reinterpret_cast<uint32_t*>(p); p += entry_bytes;
@@ -194,7 +210,7 @@ static int merge_by_cell_lists(bahip_context* ctx, const std::vector<MergeBatchF
   }
   const float cell = (float)ctx->in.cell;
   const float cell_merge_dist_sq = cell * cell * merge_dist_factor * merge_dist_factor;
-  uint32_t* counter = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 3;   // the deferred count of bahip_take_merged_count
+  uint32_t* counter = reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 3;   // the deferred count of bahip_take_merged_count
   for (int j = 0; j < num_frames; ++j) {
     launch_merge_pairs(st, s, members, member_cell, first[(size_t)j], first[(size_t)j + 1], (uint32_t)j, deleted_at, cell_merge_dist_sq,
                        kCosNormalCompat);
@@ -218,15 +234,8 @@ static int merge_pipelined(bahip_context* ctx, int num_frames, const std::functi
   hipStream_t st = ctx->stream;
   // the second set of planes: same pitch, the sparse-cell region's rows
   const size_t plane_bytes = (size_t)supporting_pitch * (size_t)ctx->in.cf_height;
-  if (plane_bytes > ctx->merge_planes_bytes) {
-    for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) {
-      hipFree(ctx->merge_planes[b]);
-      ctx->merge_planes[b] = nullptr;
-    }
-    ctx->merge_planes_bytes = 0;
-    for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) HIP_TRY(hipMalloc(&ctx->merge_planes[b], plane_bytes));
-    ctx->merge_planes_bytes = plane_bytes;
-  }
+  for (auto& plane : ctx->merge_planes)
+    if (plane.reserve((plane_bytes + 3) / 4, 0, "the second set of supporting planes", true)) return 1;
   for (int b = 0; b < BAHIP_MERGE_BUFFER_COUNT; ++b) sup[1].b[b] = ctx->merge_planes[b];
   sup[1].pitch = supporting_pitch;
   if (ctx->supporting_planes_empty != sup[0].b[0]) launch_supporting_fill(st, sup[0], ctx->in.cf_width, ctx->in.cf_height);
@@ -239,7 +248,7 @@ static int merge_pipelined(bahip_context* ctx, int num_frames, const std::functi
   uint32_t* flags = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)kSurfelAccum0 * surfels->pitch_bytes);
   uint32_t* cell_of = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(surfels->data) + (size_t)(kSurfelAccum0 + 1) * surfels->pitch_bytes);
   HIP_TRY(hipMemsetAsync(flags, 0, sizeof(uint32_t) * (size_t)surfels->surfels_size, st));
-  uint32_t* counter = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 3;   // the deferred count of bahip_take_merged_count
+  uint32_t* counter = reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 3;   // the deferred count of bahip_take_merged_count
   const SurfelsView s = make_view(surfels);
   std::vector<KfEntry> entries((size_t)num_frames);
   std::vector<LifecycleCull> culls((size_t)num_frames);
@@ -386,11 +395,8 @@ int bahip_lifecycle_batch_begin(bahip_context* ctx, const bahip_surfels* surfels
   const uint32_t tiles = surfels->surfels_size / 64;   // whole tiles only: what is appended later starts in the tile behind them
   if (tiles == 0) return 0;
   if (tiles > ctx->lifecycle_bounds_capacity) {
-    void* grown = nullptr;
     const size_t capacity = (size_t)tiles + tiles / 4 + 1024;
-    HIP_TRY(hipMalloc(&grown, capacity * 16));   // WaveBounds: four floats
-    hipFree(ctx->dev_lifecycle_bounds);
-    ctx->dev_lifecycle_bounds = grown;
+    if (ctx->dev_lifecycle_bounds.reserve(capacity * 16, 0, "the tile bounds of a lifecycle batch")) return 1;   // WaveBounds: four floats
     ctx->lifecycle_bounds_capacity = capacity;
   }
   launch_lifecycle_bounds(ctx->stream, make_view(surfels), tiles, ctx->dev_lifecycle_bounds);
@@ -407,28 +413,19 @@ int bahip_lifecycle_batch_set_frames(bahip_context* ctx, const float* frame_T_gl
   const uint32_t tiles = ctx->lifecycle_bounds_tiles;
   if (tiles == 0 || num_frames == 0) return 0;   // no batch open (or an empty cloud): the sweeps take everything
   hipStream_t st = ctx->stream;
-  if ((size_t)num_frames > ctx->lifecycle_frames_capacity) {
-    float* F = nullptr; uint32_t* cursors = nullptr;
+  if (2 * (size_t)num_frames > ctx->dev_lifecycle_cursors.size()) {   // (frames and cursors grow together: two cursor words per frame)
+    DeviceBuffer<float> F; DeviceBuffer<uint32_t> cursors;
     const size_t capacity = (size_t)num_frames + 64;
-    if (hipMalloc(&F, capacity * 12 * sizeof(float)) != hipSuccess || hipMalloc(&cursors, 2 * capacity * sizeof(uint32_t)) != hipSuccess) {
-      hipFree(F); hipFree(cursors);
+    if (F.reserve(capacity * 12, 0, "the lifecycle batch's frames") || cursors.reserve(2 * capacity, 0, "the lifecycle batch's cursors"))
       return fail("allocation of the lifecycle batch's frame table failed", __FILE__, __LINE__);
-    }
-    hipFree(ctx->dev_lifecycle_frames); hipFree(ctx->dev_lifecycle_cursors);
-    ctx->dev_lifecycle_frames = F; ctx->dev_lifecycle_cursors = cursors;
-    ctx->lifecycle_frames_capacity = capacity;
+    ctx->dev_lifecycle_frames = std::move(F); ctx->dev_lifecycle_cursors = std::move(cursors);
   }
   uint32_t* cursors = ctx->dev_lifecycle_cursors;
   std::vector<uint32_t> counts(num_frames), starts(num_frames);
   const size_t total = (size_t)num_frames * tiles;   // room for every tile in every frame's list: one pass, no counting pass, one host wait
-  if (total > ctx->lifecycle_lists_capacity) {
-    uint32_t* lists = nullptr;
-    const size_t capacity = total + total / 4 + 4096;
+  if (total > ctx->dev_lifecycle_lists.size()) {
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMalloc(&lists, capacity * sizeof(uint32_t)));
-    hipFree(ctx->dev_lifecycle_lists);
-    ctx->dev_lifecycle_lists = lists;
-    ctx->lifecycle_lists_capacity = capacity;
+    if (ctx->dev_lifecycle_lists.reserve(total, total / 4 + 4096, "the lifecycle batch's tile lists")) return 1;
   }
   HIP_TRY(hipMemcpyAsync(ctx->dev_lifecycle_frames, frame_T_global_3x4, (size_t)num_frames * 12 * sizeof(float), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(cursors, 0, (size_t)num_frames * sizeof(uint32_t), st));
@@ -485,17 +482,7 @@ int bahip_create_surfels_for_keyframe(bahip_context* ctx, int keyframe_index, in
   launch_create_flag(ctx->stream, ctx->in, e, sup, ctx->dev_flags);
   CHECK_LAUNCH();
   if (filter_new_surfels && n_covis > 0) {
-    if (n_covis > ctx->covis_capacity) {
-      int* idx = nullptr; float* T = nullptr;
-      const int cap = n_covis + 64;
-      if (hipMalloc(&idx, sizeof(int) * cap) != hipSuccess || hipMalloc(&T, sizeof(float) * 12 * cap) != hipSuccess) {
-        hipFree(idx); hipFree(T);
-        return fail("allocation of the co-visibility scratch failed", __FILE__, __LINE__);
-      }
-      hipFree(ctx->dev_covis); hipFree(ctx->dev_covis_T);
-      ctx->dev_covis = idx; ctx->dev_covis_T = T;
-      ctx->covis_capacity = cap;
-    }
+    if (ensure_covis(ctx, n_covis)) return 1;
     std::vector<float> rel(12 * (size_t)n_covis);
     for (int c = 0; c < n_covis; ++c) {
       REQUIRE(covis[c] >= 0 && covis[c] < ctx->num_kfs, "co-visibility index out of range");
@@ -515,7 +502,7 @@ int bahip_create_surfels_for_keyframe(bahip_context* ctx, int keyframe_index, in
     // no co-visible keyframe: every candidate has exactly one observation
     if (1 < min_observation_count) HIP_TRY(hipMemsetAsync(ctx->dev_flags, 0, px, ctx->stream));
   }
-  HIP_TRY(scan_flags_inclusive(ctx->stream, ctx->scan_temp, ctx->scan_temp_bytes, ctx->dev_flags, ctx->dev_indices, (int)px));
+  HIP_TRY(scan_flags_inclusive(ctx->stream, ctx->scan_temp, ctx->scan_temp.size(), ctx->dev_flags, ctx->dev_indices, (int)px));
   HIP_TRY(hipMemcpyAsync(ctx->pinned_i, ctx->dev_indices + (px - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   const uint32_t count = (uint32_t)ctx->pinned_i[0];
@@ -581,13 +568,8 @@ static int create_batch_keyframe_sharded(bahip_context* ctx, const int* keyframe
                       align(scan_temp_bytes);
   REQUIRE(need <= ((size_t)16 << 30) && sizeof(float) * columns * (kSurfelAccum0 + 1) < ((size_t)1 << 32) && N * px < ((size_t)1 << 31),
           "keyframe sharding: the creation batch is too large for one pass: split it");
-  if (need > ctx->create_batch_bytes) {
-    HIP_TRY(hipStreamSynchronize(st));
-    hipFree(ctx->dev_create_batch); ctx->dev_create_batch = nullptr; ctx->create_batch_bytes = 0;
-    HIP_TRY(hipMalloc(&ctx->dev_create_batch, need + need / 4));
-    ctx->create_batch_bytes = need + need / 4;
-  }
-  char* p = static_cast<char*>(ctx->dev_create_batch);
+  if (ensure_create_batch(ctx, need)) return 1;
+  char* p = static_cast<char*>(ctx->dev_create_batch.get());
   uint8_t* occupancy = reinterpret_cast<uint8_t*>(p); p += occupancy_bytes;
   uint8_t* candidates = reinterpret_cast<uint8_t*>(p); p += candidates_bytes;
   uint32_t* cand_px = reinterpret_cast<uint32_t*>(p); p += cand_px_bytes;
@@ -640,8 +622,8 @@ static int create_batch_keyframe_sharded(bahip_context* ctx, const int* keyframe
     if (kf_exchange(ctx, cand_cell, sizeof(uint32_t) * total_al * (kSurfelAccum0 + 1), "the creation batch's records")) return 1;
   }
   // ---- the chain, keyframe by keyframe (the size cells and the appends' scratch as bahip_create_surfels_for_keyframes sets them up)
-  uint32_t* size_cell[2] = {reinterpret_cast<uint32_t*>(ctx->dev_counter) + 4, reinterpret_cast<uint32_t*>(ctx->dev_counter) + 5};
-  uint32_t* exceeded_on_device = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 6;
+  uint32_t* size_cell[2] = {reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 4, reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 5};
+  uint32_t* exceeded_on_device = reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 6;
   ctx->pinned_i[2] = (int)surfels->surfels_size; ctx->pinned_i[3] = (int)surfels->surfels_size; ctx->pinned_i[4] = 0;
   HIP_TRY(hipMemcpyAsync(size_cell[0], ctx->pinned_i + 2, 3 * sizeof(int), hipMemcpyHostToDevice, st));
   const int groups = create_append_groups();
@@ -714,13 +696,8 @@ static int create_upfront_dealt(bahip_context* ctx, const std::vector<CreateBatc
   const size_t need = occupancy_bytes + candidates_bytes + cand_px_bytes + counts_bytes + scan_bytes + list_bytes + items_bytes + align(2 * sizeof(uint32_t)) +
                       align(scan_temp_bytes);
   if (!(need <= ((size_t)16 << 30) && sizeof(float) * columns * (kSurfelAccum0 + 1) < ((size_t)1 << 32) && N * px < ((size_t)1 << 31))) return 0;
-  if (need > ctx->create_batch_bytes) {
-    HIP_TRY(hipStreamSynchronize(st));
-    hipFree(ctx->dev_create_batch); ctx->dev_create_batch = nullptr; ctx->create_batch_bytes = 0;
-    HIP_TRY(hipMalloc(&ctx->dev_create_batch, need + need / 4));
-    ctx->create_batch_bytes = need + need / 4;
-  }
-  char* p = static_cast<char*>(ctx->dev_create_batch);
+  if (ensure_create_batch(ctx, need)) return 1;
+  char* p = static_cast<char*>(ctx->dev_create_batch.get());
   uint8_t* occupancy = reinterpret_cast<uint8_t*>(p); p += occupancy_bytes;
   uint8_t* candidates = reinterpret_cast<uint8_t*>(p); p += candidates_bytes;
   uint32_t* cand_px = reinterpret_cast<uint32_t*>(p); p += cand_px_bytes;
@@ -809,17 +786,7 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
   if (ensure_px(ctx, px, px > surfels->capacity ? px : surfels->capacity)) return 1;
   hipStream_t st = ctx->stream;
   if (filter_new_surfels && total_covis > 0) {
-    if (total_covis > ctx->covis_capacity) {
-      int* idx = nullptr; float* T = nullptr;
-      const int cap = total_covis + 64;
-      if (hipMalloc(&idx, sizeof(int) * cap) != hipSuccess || hipMalloc(&T, sizeof(float) * 12 * cap) != hipSuccess) {
-        hipFree(idx); hipFree(T);
-        return fail("allocation of the co-visibility scratch failed", __FILE__, __LINE__);
-      }
-      hipFree(ctx->dev_covis); hipFree(ctx->dev_covis_T);
-      ctx->dev_covis = idx; ctx->dev_covis_T = T;
-      ctx->covis_capacity = cap;
-    }
+    if (ensure_covis(ctx, total_covis)) return 1;
     std::vector<float> rel(12 * (size_t)total_covis);
     for (int j = 0; j < num_keyframes; ++j) {
       const KfEntry& e = ctx->host_kfs[keyframe_indices[j]];
@@ -841,8 +808,8 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
                                          min_observation_count, covis_offsets, surfels, sup, new_surfel_count_out);
   // The cloud's size lives on the device between the keyframes of the batch, in TWO cells: a keyframe's launches read one, its append
   // writes the other (kernels_lifecycle.hip: create_append_fused_kernel); [6] = the sticky "capacity exceeded" flag.
-  uint32_t* size_cell[2] = {reinterpret_cast<uint32_t*>(ctx->dev_counter) + 4, reinterpret_cast<uint32_t*>(ctx->dev_counter) + 5};
-  uint32_t* exceeded_on_device = reinterpret_cast<uint32_t*>(ctx->dev_counter) + 6;
+  uint32_t* size_cell[2] = {reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 4, reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 5};
+  uint32_t* exceeded_on_device = reinterpret_cast<uint32_t*>(ctx->dev_counter.get()) + 6;
   ctx->pinned_i[2] = (int)surfels->surfels_size; ctx->pinned_i[3] = (int)surfels->surfels_size; ctx->pinned_i[4] = 0;
   HIP_TRY(hipMemcpyAsync(size_cell[0], ctx->pinned_i + 2, 3 * sizeof(int), hipMemcpyHostToDevice, st));
   // scratch of the fused appends in the (otherwise unused) index vector: one tagged word per slice of the flag sequence
@@ -897,13 +864,8 @@ int bahip_create_surfels_for_keyframes(bahip_context* ctx, const int* keyframe_i
       if (create_upfront_dealt(ctx, items, filter_new_surfels != 0 && covis_offsets[n] > 0, filter_new_surfels != 0, min_observation_count, surfels,
                                bounded_tiles, &occupancy, &cand_cell, &records, &first, &prepared)) return 1;
     } else if (known && need <= ((size_t)16 << 30) && sizeof(float) * columns < ((size_t)1 << 32) && n * px < ((size_t)1 << 31)) {   // (the scan counts in int)
-      if (need > ctx->create_batch_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        hipFree(ctx->dev_create_batch); ctx->dev_create_batch = nullptr; ctx->create_batch_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->dev_create_batch, need + need / 4));
-        ctx->create_batch_bytes = need + need / 4;
-      }
-      char* p = static_cast<char*>(ctx->dev_create_batch);
+      if (ensure_create_batch(ctx, need)) return 1;
+      char* p = static_cast<char*>(ctx->dev_create_batch.get());
       occupancy = reinterpret_cast<uint8_t*>(p); p += align(occupancy_bytes);
       uint8_t* candidates = reinterpret_cast<uint8_t*>(p); p += align(candidates_bytes);
       uint32_t* scan = reinterpret_cast<uint32_t*>(p); p += align(sizeof(uint32_t) * n * px);
@@ -991,14 +953,14 @@ int bahip_delete_surfels_and_update_radii(bahip_context* ctx, int min_observatio
     // the surfels' rows), summed over the ranks, then the decision on every rank
     const SurfelsView v = make_view(surfels);
     const size_t stride = ((size_t)v.size + 63) & ~(size_t)63, words = (2 + (size_t)ctx->kf_world) * stride;
-    if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, words, 0, "the partial sums of the deletion")) return 1;
-    uint32_t* partial = reinterpret_cast<uint32_t*>(ctx->kf_partials);
+    if (ctx->kf_partials.reserve(words, 0, "the partial sums of the deletion")) return 1;
+    uint32_t* partial = reinterpret_cast<uint32_t*>(ctx->kf_partials.get());
     HIP_TRY(hipMemsetAsync(partial, 0, sizeof(uint32_t) * words, ctx->stream));
     launch_delete_partial(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, v, ctx->kf_rank, ctx->kf_world, partial, (uint32_t)stride);
     CHECK_LAUNCH();
     if (kf_exchange(ctx, partial, sizeof(uint32_t) * words, "the deletion's observation counts and radii")) return 1;
     HIP_TRY(hipMemsetAsync(ctx->dev_counter, 0, sizeof(int), ctx->stream));
-    launch_delete_decide(ctx->stream, v, partial, (uint32_t)stride, ctx->kf_world, min_observation_count, reinterpret_cast<uint32_t*>(ctx->dev_counter));
+    launch_delete_decide(ctx->stream, v, partial, (uint32_t)stride, ctx->kf_world, min_observation_count, reinterpret_cast<uint32_t*>(ctx->dev_counter.get()));
     CHECK_LAUNCH();
     HIP_TRY(hipMemcpyAsync(ctx->pinned_i, ctx->dev_counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1010,9 +972,9 @@ int bahip_delete_surfels_and_update_radii(bahip_context* ctx, int min_observatio
     // keyframes; per surfel the (x, radius^2) words the decision leaves, and the count, are summed over the ranks as int64
     const SurfelsView v = make_view(surfels);
     const size_t words = (size_t)v.size + 1;   // one int64 per surfel, then the count of newly deleted surfels
-    if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, 2 * words, 0, "the rows of the dealt deletion")) return 1;
+    if (ctx->kf_partials.reserve(2 * words, 0, "the rows of the dealt deletion")) return 1;
     void* packed = ctx->kf_partials;
-    uint32_t* count = reinterpret_cast<uint32_t*>(ctx->kf_partials) + 2 * (size_t)v.size;
+    uint32_t* count = reinterpret_cast<uint32_t*>(ctx->kf_partials.get()) + 2 * (size_t)v.size;
     HIP_TRY(hipMemsetAsync(packed, 0, 8 * words, ctx->stream));
     launch_delete_chunks(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, v, (uint32_t)ctx->deal_rank, (uint32_t)ctx->deal_world, ctx->deal_chunk,
                          min_observation_count, packed, count);
@@ -1029,7 +991,7 @@ int bahip_delete_surfels_and_update_radii(bahip_context* ctx, int min_observatio
   }
   HIP_TRY(hipMemsetAsync(ctx->dev_counter, 0, sizeof(int), ctx->stream));
   launch_delete_update(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels), min_observation_count,
-                       reinterpret_cast<uint32_t*>(ctx->dev_counter));
+                       reinterpret_cast<uint32_t*>(ctx->dev_counter.get()));
   CHECK_LAUNCH();
   HIP_TRY(hipMemcpyAsync(ctx->pinned_i, ctx->dev_counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1048,7 +1010,7 @@ int bahip_compact_surfels(bahip_context* ctx, uint32_t surfel_count, const bahip
   uint32_t* invalid = reinterpret_cast<uint32_t*>(base + (size_t)(kSurfelAccum0 + 2) * surfels->pitch_bytes);
   uint32_t* free_rank = reinterpret_cast<uint32_t*>(base + (size_t)(kSurfelAccum0 + 0) * surfels->pitch_bytes);
   uint32_t* free_list = reinterpret_cast<uint32_t*>(base + (size_t)(kSurfelAccum0 + 3) * surfels->pitch_bytes);
-  HIP_TRY(launch_compact(ctx->stream, make_view(surfels), invalid, free_rank, free_list, surfel_count, ctx->scan_temp, ctx->scan_temp_bytes));
+  HIP_TRY(launch_compact(ctx->stream, make_view(surfels), invalid, free_rank, free_list, surfel_count, ctx->scan_temp, ctx->scan_temp.size()));
   return 0;
 }
 
@@ -1059,13 +1021,11 @@ int bahip_sort_surfels_spatially(bahip_context* ctx, const bahip_surfels* surfel
   const float inv_cell = 1.0f / grid_cell_size;
   if (surfels->surfels_size >= 2) {
     const size_t need = sort_scratch_bytes(surfels->surfels_size);
-    if (need > ctx->sort_scratch_bytes) {
+    if (need > ctx->dev_sort_scratch.size()) {
       HIP_TRY(hipStreamSynchronize(ctx->stream));   // (a sort still reading the old scratch)
-      hipFree(ctx->dev_sort_scratch); ctx->dev_sort_scratch = nullptr; ctx->sort_scratch_bytes = 0;
-      HIP_TRY(hipMalloc(&ctx->dev_sort_scratch, need + need / 4));
-      ctx->sort_scratch_bytes = need + need / 4;
+      if (ctx->dev_sort_scratch.reserve(need, need / 4, "the scratch of the spatial sort", true)) return 1;
     }
-    HIP_TRY(sort_surfels_spatially(ctx->stream, make_view(surfels), inv_cell, ctx->dev_sort_scratch, ctx->sort_scratch_bytes));
+    HIP_TRY(sort_surfels_spatially(ctx->stream, make_view(surfels), inv_cell, ctx->dev_sort_scratch, ctx->dev_sort_scratch.size()));
   }
   return 0;
 }

@@ -68,7 +68,7 @@ int bahip_pcg_iteration_controlled(bahip_context* ctx, const bahip_pcg_options* 
     shape.rows_saved = (uint32_t)__builtin_popcount(shape.rows_mask);
     shape.num_tiles = all_tiles;
   }
-  if (opt->optimize_poses) { shape.kf_table = reinterpret_cast<uint32_t*>(ctx->dev_kfs); shape.kf_words = (uint32_t)(sizeof(KfEntry) / 4 * (size_t)K); }
+  if (opt->optimize_poses) { shape.kf_table = reinterpret_cast<uint32_t*>(ctx->dev_kfs.get()); shape.kf_words = (uint32_t)(sizeof(KfEntry) / 4 * (size_t)K); }
   static_assert(sizeof(KfEntry) % 4 == 0, "the keyframe table is saved word by word");
   if (opt->optimize_depth_intrinsics) {
     shape.cfactor = reinterpret_cast<uint32_t*>(ctx->dp.cfactor);
@@ -80,7 +80,7 @@ int bahip_pcg_iteration_controlled(bahip_context* ctx, const bahip_pcg_options* 
   const size_t list_words = 1 + (size_t)all_tiles;
   const bool listed = windowed && shape.num_tiles > 0;
   auto reserve = [&]() -> int {
-    return grow_device(&ctx->pcg_trial, &ctx->pcg_trial_capacity, list_words + pcg_trial_snapshot_words(shape), 1024, "the snapshot of a PCG trial step");
+    return ctx->pcg_trial.reserve(list_words + pcg_trial_snapshot_words(shape), 1024, "the snapshot of a PCG trial step");
   };
   auto list_tiles = [&]() -> int {
     HIP_TRY(hipMemsetAsync(ctx->pcg_trial, 0, sizeof(uint32_t), st));
@@ -94,7 +94,7 @@ int bahip_pcg_iteration_controlled(bahip_context* ctx, const bahip_pcg_options* 
   if (listed) {
     shape.num_tiles = 0;
     if (reserve() || list_tiles()) return 1;
-    if (list_words + pcg_trial_snapshot_words(shape) > ctx->pcg_trial_capacity && (reserve() || list_tiles())) return 1;   // (growing drops the list)
+    if (list_words + pcg_trial_snapshot_words(shape) > ctx->pcg_trial.size() && (reserve() || list_tiles())) return 1;   // (growing drops the list)
     shape.tile_list = ctx->pcg_trial + 1;
   } else if (reserve()) {
     return 1;

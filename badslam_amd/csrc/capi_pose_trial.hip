@@ -37,7 +37,7 @@ int bahip_estimate_keyframe_poses_controlled(bahip_context* ctx, int use_depth, 
   // the buffer, in int64 words: [Hb | cost rows] (exchanged), records, lambdas, two lists, control words
   const size_t sum_words = (size_t)K * (kHbStride + kCostWords), record_words = (size_t)K * (sizeof(PoseTrialRecord) / 8);
   const size_t lambda_words = ((size_t)K + 1) / 2, list_words = (size_t)K, ctl_words = kPoseTrialWords / 2;
-  if (grow_device(&ctx->pose_trial, &ctx->pose_trial_capacity, sum_words + record_words + lambda_words + list_words + ctl_words, 0,
+  if (ctx->pose_trial.reserve(sum_words + record_words + lambda_words + list_words + ctl_words, 0,
                   "the records of a controlled pose phase")) return 1;
   HbFixed* Hb = ctx->pose_trial;
   long long* cost_rows = Hb + (size_t)K * kHbStride;

@@ -159,11 +159,11 @@ int bahip_context_count_ranks(bahip_context* ctx, int timeout_ms, int* ranks_out
   REQUIRE(ctx != nullptr && ranks_out != nullptr, "bahip_context_count_ranks: NULL argument");
   *ranks_out = 1;
   if (!is_sharded(ctx)) return 0;
-  DevMem word;
-  HIP_TRY(hipMalloc(&word.p, sizeof(long long)));
+  DeviceBuffer<long long> word;
+  if (word.reserve(1, 0, "the probe exchange")) return 1;
   const long long one = 1;
-  HIP_TRY(hipMemcpyAsync(word.p, &one, sizeof(one), hipMemcpyHostToDevice, ctx->stream));
-  if (reduce_over_ranks(ctx, word.p, 1, BAHIP_SUM_I64)) return 1;
+  HIP_TRY(hipMemcpyAsync(word, &one, sizeof(one), hipMemcpyHostToDevice, ctx->stream));
+  if (reduce_over_ranks(ctx, word, 1, BAHIP_SUM_I64)) return 1;
   hipEvent_t done;
   HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(done, ctx->stream));
@@ -174,7 +174,7 @@ int bahip_context_count_ranks(bahip_context* ctx, int timeout_ms, int* ranks_out
     if (state != hipErrorNotReady) { hipEventDestroy(done); return fail("the probe exchange failed on the device", __FILE__, __LINE__); }
     if (timeout_ms > 0 && std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - start).count() > timeout_ms) {
       // (the event and the buffer are left alone: the collective may still own them)
-      word.p = nullptr;
+      word.detach();
       return fail(ctx->allreduce ? "the first all-reduce (hook transport) did not complete within the time limit: not every rank reached it"
                                  : "the first ncclAllReduce (native RCCL transport over xGMI) did not complete within the time limit: not every rank "
                                    "reached it, or the communicator's links did not come up (NCCL_DEBUG=INFO shows the ring)", __FILE__, __LINE__);
@@ -183,7 +183,7 @@ int bahip_context_count_ranks(bahip_context* ctx, int timeout_ms, int* ranks_out
   }
   HIP_TRY(hipEventDestroy(done));
   long long seen = 0;
-  HIP_TRY(hipMemcpy(&seen, word.p, sizeof(seen), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&seen, word, sizeof(seen), hipMemcpyDeviceToHost));
   *ranks_out = (int)seen;
   return 0;
 }
@@ -218,7 +218,7 @@ int bahip_gather_surfel_shards(bahip_context* ctx, const bahip_surfels* shard, u
   // the context's lifetime and travels through the gather's page-locked stage both ways (no allocation, no free, one stream wait).
   long long table[kGatherTableWords] = {0};
   table[2 * rank] = shard->surfels_size; table[2 * rank + 1] = shard_surfel_count;
-  if (!ctx->dev_gather_table) HIP_TRY(hipMalloc(&ctx->dev_gather_table, sizeof(table)));
+  if (ctx->dev_gather_table.reserve(kGatherTableWords, 0, "the gather table")) return 1;
   if (stage_upload(&ctx->stage_gather, ctx->dev_gather_table, table, sizeof(table), st)) return 1;
   if (reduce_over_ranks(ctx, ctx->dev_gather_table, 2 * (size_t)world, BAHIP_SUM_I64)) return 1;
   // (stream order: the upload has read the stage before this copy writes it)

@@ -26,14 +26,12 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
   const int S = ctx->in.cf_width * ctx->in.cf_height;
   if (S > ctx->intr_capacity) {
     const int cap = S + 1024;
-    float* grown = nullptr;
     // doubles first (8-byte aligned): glob_d[64] | cells_d[8 cap] | then floats: glob_f[64] | cells_f[8 cap] | Schur partials
-    HIP_TRY(hipMalloc(&grown, sizeof(double) * (64 + 8 * (size_t)cap) + sizeof(float) * (64 + 8 * (size_t)cap + intrinsics_schur_partials(cap))));
-    hipFree(ctx->intr_scratch);
-    ctx->intr_scratch = grown;
+    if (ctx->intr_scratch.reserve(sizeof(double) * (64 + 8 * (size_t)cap) + sizeof(float) * (64 + 8 * (size_t)cap + intrinsics_schur_partials(cap)), 0,
+                                  "the sums of the intrinsics step")) return 1;
     ctx->intr_capacity = cap;
   }
-  double* glob_d = reinterpret_cast<double*>(ctx->intr_scratch);   // 34 sums
+  double* glob_d = static_cast<double*>(ctx->intr_scratch.get());   // 34 sums
   double* cells_d = glob_d + 64;                                   // S records {B0..B4, D, b2, observation count}
   float* glob = reinterpret_cast<float*>(cells_d + 8 * (size_t)ctx->intr_capacity);   // the 34 sums rounded (+ Schur); x1 at [40..44]
   float* cells = glob + 64;
@@ -59,12 +57,14 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
   const uint32_t per_slice = ((positions + (uint32_t)slices - 1) / (uint32_t)slices + 7u) & ~7u;
   const int sets = slices > 1 ? 2 : 1;
   if (optimize_depth) {
-    if (num_bins != ctx->intr_bin_count || sets != ctx->intr_bin_sets) {
-      hipFree(ctx->intr_bin_cursors); hipHostFree(ctx->intr_bin_counts_host); hipFree(ctx->intr_bin_records);
-      ctx->intr_bin_cursors = nullptr; ctx->intr_bin_counts_host = nullptr; ctx->intr_bin_records = nullptr;
+    if (num_bins != ctx->intr_bin_count || sets != ctx->intr_bin_sets) {   // another layout: nothing of the old one is kept
+      ctx->intr_bin_cursors.release(); ctx->intr_bin_counts_host.release(); ctx->intr_bin_records.release();
+    }
+    bool fresh = false;
+    if (ctx->intr_bin_cursors.reserve((size_t)num_bins * 2, 0, "the cursors of the intrinsics records", false, &fresh) ||
+        ctx->intr_bin_counts_host.reserve((size_t)num_bins * kIntrMaxSlices, 0, "the counts of the intrinsics records")) return 1;   // one row of counts per slice
+    if (fresh) {
       ctx->intr_bin_capacity = 0; ctx->intr_bin_wanted = 0;
-      HIP_TRY(hipMalloc(&ctx->intr_bin_cursors, sizeof(uint32_t) * (size_t)num_bins * 2));
-      HIP_TRY(hipHostMalloc(&ctx->intr_bin_counts_host, sizeof(uint32_t) * (size_t)num_bins * kIntrMaxSlices));   // one row of counts per slice
       ctx->intr_bin_count = num_bins;
       ctx->intr_bin_sets = sets;
     }
@@ -80,10 +80,11 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
     if (want > ctx->intr_bin_capacity || (ctx->intr_bin_forced >= 0 && want != ctx->intr_bin_capacity)) {
       static const bool host_timing = getenv("BADSLAM_HOST_TIMING") != nullptr;
       const auto t0 = std::chrono::steady_clock::now();
-      hipFree(ctx->intr_bin_records);
-      ctx->intr_bin_records = nullptr; ctx->intr_bin_capacity = 0;
+      ctx->intr_bin_records.release();   // (30 GB at BASELINE configs[4]: the old block goes before the new one comes; it may also shrink)
+      ctx->intr_bin_capacity = 0;
       const uint64_t cap = (want + 63) / 64 * 64;
-      if (cap) HIP_TRY(hipMalloc(&ctx->intr_bin_records, intrinsics_bin_record_bytes() * cap * (uint64_t)num_bins * (uint64_t)sets));
+      if (cap && ctx->intr_bin_records.reserve(intrinsics_bin_record_bytes() / sizeof(uint32_t) * cap * (uint64_t)num_bins * (uint64_t)sets, 0,
+                                               "the record buffers of the intrinsics step", true)) return 1;
       ctx->intr_bin_capacity = (uint32_t)cap;
       if (host_timing)
         fprintf(stderr, "[intrinsics record buffers] %d set(s) x %d buffers x %llu records = %.2f GB (re)allocated in %.1f ms (%d slices)\n", sets, num_bins,
@@ -208,12 +209,14 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
 // One outer Gauss-Newton iteration of the PCG scheme: B/direct_ba_pcg.cc:229-646.
 static int ensure_pcg_exact(bahip_context* ctx, uint32_t head_count) {
   const size_t need = pcg_exact_cells(head_count);
-  if (need <= ctx->pcg_exact_capacity && ctx->pcg_exact) return 0;
-  void* grown = nullptr;
-  HIP_TRY(hipMalloc(&grown, sizeof(ExactCell) * (need + need / 8)));
-  hipFree(ctx->pcg_exact);   // (pcg_stage_ctl is an allocation of its own, 64 bytes, and stays: ADVICE r3 -- it was freed here and used afterwards)
-  ctx->pcg_exact = grown;
-  ctx->pcg_exact_capacity = need + need / 8;
+  return ctx->pcg_exact.reserve(need, need / 8, "the exact accumulators of the PCG scheme");   // (pcg_stage_ctl is a buffer of its own and stays)
+}
+// The PCG vectors r, M, delta, g, p and the 16 scalars behind them, for U unknowns (lazy (re-)allocation like B/direct_ba_pcg.cc:255-268).
+static int ensure_pcg_vectors(bahip_context* ctx, size_t U) {
+  if (U <= ctx->pcg_capacity && ctx->pcg_buf) return 0;
+  const size_t cap = (U + U / 8 + 4096 + 3) & ~(size_t)3;   // multiple of 4: the scalar block behind the vectors stays 16-byte aligned
+  if (ctx->pcg_buf.reserve(5 * cap + 16, 0, "the vectors of the PCG scheme")) return 1;   // (U > pcg_capacity: always more than there is)
+  ctx->pcg_capacity = cap;
   return 0;
 }
 int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const bahip_surfels* surfels,
@@ -267,15 +270,7 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
     if (num_converged_out) *num_converged_out = K;
     return 0;
   }
-  if (U > ctx->pcg_capacity || ctx->pcg_buf == nullptr) {   // lazy (re-)allocation like B/direct_ba_pcg.cc:255-268
-    const size_t cap = (U + U / 8 + 4096 + 3) & ~(size_t)3;   // multiple of 4: the scalar block behind the vectors stays 16-byte aligned
-    float* grown = nullptr;
-    HIP_TRY(hipMalloc(&grown, sizeof(float) * (5 * cap + 16)));
-    hipFree(ctx->pcg_buf);
-    ctx->pcg_buf = grown;
-    ctx->pcg_capacity = cap;
-  }
-  if (ensure_pcg_exact(ctx, head_count)) return 1;
+  if (ensure_pcg_vectors(ctx, U) || ensure_pcg_exact(ctx, head_count)) return 1;
   const PcgExact ex = pcg_exact_view(ctx->pcg_exact, head_count);
   const size_t cap = ctx->pcg_capacity;
   float* r_ = ctx->pcg_buf; float* M_ = r_ + cap; float* delta = M_ + cap; float* g_ = delta + cap; float* p_ = g_ + cap;
@@ -312,7 +307,7 @@ int bahip_pcg_iteration(bahip_context* ctx, const bahip_pcg_options* opt, const 
     pc.cp.owned = owned_classes(ctx, classes);
     if (L.optimize_geometry && N > 0) {
       class_floats = (size_t)classes * 2 * L.geom_stride * stride;
-      if (grow_device(&ctx->kf_partials, &ctx->kf_partials_capacity, class_floats, 0, "the class partials of the PCG scheme")) return 1;
+      if (ctx->kf_partials.reserve(class_floats, 0, "the class partials of the PCG scheme")) return 1;
       pc.cp.data = ctx->kf_partials;
     }
   }
@@ -532,19 +527,11 @@ int bahip_pcg_iteration_windowed(bahip_context* ctx, const bahip_pcg_options* op
     if (num_converged_out) *num_converged_out = K;
     return 0;
   }
-  if (U > ctx->pcg_capacity || ctx->pcg_buf == nullptr) {
-    const size_t cap = (U + U / 8 + 4096 + 3) & ~(size_t)3;
-    float* grown = nullptr;
-    HIP_TRY(hipMalloc(&grown, sizeof(float) * (5 * cap + 16)));
-    hipFree(ctx->pcg_buf);
-    ctx->pcg_buf = grown;
-    ctx->pcg_capacity = cap;
-  }
-  if (ensure_pcg_exact(ctx, head_count)) return 1;
+  if (ensure_pcg_vectors(ctx, U) || ensure_pcg_exact(ctx, head_count)) return 1;
   // the window on the device: [tile count | keyframe list | pose indices | tile list]
   const uint32_t tiles = (N + 63) / 64;
   const size_t words = 1 + 2 * swept.size() + tiles;
-  if (grow_device(&ctx->pcg_window, &ctx->pcg_window_capacity, words, 1024, "the window lists of the windowed PCG scheme")) return 1;
+  if (ctx->pcg_window.reserve(words, 1024, "the window lists of the windowed PCG scheme")) return 1;
   uint32_t* tile_count = ctx->pcg_window;
   int32_t* kf_list = reinterpret_cast<int32_t*>(ctx->pcg_window + 1);
   uint32_t* pose_list = ctx->pcg_window + 1 + swept.size();
@@ -736,7 +723,7 @@ int bahip_pcg_begin(bahip_context* ctx, const bahip_pcg_layout* layout, uint32_t
   if (ensure_pcg_exact(ctx, head)) return 1;
   // the control block the stage kernels look at: never stopped (the caller owns the inner loop)
   HIP_TRY(hipMemsetAsync(ctx->pcg_exact, 0, sizeof(ExactCell) * pcg_exact_cells(head), ctx->stream));
-  if (!ctx->pcg_stage_ctl) HIP_TRY(hipMalloc(&ctx->pcg_stage_ctl, 64));
+  if (ctx->pcg_stage_ctl.reserve(64, 0, "the control block of the PCG stages")) return 1;
   HIP_TRY(hipMemsetAsync(ctx->pcg_stage_ctl, 0, 64, ctx->stream));
   ctx->pcg_stage_head = head;
   ctx->pcg_stage_step1_calls = 0;

@@ -17,6 +17,13 @@ def cost_dict(c):
                 descriptor_pairs=int(c.descriptor_pairs))
 
 
+def live_allocations(lib=None):
+    """(blocks, bytes) of device and page-locked memory the library holds for itself at the moment: bahip_debug_live_allocations."""
+    count, nbytes = C.c_longlong(), C.c_longlong()
+    capi.check((lib or capi.load()).bahip_debug_live_allocations(C.byref(count), C.byref(nbytes)))
+    return int(count.value), int(nbytes.value)
+
+
 class DeviceBuffer2D:
     """libvis CUDABuffer<T> semantics: (height, width) pitched device allocation."""
 

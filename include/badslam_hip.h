@@ -793,6 +793,10 @@ int bahip_debug_pose_form_launches(long long* global_form, long long* lds_form, 
 /* Kernel dispatches of the pose accumulate sweep since the process started (each slice of a sliced launch counts; never reset).
  * A profile of a bench run uses it to pick the dispatches of the timed region out of rocprofv3's per-dispatch rows. */
 int bahip_debug_pose_kernel_dispatches(long long* dispatches_out);
+/* Blocks of device and page-locked memory the library holds for itself in this process at the moment (all contexts, frame planes from
+ * bahip_frame_planes_create, the scratch of a running test hook) and their bytes; memory handed to the caller (bahip_malloc_pitch,
+ * bahip_host_alloc) is not counted.  A context that is destroyed gives back exactly what it took: a test reads this before and after. */
+int bahip_debug_live_allocations(long long* count_out, long long* bytes_out);
 /* launches of the PCG scheme's step-1 sweep by form since the process started: one tile per wavefront with global atomics on the
  * exact accumulators / persistent workgroups with the pose block of the dense head in LDS (bench.py names the kernel it measured) */
 int bahip_debug_pcg_step1_form_launches(long long* tile_form, long long* lds_form);
