@@ -52,6 +52,18 @@ int bahip_debug_read_pcg_vector(bahip_context* ctx, int which, size_t offset, si
   return 0;
 }
 
+int bahip_debug_read_keyframe_activations(bahip_context* ctx, int* activation_out, int num_keyframes) {
+  REQUIRE(num_keyframes == ctx->num_kfs && (activation_out != nullptr || num_keyframes == 0),
+          "bahip_debug_read_keyframe_activations: one entry per bound keyframe");
+  if (num_keyframes == 0) return 0;
+  // the DEVICE table: the activation field of the host-side copy is "as bound" (capi_ba.hip: bahip_propagate_covisible_activation)
+  std::vector<KfEntry> table((size_t)num_keyframes);
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipMemcpy(table.data(), ctx->dev_kfs, sizeof(KfEntry) * table.size(), hipMemcpyDeviceToHost));
+  for (int k = 0; k < num_keyframes; ++k) activation_out[k] = table[k].activation;
+  return 0;
+}
+
 int bahip_debug_set_pose_lds_items(int items) {
   if (items < 0) return fail("bahip_debug_set_pose_lds_items: items must be >= 0", __FILE__, __LINE__, hipSuccess);
   set_pose_lds_items(items);

@@ -214,6 +214,14 @@ class Scene:
             arr[i].activation = int(kf["activation"])
         capi.check(self.lib.bahip_set_keyframes(self.ctx.handle, arr, len(self.keyframes)))
 
+    def read_keyframe_activations(self):
+        """The activation (capi.KF_*) of every bound keyframe as the DEVICE table holds it now, after waiting for the stream
+        (bahip_debug_read_keyframe_activations): what the window, the co-visible propagation and the pose phase left there."""
+        K = len(self.keyframes)
+        out = (C.c_int * max(1, K))()
+        capi.check(self.lib.bahip_debug_read_keyframe_activations(self.ctx.handle, out, K))
+        return [int(v) for v in out[:K]]
+
     def _supporting_ptrs(self):
         return (C.c_void_p * capi.MERGE_BUFFER_COUNT)(*[b.ptr for b in self.supporting])
 

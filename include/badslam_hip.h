@@ -773,6 +773,10 @@ int bahip_debug_set_pose_rounds_ahead(int rounds);
  * window / propagation, work items) when the keyframe table has at most 1024 entries; 0 (default -- the fused launch measured
  * slower): a launch of its own does.  Results do not depend on it. */
 int bahip_debug_set_fused_iteration_begin(int enabled);
+/* The activation field (BAHIP_KF_*) of every entry of the DEVICE keyframe table, after waiting for the context stream: what
+ * bahip_apply_activation_window, bahip_propagate_covisible_activation, the pose phase's activation update and
+ * bahip_alternating_iterations left there.  num_keyframes: the number of bound keyframes.  Host code only (one copy). */
+int bahip_debug_read_keyframe_activations(bahip_context* ctx, int* activation_out, int num_keyframes);
 /* How the binned per-cell records of the intrinsics step are added (kernels_intrinsics.hip): 0 = into a table in LDS by
  * binary64 LDS atomics, 1 = sorted by cell in LDS and added by the thread that owns the cell, -1 = the default.  Same sums (binary64 sums of
  * binary32 terms, rounded to binary32 afterwards). */
