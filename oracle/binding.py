@@ -408,6 +408,19 @@ class OracleBA:
                                   C.byref(self.surfels), _ptr(idx, C.c_uint32), C.c_int(len(idx)), out.ctypes.data_as(C.c_void_p))
         return out
 
+    def pair_pixel_positions(self, i, surfel_indices, frame_T_global=None):
+        """The float pixel position (pixel-corner convention) of each surfel index in keyframe i as orc_project_associate
+        computes it (orc_pair_pixel_position): (count, 2) float32, meaningful where the pair is associated."""
+        kf = self.keyframes[i]
+        F = (C.c_float * 12)(*(list(kf.frame_T_global) if frame_T_global is None else [float(v) for v in frame_T_global]))
+        out = np.zeros((len(surfel_indices), 2), np.float32)
+        pxy = (C.c_float * 2)()
+        for t, index in enumerate(surfel_indices):
+            self.L.orc_pair_pixel_position(C.byref(self.depth_cam), C.byref(self.dp), C.byref(kf), F, C.byref(self.surfels),
+                                           C.c_uint32(int(index)), pxy)
+            out[t] = pxy[0], pxy[1]
+        return out
+
     # -- geometry / activation --
     def update_surfel_activation(self):
         self.L.orc_update_surfel_activation(C.byref(self.depth_cam), C.byref(self.dp), self._kf_ptr_array(),

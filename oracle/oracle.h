@@ -205,6 +205,10 @@ int orc_evaluate_pair(const orc_camera* color_cam, const orc_camera* depth_cam, 
 void orc_evaluate_pairs(const orc_camera* color_cam, const orc_camera* depth_cam, const orc_depth_params* dp,
                         const orc_keyframe* kf, const float frame_T_global[12], const orc_surfels* s,
                         const uint32_t* surfel_indices, int count, orc_pair_eval* out);
+/* Test hook: the float pixel position (pixel-corner convention) orc_project_associate computes for the pair, which orc_pair_eval
+ * does not hold (0, 0 where z <= 0; meaningful where the pair is associated).  Returns orc_project_associate's decision. */
+int orc_pair_pixel_position(const orc_camera* depth_cam, const orc_depth_params* dp, const orc_keyframe* kf,
+                            const float frame_T_global[12], const orc_surfels* s, uint32_t surfel_index, float pxy[2]);
 
 /* ---- pose optimisation ---- */
 /* B/kernel_opt_pose.cc:39-97 + B/kernel_opt_pose.cu:251-383 + B/gauss_newton.cuh:46-93.

@@ -577,6 +577,16 @@ int orc_evaluate_pair(const orc_camera* color_cam, const orc_camera* depth_cam, 
   return 1;
 }
 
+int orc_pair_pixel_position(const orc_camera* depth_cam, const orc_depth_params* dp, const orc_keyframe* kf, const float F[12],
+                            const orc_surfels* s, uint32_t i, float pxy[2]) {
+  proj_params p = make_proj_params(depth_cam, dp, s, kf, F);
+  proj_result r;
+  memset(&r, 0, sizeof(r));
+  const int associated = orc_project_associate(&p, i, &r, NULL);
+  pxy[0] = r.pxx; pxy[1] = r.pxy;
+  return associated;
+}
+
 /* orc_evaluate_pair for `count` surfel indices against one keyframe (OpenMP over the pairs); used by the sampled
  * per-pair parity test at full size. */
 void orc_evaluate_pairs(const orc_camera* color_cam, const orc_camera* depth_cam, const orc_depth_params* dp,
