@@ -79,6 +79,11 @@ class Cost(C.Structure):           # bahip_cost: the value of the BA objective (
                 ("depth_residuals", C.c_uint64), ("descriptor_pairs", C.c_uint64)]
 
 
+class SurfelCosts(C.Structure):    # bahip_surfel_costs: device planes of the objective per surfel (bahip_evaluate_surfel_costs)
+    _fields_ = [("depth", C.c_void_p), ("descriptor_1", C.c_void_p), ("descriptor_2", C.c_void_p),
+                ("depth_residuals", C.c_void_p), ("descriptor_pairs", C.c_void_p)]
+
+
 class PoseStepControl(C.Structure):   # bahip_pose_step_control: step control of the pose phase (bahip_estimate_keyframe_poses_controlled)
     _fields_ = [("lambda_up", C.c_float), ("lambda_down", C.c_float), ("lambda_min", C.c_float), ("lambda_max", C.c_float),
                 ("max_trials", C.c_int)]
@@ -214,6 +219,8 @@ SIGNATURES = {
     "bahip_evaluate_frame_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                             C.POINTER(Cost)]),
     "bahip_debug_set_cost_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bahip_evaluate_surfel_costs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Surfels), C.POINTER(SurfelCosts)]),
+    "bahip_debug_set_surfel_cost_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

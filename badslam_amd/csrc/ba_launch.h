@@ -450,6 +450,40 @@ void launch_cost(hipStream_t stream, bool use_depth, bool use_desc, const Intrin
 // zeroed words of scratch
 void launch_cost_resolve(hipStream_t stream, const long long* rows, int num, long long* total, bahip_cost* out);
 
+// kernels_surfel_cost.hip: the value of the BA objective per surfel.  Output planes (device, one entry per surfel, any may be NULL);
+// launch shape: `waves` wavefronts per workgroup (each with its own accumulator block in LDS), at most `workgroups` of them.
+constexpr int kSurfelCostMaxWaves = 8;
+constexpr int kSurfelCostLdsPerWave = 3 * kCostCellWords * 64 * 8;   // 13 824 bytes: three exact accumulators per lane
+// default shape: one wavefront per workgroup (13.5 KB), 11 workgroups per compute unit (148.5 of its 160 KB) -- the fastest of the
+// shapes scripts/surfel_cost_eval.py times ("The objective per surfel")
+constexpr int kSurfelCostDefaultWaves = 1, kSurfelCostWorkgroupsPerUnit = 11;
+struct SurfelCostPlanes {
+  double *depth, *descriptor_1, *descriptor_2;
+  uint32_t *depth_residuals, *descriptor_pairs;
+};
+struct SurfelCostShape {
+  int waves, workgroups;
+};
+// The sweep over the surfels [surfel_begin, min(surfel_end, s.size)) (surfel_begin a multiple of 64) against the keyframes of `frames`
+// this rank owns.  rows == NULL: every entry of that range of `out` is written, resolved.  rows != NULL (keyframe sharding): word w of
+// surfel i goes to rows[w * row_stride + (i - surfel_begin)] (kCostWords planes), for the sum over the ranks and
+// launch_surfel_cost_resolve.  *error: a refused opt-in for the LDS of more than 4 wavefronts per workgroup (nothing launched).
+namespace exact {
+void launch_surfel_cost(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, int num_kfs, int kf_rank,
+                        int kf_world, const SurfelsView& s, uint32_t surfel_begin, uint32_t surfel_end, const uint32_t* sched,
+                        const SurfelCostShape& shape, const SurfelCostPlanes& out, long long* rows, uint32_t row_stride, hipError_t* error);
+}
+namespace fast {
+void launch_surfel_cost(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, int num_kfs, int kf_rank,
+                        int kf_world, const SurfelsView& s, uint32_t surfel_begin, uint32_t surfel_end, const uint32_t* sched,
+                        const SurfelCostShape& shape, const SurfelCostPlanes& out, long long* rows, uint32_t row_stride, hipError_t* error);
+}
+void launch_surfel_cost(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* frames, int num_kfs, int kf_rank,
+                        int kf_world, const SurfelsView& s, uint32_t surfel_begin, uint32_t surfel_end, const uint32_t* sched,
+                        const SurfelCostShape& shape, const SurfelCostPlanes& out, long long* rows, uint32_t row_stride, hipError_t* error);
+// the summed staging planes of the surfels [begin, begin + count) -> their entries of `out`
+void launch_surfel_cost_resolve(hipStream_t stream, const long long* rows, uint32_t stride, uint32_t begin, uint32_t count, const SurfelCostPlanes& out);
+
 // kernels_pose_trial.hip: the pose phase under step control.  The record the controlled solve keeps per work item: the limbs of the
 // normal equations and the cost at the accepted pose (PoseWork::T), the cost the phase began with, the candidate the next sweep
 // evaluates (its frame_T_global is PoseWork::F), the damping factor and the counters.

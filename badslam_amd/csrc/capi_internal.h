@@ -7,6 +7,7 @@
 //   capi_solvers.hip    the intrinsics step and the PCG scheme (whole iteration and stage by stage)
 //   capi_debug.hip      test hooks and experiment switches
 //   capi_cost.hip       the value of the BA objective (bahip_evaluate_cost, bahip_evaluate_frame_cost)
+//   capi_surfel_cost.hip the value of the BA objective per surfel (bahip_evaluate_surfel_costs)
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
 // Ownership: every block of device or page-locked memory the boundary allocates for itself is a DeviceBuffer / PinnedBuffer
@@ -198,6 +199,7 @@ struct bahip_context {
   int intr_sums_cells = -1;        // sparse cells of the accumulators the last intrinsics step left in intr_scratch (-1: none; bahip_debug_read_intrinsics_sums)
   DeviceBuffer<float> kf_partials; // class partials of the geometry step (normals, then position) / hit words of the activation
   DeviceBuffer<long long> dev_cost;   // rows of the cost sweep (kernels_cost.hip): kCostWords int64 per keyframe
+  DeviceBuffer<long long> dev_surfel_cost_rows;   // keyframe sharding: staged words of one slice of the per-surfel cost sweep (kernels_surfel_cost.hip)
   // dealing the lifecycle under surfel sharding (bahip_context_set_lifecycle_dealing): the switch, and the surfel partition of the
   // whole-cloud phase in progress -- set by bahip_gather_surfel_shards, cleared by bahip_extract_surfel_shard (deal_world 1: none) --
   // with the gathered cloud it belongs to: lifecycle calls on any other buffer are not dealt

@@ -42,6 +42,7 @@ def _load():
         L.dba_estimate_frame_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.dba_bundle_adjustment.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
         L.dba_compute_cost.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(capi.Cost), C.POINTER(capi.Cost)]
+        L.dba_compute_surfel_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
         L.dba_surfel_count.restype = C.c_uint32
         L.dba_surfel_count.argtypes = [C.c_void_p]
         L.dba_surfels_size.restype = C.c_uint32
@@ -235,6 +236,17 @@ class DirectBA:
         per = (capi.Cost * max(1, n))() if per_keyframe else None
         assert self.L.dba_compute_cost(self.h, self.stream, C.byref(total), per) == 0
         return cost_dict(total), ([cost_dict(c) for c in per[:n]] if per_keyframe else None)
+
+    def compute_surfel_costs(self):
+        """DirectBA::ComputeSurfelCosts: the objective per surfel with this object's residual switches, in buffer order.  Returns a
+        dict of five numpy arrays of surfels_size() entries: depth, descriptor_1, descriptor_2 (float64: exact sums over all keyframes)
+        and depth_residuals, descriptor_pairs (uint32).  Under keyframe sharding every rank gets the unsharded values, under surfel
+        sharding those of its own shard."""
+        n = self.surfels_size()
+        out = {name: np.zeros(n, np.float64) for name in ("depth", "descriptor_1", "descriptor_2")}
+        out.update({name: np.zeros(n, np.uint32) for name in ("depth_residuals", "descriptor_pairs")})
+        assert self.L.dba_compute_surfel_costs(self.h, self.stream, n, *[a.ctypes.data for a in out.values()]) == 0
+        return out
 
     def BundleAdjustment(self, optimize_depth_intrinsics=False, optimize_color_intrinsics=False, do_surfel_updates=False,
                          optimize_poses=True, optimize_geometry=True, min_iterations=1, max_iterations=1, use_pcg=False,

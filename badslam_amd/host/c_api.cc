@@ -158,6 +158,19 @@ int dba_compute_cost(dba_handle* h, void* stream, bahip_cost* total, bahip_cost*
   return 0;
 }
 
+int dba_compute_surfel_costs(dba_handle* h, void* stream, uint32_t capacity, double* depth, double* descriptor_1, double* descriptor_2,
+                             uint32_t* depth_residuals, uint32_t* descriptor_pairs) {
+  if (capacity < h->ba->surfels_size()) return 1;
+  DirectBA::SurfelCosts costs;
+  h->ba->ComputeSurfelCosts(static_cast<hipStream_t>(stream), &costs);
+  if (depth) std::copy(costs.depth.begin(), costs.depth.end(), depth);
+  if (descriptor_1) std::copy(costs.descriptor_1.begin(), costs.descriptor_1.end(), descriptor_1);
+  if (descriptor_2) std::copy(costs.descriptor_2.begin(), costs.descriptor_2.end(), descriptor_2);
+  if (depth_residuals) std::copy(costs.depth_residuals.begin(), costs.depth_residuals.end(), depth_residuals);
+  if (descriptor_pairs) std::copy(costs.descriptor_pairs.begin(), costs.descriptor_pairs.end(), descriptor_pairs);
+  return 0;
+}
+
 uint32_t dba_surfel_count(dba_handle* h) { return h->ba->surfel_count(); }
 uint32_t dba_surfels_size(dba_handle* h) { return h->ba->surfels_size(); }
 int dba_set_surfel_count(dba_handle* h, uint32_t surfel_count, uint32_t surfels_size) {

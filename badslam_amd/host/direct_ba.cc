@@ -510,6 +510,31 @@ void DirectBA::ComputeCost(hipStream_t stream, BACost* total, vector<BACost>* pe
   }
 }
 
+void DirectBA::ComputeSurfelCosts(hipStream_t stream, SurfelCosts* out) {
+  BindScene(stream);
+  const bahip_surfels s = SurfelsStruct(/*with_active*/ false);
+  const size_t n = s.surfels_size;
+  out->depth.assign(n, 0.0); out->descriptor_1.assign(n, 0.0); out->descriptor_2.assign(n, 0.0);
+  out->depth_residuals.assign(n, 0u); out->descriptor_pairs.assign(n, 0u);
+  if (n == 0) return;
+  // one device block for the five planes: 3 x n binary64 followed by 2 x n words
+  CUDABuffer<uint32_t> planes(1, (int)(8 * n));
+  char* base = reinterpret_cast<char*>(planes.ToCUDA().address());
+  bahip_surfel_costs dev{};
+  dev.depth = reinterpret_cast<double*>(base);
+  dev.descriptor_1 = dev.depth + n;
+  dev.descriptor_2 = dev.depth + 2 * n;
+  dev.depth_residuals = reinterpret_cast<uint32_t*>(dev.depth + 3 * n);
+  dev.descriptor_pairs = dev.depth_residuals + n;
+  BAHIP_CHECKED_CALL(bahip_evaluate_surfel_costs(ctx_, use_depth_residuals_ ? 1 : 0, use_descriptor_residuals_ ? 1 : 0, &s, &dev));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->depth.data(), dev.depth, sizeof(double) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->descriptor_1.data(), dev.descriptor_1, sizeof(double) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->descriptor_2.data(), dev.descriptor_2, sizeof(double) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->depth_residuals.data(), dev.depth_residuals, sizeof(uint32_t) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->descriptor_pairs.data(), dev.descriptor_pairs, sizeof(uint32_t) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
+}
+
 void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsics, bool optimize_color_intrinsics,
                                 bool do_surfel_updates, bool optimize_poses, bool optimize_geometry, int min_iterations,
                                 int max_iterations, bool use_pcg, int active_keyframe_window_start,

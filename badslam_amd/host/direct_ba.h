@@ -54,6 +54,15 @@ class DirectBA {
     uint64_t depth_residuals = 0, descriptor_pairs = 0;
   };
   void ComputeCost(hipStream_t stream, BACost* total, vector<BACost>* per_keyframe = nullptr);
+  // The same objective per surfel (bahip_evaluate_surfel_costs): for every entry of the surfel buffer, in buffer order, the exact sums
+  // of its terms over all keyframes and its counts -- zeros for a deleted surfel or one no keyframe sees, NaN sums for a surfel with a
+  // non-finite term.  Each vector gets surfels_size() entries.  Keyframe sharding: every rank gets the unsharded values; surfel
+  // sharding: the values of this rank's shard (nothing is exchanged).  Waits for the stream.
+  struct SurfelCosts {
+    vector<double> depth, descriptor_1, descriptor_2;
+    vector<uint32_t> depth_residuals, descriptor_pairs;
+  };
+  void ComputeSurfelCosts(hipStream_t stream, SurfelCosts* out);
   void UpdateKeyframeCoVisibility(const shared_ptr<Keyframe>& keyframe);
   // B/direct_ba.h:167, B/direct_ba.cc:456-459: surfel colours := mean of their observations in all keyframes (before an export).
   void AssignColors(hipStream_t stream);

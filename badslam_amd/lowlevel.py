@@ -531,6 +531,30 @@ class Scene:
         capi.check(self.lib.bahip_evaluate_frame_cost(self.ctx.handle, int(use_depth), int(use_desc), C.byref(fr), F, C.byref(s), C.byref(out)))
         return cost_dict(out)
 
+    SURFEL_COST_PLANES = (("depth", np.float64), ("descriptor_1", np.float64), ("descriptor_2", np.float64),
+                          ("depth_residuals", np.uint32), ("descriptor_pairs", np.uint32))
+
+    def evaluate_surfel_costs(self, use_depth=True, use_desc=True, planes=None, prefill=None):
+        """The value of the BA objective per surfel over the bound keyframes (bahip_evaluate_surfel_costs): a dict of five numpy arrays
+        of surfels_size entries in buffer order -- depth, descriptor_1, descriptor_2 (float64, exact sums) and depth_residuals,
+        descriptor_pairs (uint32).  planes: the names to ask for (the others are passed as NULL and left out of the dict); prefill: a
+        byte value the device planes are filled with before the call (tests: an entry the call did not write shows).  Call
+        bind_keyframes first."""
+        n = self.surfels_size
+        wanted = [name for name, _ in self.SURFEL_COST_PLANES] if planes is None else list(planes)
+        bufs = {name: DeviceBuffer2D(self.ctx, 1, max(1, n), dtype) for name, dtype in self.SURFEL_COST_PLANES if name in wanted}
+        try:
+            if prefill is not None:
+                for b in bufs.values():
+                    b.clear(prefill)
+            s = self.surfels_struct()
+            out = capi.SurfelCosts(*[bufs[name].ptr if name in bufs else None for name, _ in self.SURFEL_COST_PLANES])
+            capi.check(self.lib.bahip_evaluate_surfel_costs(self.ctx.handle, int(use_depth), int(use_desc), C.byref(s), C.byref(out)))
+            return {name: b.download()[0, :n].copy() for name, b in bufs.items()}
+        finally:
+            for b in bufs.values():
+                b.free()
+
     def exact_sum(self, values, mode=0):
         """Exactly rounded binary64 sum of binary32 values through the device's exact accumulators (test hook)."""
         v = np.ascontiguousarray(values, np.float32)

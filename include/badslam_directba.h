@@ -64,6 +64,11 @@ int dba_bundle_adjustment(dba_handle* h, void* hip_stream, int optimize_depth_in
 /* DirectBA::ComputeCost (ours): the value of the BA objective with the object's residual switches (bahip_evaluate_cost; the same bits
  * under surfel or keyframe sharding).  per_keyframe: NULL or dba_keyframe_count entries indexed by keyframe id, deleted ids zero. */
 int dba_compute_cost(dba_handle* h, void* hip_stream, bahip_cost* total, bahip_cost* per_keyframe);
+/* DirectBA::ComputeSurfelCosts (ours): the same objective per surfel (bahip_evaluate_surfel_costs), in buffer order.  Host arrays of
+ * `capacity` >= dba_surfels_size entries, any may be NULL; the first dba_surfels_size entries are written.  Keyframe sharding: the
+ * unsharded values on every rank; surfel sharding: this rank's shard.  Returns non-zero when capacity is too small. */
+int dba_compute_surfel_costs(dba_handle* h, void* hip_stream, uint32_t capacity, double* depth, double* descriptor_1, double* descriptor_2,
+                             uint32_t* depth_residuals, uint32_t* descriptor_pairs);
 
 /* accessors */
 uint32_t dba_surfel_count(dba_handle* h);

@@ -604,6 +604,29 @@ int bahip_evaluate_frame_cost(bahip_context* ctx, int use_depth, int use_desc, c
  * per launch 1 .. 256, tile_order 0 = buffer order, 1 = the sweeps' heavy-first order when there is one; 0 / -1 = the default. */
 int bahip_debug_set_cost_shape(int waves, int workgroups, int slice, int tile_order);
 
+/* ---- the value of the BA objective per surfel (kernels_surfel_cost.hip; DESIGN.md section 3, "The objective per surfel") -----------
+ * For every surfel i < surfels_size: the pairs (i, k) over the bound keyframes k that bahip_evaluate_cost takes (the production
+ * association rule; activation flags of surfels and keyframes ignored) and its terms.  depth, descriptor_1, descriptor_2: each the
+ * exact sum of the surfel's binary32 terms rounded once to binary64 -- no dependence on the keyframe order, the launch shape, the tile
+ * order or the sharding; depth_residuals, descriptor_pairs: the surfel's depth terms and descriptor pairs (0 when the residual type is
+ * off).  A non-finite term makes that surfel's three sums NaN (its counts still count; no other surfel is touched).  A surfel without
+ * a term -- deleted (NaN position), outside every frustum -- gets +0.0, +0.0, +0.0, 0, 0: every entry [0, surfels_size) of every
+ * non-NULL plane is written by every successful call.  No bound keyframe, or both switches off: the planes are zero-filled, nothing is
+ * swept.  The planes are device memory, borrowed for the call.
+ * Asynchronous on the context's stream.  Surfel sharding: the call covers the shard it is given and exchanges nothing.  Keyframe
+ * sharding: each rank sweeps its own keyframes; the integer words of the surfels (30 per surfel) are summed over the ranks in slices of
+ * 65 536 surfels (one exchange per slice, as many on every rank; the hook's waits apply) and resolved on the device: every rank gets
+ * the unsharded bits.  A failing exchange fails the call and leaves the context usable. */
+typedef struct bahip_surfel_costs {      /* device pointers, borrowed; surfels_size entries each; any may be NULL */
+  double *depth, *descriptor_1, *descriptor_2;
+  uint32_t *depth_residuals, *descriptor_pairs;
+} bahip_surfel_costs;
+int bahip_evaluate_surfel_costs(bahip_context* ctx, int use_depth, int use_desc, const bahip_surfels* surfels, const bahip_surfel_costs* out);
+/* Launch shape of that sweep (test hook; results never depend on it): wavefronts per workgroup 1 .. 8, workgroups >= 1, surfels per
+ * exchange under keyframe sharding (a multiple of 64), tile_order 0 = buffer order, 1 = the sweeps' heavy-first order when there is
+ * one; 0 / -1 = the default. */
+int bahip_debug_set_surfel_cost_shape(int waves, int workgroups, int slice_surfels, int tile_order);
+
 /* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
  * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
  * e = 1e-8 + prior(u) as before and t = lambda * M[u] (one binary32 product), the preconditioner divides by ((M[u] + 1e-8) + prior(u))
