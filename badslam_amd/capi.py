@@ -94,6 +94,16 @@ class PCGStepControl(C.Structure):   # bahip_pcg_step_control: step control of t
                 ("lambda_min", C.c_float), ("lambda_max", C.c_float), ("max_trials", C.c_int)]
 
 
+class GeometryStepControl(C.Structure):   # bahip_geometry_step_control: step control of the geometry phase (bahip_optimize_geometry_iteration_controlled)
+    _fields_ = [("lambda_initial", C.c_float), ("lambda_up", C.c_float), ("lambda_min", C.c_float), ("lambda_max", C.c_float),
+                ("max_trials", C.c_int), ("guard_pairs", C.c_int)]
+
+
+class GeometryStepStats(C.Structure):   # bahip_geometry_step_stats
+    _fields_ = [("candidates", C.c_uint32), ("accepted", C.c_uint32), ("restored", C.c_uint32), ("rejected_cost", C.c_uint32),
+                ("rejected_pairs", C.c_uint32), ("trials", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol declared in include/badslam_hip.h
@@ -221,6 +231,10 @@ SIGNATURES = {
     "bahip_debug_set_cost_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bahip_evaluate_surfel_costs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Surfels), C.POINTER(SurfelCosts)]),
     "bahip_debug_set_surfel_cost_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bahip_optimize_geometry_iteration_controlled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(GeometryStepControl), C.POINTER(Surfels),
+                                                               C.c_longlong, C.c_void_p, C.POINTER(GeometryStepStats)]),
+    "bahip_debug_read_geometry_sums": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "bahip_debug_geometry_trial_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

@@ -525,4 +525,28 @@ void launch_pose_trial_solve(hipStream_t stream, void* work, int num_work, PoseT
 void set_pose_trial_shape(int waves, int parts_shift);   // test hook: wavefronts per workgroup (0: 16), 2^shift wavefronts share a tile's items (-1: from the grid size)
 void launch_pose_step_damped_debug(hipStream_t stream, const float* in, float* out);
 
+// kernels_geometry_trial.hip: the geometry phase under step control.  Per surfel the five words a geometry step may write (x, y, z,
+// descriptor_1, descriptor_2; plane r of `saved`), whether its trial is still open, and its outcome so far; `stride` entries per plane.
+constexpr int kGeometryTrialWords = 5, kGeometryTrialBlock = 256;
+struct GeometryTrialState {
+  uint32_t* saved;
+  uint8_t* open;
+  uint8_t* outcome;
+  uint32_t stride;
+};
+// control words of a controlled step, kept by the one-workgroup count launch behind every decide launch: the surfels still open (what
+// the host reads per trial) and the totals of bahip_geometry_step_stats
+constexpr int kGeometryTrialCtlOpen = 0, kGeometryTrialCtlCandidates = 1, kGeometryTrialCtlAccepted = 2, kGeometryTrialCtlRejectedCost = 3,
+              kGeometryTrialCtlRejectedPairs = 4, kGeometryTrialCtlWords = 8;
+void launch_geometry_trial_snapshot(hipStream_t st, const SurfelsView& s, const GeometryTrialState& state);
+// the candidate of trial `trial` (damping `lambda`) for the open surfels from the position pass's class partials `cpp` (2 or 8 sums)
+void launch_geometry_trial_solve(hipStream_t st, const SurfelsView& s, const ClassPartials& cpp, int classes, bool use_desc, float lambda, int trial,
+                                 const GeometryTrialState& state);
+// keep or undo per open surfel (c0: the cost planes before the trials, c1: of the candidate state), then the counts into `ctl`;
+// partials: 4 words per workgroup of kGeometryTrialBlock surfels
+void launch_geometry_trial_decide(hipStream_t st, const SurfelsView& s, const SurfelCostPlanes& c0, const SurfelCostPlanes& c1, bool guard_pairs,
+                                  int trial, const GeometryTrialState& state, uint32_t* partials, uint32_t* ctl);
+void launch_geometry_trial_finish(hipStream_t st, uint32_t size, const GeometryTrialState& state, uint8_t* out /* may be NULL */);
+void launch_geometry_trial_restore(hipStream_t st, const SurfelsView& s, const GeometryTrialState& state);
+
 }  // namespace bahip

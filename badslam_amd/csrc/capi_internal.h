@@ -10,6 +10,7 @@
 //   capi_surfel_cost.hip the value of the BA objective per surfel (bahip_evaluate_surfel_costs)
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
+//   capi_geometry_trial.hip step control of the geometry phase of the alternating scheme
 // Ownership: every block of device or page-locked memory the boundary allocates for itself is a DeviceBuffer / PinnedBuffer
 // (capi_buffers.h) -- a member of bahip_context, of bahip_frame_planes or of an UploadStage, or a local of a test hook -- and is freed
 // with its owner; a unit grows one with reserve().  Only memory handed to the caller (bahip_malloc_pitch, bahip_host_alloc) is raw.
@@ -190,6 +191,14 @@ struct bahip_context {
   float pcg_damping = 0.f;         // lambda of the damped PCG system (bahip_context_set_pcg_damping; kernels_pcg_trial.hip)
   DeviceBuffer<uint32_t> pcg_trial;    // bahip_pcg_iteration_controlled: [tile count | tile list] followed by the snapshot
   DeviceBuffer<long long> pose_trial;  // bahip_estimate_keyframe_poses_controlled: [Hb | cost rows] (what the ranks exchange), records, lambdas, lists, control words
+  // bahip_optimize_geometry_iteration_controlled: [position class partials | saved words | cost planes c0, c1 | open | outcome | count
+  // partials | control words]; the partials stay until the next controlled call (bahip_debug_read_geometry_sums)
+  DeviceBuffer<double> geometry_trial;
+  int geometry_trial_sums = 0;           // sums per surfel the last controlled call consumed (2 or 8; 0: none yet), their classes,
+  int geometry_trial_classes = 0;        // surfels and plane stride
+  uint32_t geometry_trial_size = 0, geometry_trial_stride = 0;
+  int geometry_trial_timing = 0;         // bahip_debug_geometry_trial_timing
+  double geometry_trial_ms[4] = {};
   int world = 0;                   // ranks of the RCCL communicator (0 = none)
   int kf_rank = 0, kf_world = 1;   // keyframe sharding (bahip_context_set_keyframe_sharding): keyframe k lives on rank k % kf_world (1, 2, 4 or 8)
   int arithmetic = 0;              // BAHIP_ARITHMETIC_EXACT / _FAST: flavour of the sweeps (bahip_context_set_arithmetic), mirrored in in.fast_math

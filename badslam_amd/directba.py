@@ -63,6 +63,8 @@ def _load():
         L.dba_pcg_step_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dba_set_pose_step_control.argtypes = [C.c_void_p, C.c_int] + [C.c_float] * 5 + [C.c_int]
         L.dba_get_pose_step_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float)]
+        L.dba_set_geometry_step_control.argtypes = [C.c_void_p, C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_int]
+        L.dba_get_geometry_step_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3 + [C.POINTER(C.c_int)]
         L.dba_set_distributed_lifecycle.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_ba_iteration_counts.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -370,6 +372,29 @@ class DirectBA:
         if self.L.dba_set_pose_step_control(self.h, 1, v["lambda_initial"], v["lambda_up"], v["lambda_down"], v["lambda_min"],
                                             v["lambda_max"], int(v["max_trials"])) != 0:
             raise RuntimeError("SetPoseStepControl: refused under keyframe sharding, or a value is out of range")
+
+    def SetGeometryStepControl(self, control=None, **fields):
+        """Step control of the geometry phase of the alternating scheme (default off): per surfel, a damped step is kept only if that
+        surfel's cost falls strictly (and, with guard_pairs, it loses no associated pair); otherwise its words come back bit for bit.
+        control: None / False = off, True = the defaults, or a dict; fields: lambda_initial, lambda_up, lambda_min, lambda_max,
+        max_trials, guard_pairs.  Allowed under either sharding; raises for values out of range."""
+        if control is None or control is False:
+            if self.L.dba_set_geometry_step_control(self.h, 0, 0.0, 0.0, 0.0, 0.0, 0, 0) != 0:
+                raise RuntimeError("SetGeometryStepControl: could not be switched off")
+            return
+        v = dict(lambda_initial=0.0, lambda_up=4.0, lambda_min=1.0, lambda_max=1e4, max_trials=4, guard_pairs=True)
+        v.update(control if isinstance(control, dict) else {})
+        v.update(fields)
+        if self.L.dba_set_geometry_step_control(self.h, 1, v["lambda_initial"], v["lambda_up"], v["lambda_min"], v["lambda_max"],
+                                                int(v["max_trials"]), int(bool(v["guard_pairs"]))) != 0:
+            raise RuntimeError("SetGeometryStepControl: a value is out of range")
+
+    def geometry_step_stats(self):
+        """(last_geometry_candidates, last_geometry_accepted, last_geometry_restored, last_geometry_trials): the totals over the geometry
+        calls of the last BundleAdjustment call; candidates = accepted + restored."""
+        candidates, accepted, restored, trials = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_int()
+        self.L.dba_get_geometry_step_stats(self.h, C.byref(candidates), C.byref(accepted), C.byref(restored), C.byref(trials))
+        return candidates.value, accepted.value, restored.value, trials.value
 
     def pose_step_stats(self, keyframe_id=0):
         """(last_pose_trials, last_pose_rejected_steps, lambda of keyframe_id): candidates evaluated / rejected by the pose phases of the

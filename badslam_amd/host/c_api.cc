@@ -299,6 +299,21 @@ int dba_get_pose_step_stats(dba_handle* h, int* trials, int* rejected_steps, int
   if (lambda) *lambda = h->ba->pose_lambda(keyframe_id);
   return 0;
 }
+int dba_set_geometry_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_min, float lambda_max,
+                                  int max_trials, int guard_pairs) {
+  if (!enabled) return h->ba->SetGeometryStepControl(nullptr) ? 0 : 1;
+  vis::DirectBA::GeometryStepControl control;
+  control.lambda_initial = lambda_initial; control.lambda_up = lambda_up; control.lambda_min = lambda_min; control.lambda_max = lambda_max;
+  control.max_trials = max_trials; control.guard_pairs = guard_pairs != 0;
+  return h->ba->SetGeometryStepControl(&control) ? 0 : 1;
+}
+int dba_get_geometry_step_stats(dba_handle* h, long long* candidates, long long* accepted, long long* restored, int* trials) {
+  if (candidates) *candidates = h->ba->last_geometry_candidates();
+  if (accepted) *accepted = h->ba->last_geometry_accepted();
+  if (restored) *restored = h->ba->last_geometry_restored();
+  if (trials) *trials = h->ba->last_geometry_trials();
+  return 0;
+}
 int dba_set_distributed_lifecycle(dba_handle* h, int enabled) { return h->ba->SetDistributedLifecycle(enabled != 0) ? 0 : 1; }
 int dba_last_stats(dba_handle* h, int* pose_rounds, int* pose_steps, int* pcg_inner_steps) {
   if (pose_rounds) *pose_rounds = h->ba->last_pose_rounds();

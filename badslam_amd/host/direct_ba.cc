@@ -282,6 +282,24 @@ bool DirectBA::SetPoseStepControl(const PoseStepControl* control) {
   return true;
 }
 
+bool DirectBA::SetGeometryStepControl(const GeometryStepControl* control) {
+  if (!control) {
+    geometry_step_control_on_ = false;
+    return true;
+  }
+  // (the checks of bahip_optimize_geometry_iteration_controlled, which would otherwise refuse in the middle of BundleAdjustment)
+  if (!(control->max_trials >= 1 && control->max_trials <= 254 && std::isfinite(control->lambda_initial) && control->lambda_initial >= 0.f &&
+        std::isfinite(control->lambda_up) && control->lambda_up > 1.f && std::isfinite(control->lambda_min) && control->lambda_min > 0.f &&
+        std::isfinite(control->lambda_max) && control->lambda_min <= control->lambda_max)) {
+    LOG(ERROR) << "SetGeometryStepControl: needs 1 <= max_trials <= 254, finite lambda_initial >= 0, finite lambda_up > 1, "
+                  "0 < lambda_min <= finite lambda_max";
+    return false;
+  }
+  geometry_step_control_ = *control;
+  geometry_step_control_on_ = true;
+  return true;
+}
+
 bool DirectBA::SetDistributedLifecycle(bool enabled) {
   if (enabled && keyframe_shard_world_ > 1) {
     LOG(ERROR) << "SetDistributedLifecycle: keyframe sharding deals its lifecycle by keyframe already";
@@ -550,6 +568,8 @@ void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsi
     optimize_color_intrinsics = false;
   }
   last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = last_pcg_trials_ = last_pcg_rejected_steps_ = last_pose_trials_ = last_pose_rejected_steps_ = 0;
+  last_geometry_candidates_ = last_geometry_accepted_ = last_geometry_restored_ = 0;
+  last_geometry_trials_ = 0;
   if (keyframe_shard_world_ > 1)
     CHECK(batched_creation_ || (!do_surfel_updates && !increase_ba_iteration_count))
         << "keyframe sharding runs the surfel lifecycle through the batched calls only (SetBatchedCreation(true))";
@@ -675,7 +695,8 @@ void DirectBA::BundleAdjustmentAlternating(hipStream_t stream, bool optimize_dep
             progress_function ? 1 : 0, timer ? 1 : 0, timings_stream_ ? 1 : 0, keyframe_shard_world_, (int)full_window, max_iterations);
   if (optimize_poses && optimize_geometry && !do_surfel_updates && !optimize_depth_intrinsics && !optimize_color_intrinsics &&
       !progress_function && !timer && !timings_stream_ && keyframe_shard_world_ == 1 && full_window && max_iterations > 0 &&
-      !pose_step_control_on_ /* the controlled pose phase is a stage call: the iterations go through the loop below */) {
+      !pose_step_control_on_ /* the controlled pose phase is a stage call: the iterations go through the loop below */ &&
+      !geometry_step_control_on_ /* ... and so is the controlled geometry phase */) {
     if (fixed_active_keyframe_set) {
       Lock();
       set_window_activation();
@@ -807,7 +828,19 @@ void DirectBA::BundleAdjustmentAlternating(hipStream_t stream, bool optimize_dep
     }
     if (optimize_geometry) {
       const bahip_surfels s = SurfelsStruct();
-      if (full_window) {
+      if (geometry_step_control_on_) {
+        // the same two calls under step control: per surfel a damped step that is kept only if the surfel's cost falls
+        const bahip_geometry_step_control control{geometry_step_control_.lambda_initial, geometry_step_control_.lambda_up,
+                                                  geometry_step_control_.lambda_min, geometry_step_control_.lambda_max,
+                                                  geometry_step_control_.max_trials, geometry_step_control_.guard_pairs ? 1 : 0};
+        bahip_geometry_step_stats stats{};
+        BAHIP_CHECKED_CALL(bahip_optimize_geometry_iteration_controlled(ctx_, use_depth_residuals_, use_descriptor_residuals_, &control, &s,
+                                                                        full_window ? (long long)old_surfels_size : -1, nullptr, &stats));
+        last_geometry_candidates_ += stats.candidates;
+        last_geometry_accepted_ += stats.accepted;
+        last_geometry_restored_ += stats.restored;
+        last_geometry_trials_ += stats.trials;
+      } else if (full_window) {
         // UpdateSurfelActivationCUDA + OptimizeGeometryIterationCUDA (B/direct_ba_alternating.cc:441-487) as one sweep
         BAHIP_CHECKED_CALL(bahip_update_activation_and_optimize_geometry(ctx_, use_depth_residuals_, use_descriptor_residuals_, &s,
                                                                          (uint32_t)old_surfels_size));

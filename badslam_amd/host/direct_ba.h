@@ -193,6 +193,24 @@ class DirectBA {
     const auto it = pose_lambdas_.find(keyframe_id);
     return it == pose_lambdas_.end() ? pose_step_control_.lambda_initial : it->second;
   }
+  // Step control of the geometry phase of the alternating scheme (ours; default off = NULL: every Gauss-Newton step of a surfel is
+  // applied, as the reference does).  On: both geometry calls of BundleAdjustment(!use_pcg) are
+  // bahip_optimize_geometry_iteration_controlled -- per surfel, a damped step is kept only if that surfel's cost falls strictly (and,
+  // with guard_pairs, it loses no associated pair), otherwise its words come back bit for bit; the full-window call passes the
+  // activation range, the windowed one keeps the flags.  The device-driven loop is not used.  Allowed under either sharding.
+  struct GeometryStepControl {
+    float lambda_initial = 0.f, lambda_up = 4.f, lambda_min = 1.f, lambda_max = 1e4f;
+    int max_trials = 4;
+    bool guard_pairs = true;
+  };
+  bool SetGeometryStepControl(const GeometryStepControl* control);
+  bool geometry_step_control() const { return geometry_step_control_on_; }
+  // totals over the geometry calls of the last BundleAdjustment() call: surfels with a candidate, those that ended with an accepted
+  // candidate, those that ended with their old words (candidates = accepted + restored), and the trials run
+  long long last_geometry_candidates() const { return last_geometry_candidates_; }
+  long long last_geometry_accepted() const { return last_geometry_accepted_; }
+  long long last_geometry_restored() const { return last_geometry_restored_; }
+  int last_geometry_trials() const { return last_geometry_trials_; }
   // Multi-GPU surfel sharding: sums of the per-keyframe normal equations go through this hook
   // (see include/badslam_hip.h, bahip_allreduce_fn).
   void SetAllReduce(bahip_allreduce_fn fn, void* user) { BAHIP_CHECKED_CALL(bahip_context_set_allreduce(ctx_, fn, user)); }
@@ -322,6 +340,10 @@ class DirectBA {
   PoseStepControl pose_step_control_;
   std::unordered_map<int, float> pose_lambdas_;   // keyframe id -> damping factor
   int last_pose_trials_ = 0, last_pose_rejected_steps_ = 0;
+  bool geometry_step_control_on_ = false;
+  GeometryStepControl geometry_step_control_;
+  long long last_geometry_candidates_ = 0, last_geometry_accepted_ = 0, last_geometry_restored_ = 0;
+  int last_geometry_trials_ = 0;
   bool distributed_lifecycle_ = false;   // SetDistributedLifecycle
   int pcg_sum_classes_ = 1;        // (SetPCGSumClasses: the windowed scheme needs 1)
   int shard_rank_ = 0, shard_world_ = 1, whole_cloud_depth_ = 0;

@@ -379,6 +379,44 @@ class Scene:
         n = self.surfels_size if activation_surfels_size is None else int(activation_surfels_size)
         capi.check(self.lib.bahip_update_activation_and_optimize_geometry(self.ctx.handle, int(use_depth), int(use_desc), C.byref(s), n))
 
+    GEOMETRY_STEP_CONTROL = dict(lambda_initial=0.0, lambda_up=4.0, lambda_min=1.0, lambda_max=1e4, max_trials=4, guard_pairs=1)
+
+    def optimize_geometry_controlled(self, use_depth=True, use_desc=True, control=None, activation_surfels_size=None, want_outcome=True,
+                                     want_stats=True, prefill=0xEE):
+        """One geometry step of the alternating scheme under step control (bahip_optimize_geometry_iteration_controlled).  control: a
+        dict overriding fields of GEOMETRY_STEP_CONTROL (the defaults of DirectBA::GeometryStepControl); activation_surfels_size: None
+        = the flags are kept (-1), else the range the normals pass decides.  Returns (outcome, stats): outcome a uint8 array of
+        surfels_size entries (its device buffer filled with the byte `prefill` first: an entry the call did not write shows) or None,
+        stats a dict of the fields of bahip_geometry_step_stats or None."""
+        fields = dict(self.GEOMETRY_STEP_CONTROL)
+        fields.update(control or {})
+        ctl = capi.GeometryStepControl(float(fields["lambda_initial"]), float(fields["lambda_up"]), float(fields["lambda_min"]),
+                                       float(fields["lambda_max"]), int(fields["max_trials"]), int(fields["guard_pairs"]))
+        n = self.surfels_size
+        buf = DeviceBuffer2D(self.ctx, 1, max(1, n), np.uint8) if want_outcome else None
+        stats = capi.GeometryStepStats() if want_stats else None
+        try:
+            if buf is not None:
+                buf.clear(prefill)
+            s = self.surfels_struct()
+            capi.check(self.lib.bahip_optimize_geometry_iteration_controlled(
+                self.ctx.handle, int(use_depth), int(use_desc), C.byref(ctl), C.byref(s),
+                -1 if activation_surfels_size is None else int(activation_surfels_size), buf.ptr if buf is not None else None,
+                C.byref(stats) if stats is not None else None))
+            self.ctx.synchronize()
+            outcome = buf.download()[0, :n].copy() if buf is not None else None
+        finally:
+            if buf is not None:
+                buf.free()
+        return outcome, ({name: int(getattr(stats, name)) for name, _ in capi.GeometryStepStats._fields_} if stats is not None else None)
+
+    def read_geometry_sums(self, count):
+        """The per-surfel totals the last controlled geometry step consumed (bahip_debug_read_geometry_sums): (count, surfels_size)
+        binary32, count = 2 depth-only (H, b) or 8 (a0 a1 a2 a3 a5 a6 a7 a8)."""
+        out = np.zeros((8, self.surfels_size), np.float32)   # (room for either count: the call writes what the step consumed)
+        capi.check(self.lib.bahip_debug_read_geometry_sums(self.ctx.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[:int(count)].copy()
+
     def estimate_keyframe_poses(self, use_depth, use_desc):
         K = len(self.keyframes)
         poses = (C.c_float * (7 * K))()

@@ -112,6 +112,13 @@ int dba_pcg_step_stats(dba_handle* h, float* lambda, int* trials, int* rejected_
 int dba_set_pose_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_down, float lambda_min,
                               float lambda_max, int max_trials);
 int dba_get_pose_step_stats(dba_handle* h, int* trials, int* rejected_steps, int keyframe_id, float* lambda);
+/* DirectBA::SetGeometryStepControl (ours, default off): both geometry calls of BundleAdjustment(!use_pcg) keep a damped step of a surfel
+ * only if that surfel's cost falls (bahip_optimize_geometry_iteration_controlled; the fields are bahip_geometry_step_control's).
+ * enabled = 0: off.  Allowed under either sharding; returns 1 (refused) for values out of range.  dba_get_geometry_step_stats: the totals
+ * over the geometry calls of the last BundleAdjustment call (candidates = accepted + restored) and the trials run; any may be NULL. */
+int dba_set_geometry_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_min, float lambda_max,
+                                  int max_trials, int guard_pairs);
+int dba_get_geometry_step_stats(dba_handle* h, long long* candidates, long long* accepted, long long* restored, int* trials);
 /* DirectBA::SetSurfelSharding: this object holds rank `rank`'s chunk-cyclic shard of one surfel cloud (bahip_gather_surfel_shards) */
 int dba_set_surfel_sharding(dba_handle* h, int rank, int world, uint32_t chunk);
 /* DirectBA::SetDistributedLifecycle (ours, default off): under surfel sharding the lifecycle's sweeps are dealt over the ranks

@@ -704,6 +704,65 @@ int bahip_estimate_keyframe_poses_controlled(bahip_context* ctx, int use_depth_r
 /* bahip_debug_pose_step with the damped diagonal (lambda = 0: its 25 words bit for bit). */
 int bahip_debug_pose_step_damped(bahip_context* ctx, const float* H21_b6, const float* global_T_frame, float lambda, float* out_25);
 
+/* ---- step control for the geometry phase of the alternating scheme (ours: the reference applies every Gauss-Newton step;
+ * kernels_geometry_trial.hip, DESIGN.md section 3, "Step control of the geometry phase") -------------------------------------------------
+ * With the poses frozen a surfel's cost depends on that surfel alone, so the step is kept or undone PER SURFEL, exactly.  One call:
+ *  1. Normals, activation and sums: phases 1 and 2 of the three-phase geometry step (the keyframe-sharded form of
+ *     bahip_update_activation_and_optimize_geometry; unsharded this rank owns every class and nothing is exchanged, under keyframe
+ *     sharding the two exchanges of that form are made).  Afterwards the flags and normals are those of the plain step, bit for bit, and
+ *     the class partials of the position pass hold each surfel's sums: 2 depth-only, or the 8 values a0 a1 a2 a3 a5 a6 a7 a8.  The
+ *     normals update is NOT part of the trial: the controlled objective is the cost after it.
+ *  2. c0 = bahip_evaluate_surfel_costs of that state (flavour and sharding as the context has them).
+ *  3. The five words x, y, z, descriptor_1, descriptor_2 of every surfel are saved; every live surfel (in range, active, position not
+ *     NaN) is open.
+ *  4. Trials t = 0 .. max_trials - 1 with a scalar lambda_t, the same for every surfel: lambda_0 = lambda_initial, lambda_{t+1} =
+ *     min(max(lambda_t * lambda_up, lambda_min), lambda_max) in binary32.  The trial solve (one thread per surfel, in the exact
+ *     arithmetic whatever the flavour of the sweeps) forms the totals (p0 + p1) + p2 ... from the class partials and restates the plain
+ *     solve with the diagonal damped as one binary32 product and then one add: H_ii = (a_ii + 1e-6f) + lambda * a_ii for a0, a3 and a5;
+ *     depth-only the gate stays H > 1e-6f and t = -b / (H + lambda * H).  lambda = 0 gives every bit of the plain step in the exact
+ *     flavour.  The candidate goes into the rows of open surfels only, under the plain step's own write conditions; at t = 0 an open
+ *     surfel whose candidate equals its words bit for bit is closed with outcome 0.
+ *  5. c1 = bahip_evaluate_surfel_costs of the candidate state.
+ *  6. With f(c) = (depth + descriptor_1) + descriptor_2 in binary64: an open surfel is accepted iff its five candidate words are all
+ *     finite, f(c1) is finite and f(c1) < f(c0) -- and, with guard_pairs, depth_residuals and descriptor_pairs of c1 are not below those
+ *     of c0 (the objective counts associated pairs only: without the guard a surfel is rewarded for drifting out of sight).  Accepted:
+ *     the words stay, outcome 1 + t, closed.  Rejected: the five saved words are written back, every bit, and the surfel stays open.  A
+ *     non-finite candidate is rejected without looking at c1 (a NaN position would read as a deleted surfel of cost 0).
+ *  7. The host reads one word per trial, the count of open surfels, and stops at 0 or after max_trials.  Surfels still open: outcome
+ *     255, their saved words.  Surfels that are not live: outcome 0, none of their words touched.  Every entry of a non-NULL `outcome`
+ *     (device memory, surfels_size bytes) is written by every successful call.
+ * Argument checks as for bahip_pcg_step_control (error text, context usable); max_trials <= 254.  activation_surfels_size: the range
+ * whose flags the normals pass decides, -1 = the flags are kept (bahip_optimize_geometry_iteration).  An error inside the loop writes the
+ * saved words back before it returns.  Surfel sharding: the call covers its shard and exchanges nothing; the ranks may run different
+ * numbers of trials.  Keyframe sharding: every decision is taken from bits that are equal on every rank, so every rank takes the same
+ * branches, the open count needs no exchange, and every rank ends with the unsharded bits at the same class count.  The host waits
+ * once per trial. */
+typedef struct bahip_geometry_step_control {
+  float lambda_initial;  /* damping of trial 0; finite, >= 0; 0 = the plain Gauss-Newton step */
+  float lambda_up;       /* finite, > 1 */
+  float lambda_min;      /* finite, > 0: the first non-zero rung */
+  float lambda_max;      /* finite, >= lambda_min */
+  int   max_trials;      /* >= 1 */
+  int   guard_pairs;     /* != 0: a trial that loses a depth residual or a descriptor pair is rejected */
+} bahip_geometry_step_control;
+typedef struct bahip_geometry_step_stats {
+  uint32_t candidates;      /* live surfels whose trial-0 candidate differs from their words */
+  uint32_t accepted;        /* ... that ended with an accepted candidate */
+  uint32_t restored;        /* ... that ended with their old words */
+  uint32_t rejected_cost;   /* rejections (over all trials) by the cost test or a non-finite candidate */
+  uint32_t rejected_pairs;  /* rejections whose cost test passed but the pair guard failed */
+  int      trials;          /* trials run (cost sweeps made after the first one) */
+} bahip_geometry_step_stats;
+int bahip_optimize_geometry_iteration_controlled(bahip_context* ctx, int use_depth_residuals, int use_descriptor_residuals,
+                                                 const bahip_geometry_step_control* control, const bahip_surfels* surfels,
+                                                 long long activation_surfels_size, uint8_t* outcome, bahip_geometry_step_stats* stats);
+/* The totals the last controlled call consumed, combined from its class partials in the defined order: host_out[q * surfels_size + i],
+ * q < 2 (depth-only) or 8.  Fails when no controlled call has run on this context. */
+int bahip_debug_read_geometry_sums(bahip_context* ctx, float* host_out);
+/* Host wall-clock split of the last controlled call, in milliseconds, when on (off by default; each part is then followed by a wait
+ * for the stream): out[0] phases 1-2, [1] the cost sweeps, [2] snapshot, solve and decide launches, [3] the per-trial read-backs. */
+int bahip_debug_geometry_trial_timing(bahip_context* ctx, int enable, double out[4]);
+
 /* ---- test hook --------------------------------------------------------------------------------------
  * Per-pair evaluation with the production device functions (association, the three raw residuals,
  * weights, pose Jacobians, image gradients) for `count` surfel indices against one frame; 40 floats
