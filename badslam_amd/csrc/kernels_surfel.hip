@@ -35,6 +35,18 @@ namespace bahip {
 #ifndef BAHIP_WAVES_ATTR
 #define BAHIP_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(4)))   // cap the allocation at 128 VGPRs: 4 waves per SIMD (5 spills: measured slower)
 #endif
+// The one-wavefront geometry kernel (geometry_kernel<.., 1, ..>) runs at its own occupancy: 5 wavefronts per SIMD = 512 / 5 registers at the
+// allocation granule of 8 = 96 VGPRs, reached without scratch by parking the per-lane state that its candidate loops do not touch in LDS
+// (ParkSlot below).  Measured at the bench size, alternating runs on one box (profiles/r7_ab_geometry_waves.txt): geometry sweep 0.645 ->
+// 0.606 ms; the same parked code held to four wavefronts by a larger LDS block: 0.645, so the parking costs nothing and the occupancy is
+// what pays.  `make variant NAME=g6 EXTRA=-DBAHIP_GEOMETRY_WAVES=6` builds the kernel for another occupancy (the attribute is a minimum: 4
+// gives the code of 5; at 6 = 80 VGPRs this set of parked values leaves 10-13 dwords of scratch per lane, and it was not measured).
+#ifndef BAHIP_GEOMETRY_WAVES
+#define BAHIP_GEOMETRY_WAVES 5
+#endif
+#if BAHIP_GEOMETRY_WAVES > 5
+#warning "BAHIP_GEOMETRY_WAVES > 5: the parked state (ParkSlot) does not bring the joint solve under 80 VGPRs; expect 10-13 dwords of scratch per lane"
+#endif
 constexpr int kSurfelBlock = 64;   // one wavefront per workgroup (per-wave work varies with the keyframe candidates)
 constexpr int kMaxSumClasses = 8;  // interleaved partial sums per surfel: Intrinsics::sum_classes = 4 or 8 (part of the numerical
                                    // definition, not a tuning knob; 8 exists for keyframe sharding over 8 ranks)
@@ -44,6 +56,28 @@ constexpr int kMaxSumClasses = 8;  // interleaved partial sums per surfel: Intri
 // kWaves > 1: the calling workgroup has kWaves wavefronts holding the same 64 surfels (wavefront w takes the classes
 // w, w + kWaves, ...); every thread must call.
 enum SumsMode { kSumsFused = 0, kSumsProduce = 1, kSumsConsume = 2 };
+
+// Cold per-lane state of the one-wavefront geometry kernel, parked in the workgroup's LDS block [slot][64 lanes] of dwords: a lane reads
+// and writes its own column only (no barrier; lane-contiguous rows: no bank conflict; one base address per lane: ds_read_b32 /
+// ds_write_b32 with the slot as immediate offset).  A parked value comes back as the binary32 word that was stored.
+enum ParkSlot {
+  kParkTotals = 0,    // 8: the class totals of the position pass (tile_sums_parked), touched between the class loops only
+  kParkTangents = 8,  // 6: the tangent points, read once per candidate
+  kParkDesc = 14,     // 2: the surfel's descriptors, read once per associated candidate and by the final update
+  kParkBounds = 16,   // 4: the tile's bounding sphere, read where a chunk of keyframes is tested (chunks beyond the replayed masks)
+  kParkNormal = 20,   // 3: the surfel's normal, read once per candidate (the association test) and by the final update
+  kParkSlots = 23
+};
+constexpr int kMaskChunks = 4;   // (normals_pass: the candidate masks the position pass replays)
+// the block and the candidate masks of BAHIP_GEOMETRY_WAVES workgroups per SIMD fit the compute unit's 160 KiB
+static_assert((kParkSlots * 64 * 4 + kMaxSumClasses * kMaskChunks * 8) * 4 * BAHIP_GEOMETRY_WAVES <= 160 * 1024, "parked state: LDS per workgroup");
+typedef __attribute__((address_space(3))) float ParkedFloat;
+__device__ __forceinline__ ParkedFloat* park_lane(float* block) { return (ParkedFloat*)block + (threadIdx.x & 63); }
+// In front of a group of reads: the compiler must take the column for memory it knows nothing about, or it forwards the stored values to
+// the reads (or hoists the reads out of the candidate loop) and the state is back in registers.  Emits no instruction.
+__device__ __forceinline__ void park_reopen(ParkedFloat*& lane) { asm volatile("" : "+v"(lane)); }
+__device__ __forceinline__ void park_put(ParkedFloat* lane, int slot, float v) { lane[slot * 64] = v; }
+__device__ __forceinline__ float park_get(ParkedFloat* lane, int slot) { return lane[slot * 64]; }
 __device__ __forceinline__ bool position_valid(Vec3 p) { return p.x == p.x; }   // deleted surfels carry NaN x
 static inline unsigned grid_for(uint32_t n) { return xcd_padded_tiles((n + kSurfelBlock - 1) / kSurfelBlock); }   // whole XCD runs
 #if defined(BAHIP_TILE_TIMELINE) && !defined(BAHIP_FAST_MATH)
@@ -122,6 +156,30 @@ __device__ __forceinline__ void tile_sums(float (&tot)[kCount], float* lds, Visi
   }
 }
 
+// tile_sums<1, kCount> (one launch, one wavefront per tile) with the totals parked in LDS between the class loops: the same additions in
+// the same order.
+template <int kCount, typename Visit>
+__device__ __forceinline__ void tile_sums_parked(float (&tot)[kCount], ParkedFloat*& park, int slot, Visit visit, int classes) {
+#pragma unroll
+  for (int q = 0; q < kCount; ++q) park_put(park, slot + q, 0.f);
+#pragma nounroll
+  for (int c = 0; c < classes; ++c) {
+    float acc[kCount];
+#pragma unroll
+    for (int q = 0; q < kCount; ++q) acc[q] = 0.f;
+    visit(acc, c);
+    park_reopen(park);
+    float t[kCount];
+#pragma unroll
+    for (int q = 0; q < kCount; ++q) t[q] = park_get(park, slot + q);
+#pragma unroll
+    for (int q = 0; q < kCount; ++q) park_put(park, slot + q, t[q] + acc[q]);
+  }
+  park_reopen(park);
+#pragma unroll
+  for (int q = 0; q < kCount; ++q) tot[q] = park_get(park, slot + q);
+}
+
 // B/kernel_surfel_activation.cu:38-94
 __global__ void __launch_bounds__(kSurfelBlock) BAHIP_WAVES_ATTR
 activation_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s, uint32_t surfels_size) {
@@ -158,7 +216,6 @@ activation_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, S
 // from the exchanged partials instead of visiting keyframes.
 // Candidate masks of the normals pass, replayed by the position pass of the same tile (wave_cull.h: for_each_candidate_cached): per
 // class kMaskChunks chunks of 64 keyframes (4 classes: 1024 keyframes; beyond that the position pass tests again).
-constexpr int kMaskChunks = 4;
 template <int kWaves, bool kActivate, int kMode = kSumsFused>
 __device__ __forceinline__ void normals_pass(const Intrinsics& in, const KfEntry* __restrict__ kfs, int num_kfs,
                                              const WaveBounds& wb, SurfelsView& s, uint32_t i, bool* live_inout, bool decide,
@@ -246,10 +303,16 @@ normals_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, Surf
 //   2  normals (and activation) finished from the exchanged `cpn`, then the position pass over this rank's classes -> `cpp`;
 //   3  position / descriptor solve from the exchanged `cpp`.
 // Every rank holds all surfels and ends each phase with the same bits (flags and normals after 2, positions after 3).
-template <bool kUseDepth, bool kUseDesc, int kWaves, bool kActivate, int kPhase>
+//
+// kPark (the one-wavefront kernel only): what the candidate loops of the joint solve's position pass do not touch lives in `park_block`
+// (ParkSlot) instead of registers -- parked after the early return and the normals pass, so nothing before them depends on the block;
+// the values, the operations on them and their order are those of kPark == false.
+template <bool kUseDepth, bool kUseDesc, int kWaves, bool kActivate, int kPhase, bool kPark = false>
 __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView& s,
                                               uint32_t activate_count, float* lds, const ClassPartials& cpn, const ClassPartials& cpp,
-                                              uint32_t tile /* workgroup-uniform (kWaves > 1) or wave-uniform */, unsigned long long* replay_masks) {
+                                              uint32_t tile /* workgroup-uniform (kWaves > 1) or wave-uniform */, unsigned long long* replay_masks,
+                                              float* park_block = nullptr) {
+  static_assert(!kPark || (kWaves == 1 && kPhase == 0), "state is parked by the one-wavefront kernel of the whole step only");
   constexpr int kNormalsMode = kPhase == 1 ? kSumsProduce : kPhase == 2 ? kSumsConsume : kSumsFused;
   constexpr int kPositionMode = kPhase == 2 ? kSumsProduce : kPhase == 3 ? kSumsConsume : kSumsFused;
   const int lane = threadIdx.x & 63;
@@ -273,11 +336,32 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
   if (kPhase != 3) normals_pass<kWaves, kActivate, kNormalsMode>(in, kfs, num_kfs, wb, s, ii, &live, decide, gp, &gn, lds, cpn, in_range, masks);
   if (kPhase == 1) return;
 
+  // (the depth-only solve runs at 59 VGPRs: nothing to park)
+  constexpr bool kParked = kPark && kUseDesc;
+  ParkedFloat* park = nullptr;
+  if constexpr (kParked) {
+    park = park_lane(park_block);
+    park_put(park, kParkBounds + 0, wb.cx); park_put(park, kParkBounds + 1, wb.cy);
+    park_put(park, kParkBounds + 2, wb.cz); park_put(park, kParkBounds + 3, wb.r);
+  }
   auto cand = [&](int k) {
     float f[12];
     int32_t activation;
     load_candidate(kfs[k].pose.F, &kfs[k].activation, f, &activation);
-    return activation != BAHIP_KF_INACTIVE && sphere_may_project(in, f, wb);
+    if constexpr (kParked) {
+      park_reopen(park);
+      WaveBounds b;
+      b.cx = park_get(park, kParkBounds + 0); b.cy = park_get(park, kParkBounds + 1);
+      b.cz = park_get(park, kParkBounds + 2); b.r = park_get(park, kParkBounds + 3);
+      // the norms of the frustum planes depend on the intrinsics alone: left to the compiler they are computed once per launch and held
+      // in six VGPRs across the candidate loops, for a test that runs once per 64 keyframes beyond the replayed masks
+      // (an opaque copy of what the test reads makes them part of the test again)
+      Intrinsics opaque = in;
+      asm volatile("" : "+s"(opaque.fx), "+s"(opaque.fy), "+s"(opaque.cx), "+s"(opaque.cy), "+s"(opaque.width), "+s"(opaque.height));
+      return activation != BAHIP_KF_INACTIVE && sphere_may_project(opaque, f, b);
+    } else {
+      return activation != BAHIP_KF_INACTIVE && sphere_may_project(in, f, wb);
+    }
   };
 
   if (!kUseDesc) {
@@ -314,8 +398,41 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
   const float d1 = s.row(kSurfelDescriptor1)[ii];
   const float d2 = s.row(kSurfelDescriptor2)[ii];
   const TangentPoints tp = surfel_tangent_points(gp, gn, radius_sq);
+  if constexpr (kParked) {
+    park_put(park, kParkTangents + 0, tp.q1.x); park_put(park, kParkTangents + 1, tp.q1.y); park_put(park, kParkTangents + 2, tp.q1.z);
+    park_put(park, kParkTangents + 3, tp.q2.x); park_put(park, kParkTangents + 4, tp.q2.y); park_put(park, kParkTangents + 5, tp.q2.z);
+    park_put(park, kParkDesc + 0, d1); park_put(park, kParkDesc + 1, d2);
+    park_put(park, kParkNormal + 0, gn.x); park_put(park, kParkNormal + 1, gn.y); park_put(park, kParkNormal + 2, gn.z);
+  }
+  // What the candidates and the final update read of the surfel: filled into `back` from the block where the state is parked (after a
+  // park_reopen), else the registers themselves -- by reference, so that the unparked shapes compile to the code they had.
+  auto tangents = [&](TangentPoints& back) -> const TangentPoints& {
+    if constexpr (kParked) {
+      back.q1 = mk3(park_get(park, kParkTangents + 0), park_get(park, kParkTangents + 1), park_get(park, kParkTangents + 2));
+      back.q2 = mk3(park_get(park, kParkTangents + 3), park_get(park, kParkTangents + 4), park_get(park, kParkTangents + 5));
+      return back;
+    } else {
+      return tp;
+    }
+  };
+  auto normal = [&](Vec3& back) -> const Vec3& {
+    if constexpr (kParked) {
+      back = mk3(park_get(park, kParkNormal + 0), park_get(park, kParkNormal + 1), park_get(park, kParkNormal + 2));
+      return back;
+    } else {
+      return gn;
+    }
+  };
+  auto descriptors = [&](float (&back)[2]) -> const float* {   // (null: d1, d2)
+    if constexpr (kParked) {
+      back[0] = park_get(park, kParkDesc + 0); back[1] = park_get(park, kParkDesc + 1);
+      return back;
+    } else {
+      return nullptr;
+    }
+  };
   float tot[8];   // a0 a1 a2 a3 a5 a6 a7 a8 of B/kernel_opt_geometry.cu:119-230 (a4 = H12 is exactly 0)
-  tile_sums<kWaves, 8, kPositionMode>(tot, lds, [&](float (&acc)[8], int cls) {
+  auto position_visit = [&](float (&acc)[8], int cls) {
     float &a0 = acc[0], &a1 = acc[1], &a2 = acc[2], &a3 = acc[3], &a5 = acc[4], &a6 = acc[5], &a7 = acc[6], &a8 = acc[7];
     // Two-stage candidate loop for the pixel word (wave_cull.h: for_each_candidate_pipelined): candidate k + 1 is projected and its
     // geometry word requested before candidate k is worked on; the footprint gathers stay where they were, behind the start of the
@@ -332,9 +449,14 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
       const float* F = kfs[k].pose.F;
       const Projected& p = st.p;
       const PixelWords& pix = st.pix;
-      const DescWords dw = load_descriptor_words(in, kfs[k].lumafp, F, tp, p);
+      if constexpr (kParked) park_reopen(park);   // read ahead of the candidate's scalar loads: the wait for those covers the reads
+      TangentPoints tp_back;
+      Vec3 gn_back;
+      const TangentPoints& tpk = tangents(tp_back);
+      const Vec3& gnk = normal(gn_back);
+      const DescWords dw = load_descriptor_words(in, kfs[k].lumafp, F, tpk, p);
       Assoc r;
-      const bool associated = live && associate_from_words<false>(in, F, gn, p, pix, &r, nullptr);
+      const bool associated = live && associate_from_words<false>(in, F, gnk, p, pix, &r, nullptr);
 #ifdef BAHIP_PIN_POSITION
       gathers_arrived(pix, dw);   // measured: -9 % on this pass (the footprint gathers of pairs that fail the association cost more than the second round trip saves here)
 #endif
@@ -350,7 +472,10 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
       }
       if (dw.color_ok) {
         DescEval e;
-        eval_descriptor_from_words(in, kfs[k].lumafp, dw, d1, d2, &e);
+        if constexpr (kParked) park_reopen(park);
+        float d_back[2];
+        const float* dk = descriptors(d_back);
+        eval_descriptor_from_words(in, kfs[k].lumafp, dw, dk ? dk[0] : d1, dk ? dk[1] : d2, &e);
         const float jp1 = jac_descriptor_surfel(r.nl, r.local, r.inv_z, e.gx1, e.gy1, in.cfx, in.cfy);
         const float jp2 = jac_descriptor_surfel(r.nl, r.local, r.inv_z, e.gx2, e.gy2, in.cfx, in.cfy);
         const float jd = -1.f;
@@ -374,7 +499,9 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
     else
       for_each_candidate_cached(num_kfs, cand, [&](int k) { finish_pair(k, start_pair(k)); }, in.sum_classes, cls,
                                 masks ? masks + cls * kMaskChunks : nullptr, masks ? kMaskChunks : 0, masks != nullptr);
-  }, in.sum_classes, cpp, ii, in_range);
+  };
+  if constexpr (kParked) tile_sums_parked<8>(tot, park, kParkTotals, position_visit, in.sum_classes);
+  else tile_sums<kWaves, 8, kPositionMode>(tot, lds, position_visit, in.sum_classes, cpp, ii, in_range);
   if (kPhase == 2 || !live || !writer) return;
   const float a0 = tot[0], a1 = tot[1], a2 = tot[2], a3 = tot[3], a5 = tot[4], a6 = tot[5], a7 = tot[6], a8 = tot[7];
 
@@ -392,29 +519,41 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
   const float x2 = y2 / H22;
   const float x1 = (y1 - H12 * x2) / H11;
   const float x0 = (y0 - H02 * x2 - H01 * x1) / H00;
-  if (x0 != 0) {
-    const Vec3 np = gp - x0 * gn;
-    s.row(kSurfelX)[i] = np.x; s.row(kSurfelY)[i] = np.y; s.row(kSurfelZ)[i] = np.z;
+  // what the updates read: (kParked) the index rebuilt from the tile and the lane number, not held in a register across the passes
+  uint32_t iu = i;
+  if constexpr (kParked) {
+    iu = tile * kSurfelBlock + __lane_id();
+    park_reopen(park);
   }
-  if (x1 != 0) s.row(kSurfelDescriptor1)[i] = fmaxf(-180.f, fminf(180.f, d1 - x1));
-  if (x2 != 0) s.row(kSurfelDescriptor2)[i] = fmaxf(-180.f, fminf(180.f, d2 - x2));
+  Vec3 gn_back;
+  float d_back[2];
+  const Vec3& gnu = normal(gn_back);
+  const float* du = descriptors(d_back);
+  const float d1u = du ? du[0] : d1, d2u = du ? du[1] : d2;
+  if (x0 != 0) {
+    const Vec3 np = gp - x0 * gnu;
+    s.row(kSurfelX)[iu] = np.x; s.row(kSurfelY)[iu] = np.y; s.row(kSurfelZ)[iu] = np.z;
+  }
+  if (x1 != 0) s.row(kSurfelDescriptor1)[iu] = fmaxf(-180.f, fminf(180.f, d1u - x1));
+  if (x2 != 0) s.row(kSurfelDescriptor2)[iu] = fmaxf(-180.f, fminf(180.f, d2u - x2));
 }
 
 
 template <bool kUseDepth, bool kUseDesc, int kWaves, bool kActivate>
-__global__ void __launch_bounds__(64 * kWaves) BAHIP_WAVES_ATTR
+__global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(kWaves == 1 ? BAHIP_GEOMETRY_WAVES : 4)))
 geometry_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s, uint32_t activate_count,
                 const uint32_t* __restrict__ sched, const int* __restrict__ stop /* device-driven BA loop (capi_ba.hip:
                 bahip_alternating_iterations): a launch queued behind the iteration that ended the loop does nothing; NULL: always runs */) {
   __shared__ float lds[kWaves == 1 ? 1 : kMaxSumClasses * 8 * 64];
   __shared__ unsigned long long candidate_masks[kWaves == 1 ? kMaxSumClasses * kMaskChunks : 1];
+  __shared__ float parked[kWaves == 1 ? kParkSlots * 64 : 1];   // (ParkSlot; the depth-only solve parks nothing and gets no block)
   if (stop && load_global(stop) != 0) return;
 #ifdef BAHIP_RECORD_GEOMETRY_TIMELINE
   const unsigned long long t0 = wall_clock64();
 #endif
   uint32_t tile;   // heavy work first (wave_cull.h: scheduled_tile); workgroup-uniform
   if (!scheduled_tile(blockIdx.x, gridDim.x - (sched ? kHeavySlots : 0u), sched, &tile)) return;
-  geometry_step<kUseDepth, kUseDesc, kWaves, kActivate, 0>(in, kfs, num_kfs, s, activate_count, lds, ClassPartials{}, ClassPartials{}, tile, candidate_masks);
+  geometry_step<kUseDepth, kUseDesc, kWaves, kActivate, 0, kWaves == 1>(in, kfs, num_kfs, s, activate_count, lds, ClassPartials{}, ClassPartials{}, tile, candidate_masks, parked);
 #ifdef BAHIP_RECORD_GEOMETRY_TIMELINE
   if (threadIdx.x == 0 && blockIdx.x < 65536) { g_geometry_timeline[blockIdx.x][0] = t0; g_geometry_timeline[blockIdx.x][1] = wall_clock64(); }
 #endif
