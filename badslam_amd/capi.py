@@ -104,6 +104,10 @@ class GeometryStepStats(C.Structure):   # bahip_geometry_step_stats
                 ("rejected_pairs", C.c_uint32), ("trials", C.c_int)]
 
 
+class IntrinsicsStepControl(C.Structure):   # bahip_intrinsics_step_control: step control of the intrinsics step (bahip_optimize_intrinsics_controlled)
+    _fields_ = [("lambda_first", C.c_float), ("lambda_up", C.c_float), ("lambda_max", C.c_float), ("max_trials", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol declared in include/badslam_hip.h
@@ -235,6 +239,13 @@ SIGNATURES = {
                                                                C.c_longlong, C.c_void_p, C.POINTER(GeometryStepStats)]),
     "bahip_debug_read_geometry_sums": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "bahip_debug_geometry_trial_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "bahip_optimize_intrinsics_controlled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(IntrinsicsStepControl),
+                                                       C.POINTER(Surfels), C.POINTER(C.c_float), C.POINTER(Camera), C.POINTER(Camera),
+                                                       C.POINTER(C.c_float), C.c_int, C.POINTER(Cost), C.POINTER(Cost), C.POINTER(C.c_int),
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "bahip_debug_intrinsics_solve_damped": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                      C.POINTER(C.c_float)]),
+    "bahip_debug_intrinsics_trial_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

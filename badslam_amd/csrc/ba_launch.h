@@ -549,4 +549,14 @@ void launch_geometry_trial_decide(hipStream_t st, const SurfelsView& s, const Su
 void launch_geometry_trial_finish(hipStream_t st, uint32_t size, const GeometryTrialState& state, uint8_t* out /* may be NULL */);
 void launch_geometry_trial_restore(hipStream_t st, const SurfelsView& s, const GeometryTrialState& state);
 
+// kernels_intrinsics_trial.hip: the intrinsics step under step control.  The damped Schur complement from the binary64 sums the sweep
+// left (arguments and scratch as launch_intrinsics_finish; lambda = 0: its bits), the back-substitution from a source plane into a
+// destination plane, and the copy of a pitched plane that leaves the padding alone.
+constexpr int kIntrinsicsTrialBlock = 256;
+void launch_intrinsics_trial_schur(hipStream_t st, bool schur, int S, float lambda, const double* glob_d, const double* cells_d, float* glob_f,
+                                   float* cells_f, float* partials);
+void launch_intrinsics_trial_backsub(hipStream_t st, int cf_width, int S, const float* cells_f, const float* x1, const float* src,
+                                     uint32_t src_pitch, float* dst, uint32_t dst_pitch);
+void launch_intrinsics_trial_plane_copy(hipStream_t st, int width, int height, const float* src, uint32_t src_pitch, float* dst, uint32_t dst_pitch);
+
 }  // namespace bahip

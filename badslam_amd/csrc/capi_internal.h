@@ -11,6 +11,7 @@
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
 //   capi_geometry_trial.hip step control of the geometry phase of the alternating scheme
+//   capi_intrinsics_trial.hip step control of the intrinsics step of the alternating scheme
 // Ownership: every block of device or page-locked memory the boundary allocates for itself is a DeviceBuffer / PinnedBuffer
 // (capi_buffers.h) -- a member of bahip_context, of bahip_frame_planes or of an UploadStage, or a local of a test hook -- and is freed
 // with its owner; a unit grows one with reserve().  Only memory handed to the caller (bahip_malloc_pitch, bahip_host_alloc) is raw.
@@ -199,6 +200,9 @@ struct bahip_context {
   uint32_t geometry_trial_size = 0, geometry_trial_stride = 0;
   int geometry_trial_timing = 0;         // bahip_debug_geometry_trial_timing
   double geometry_trial_ms[4] = {};
+  DeviceBuffer<float> intrinsics_trial;  // bahip_optimize_intrinsics_controlled: the saved cfactor plane (rows of cf_width words, no padding)
+  double intrinsics_trial_ms[4] = {};    // bahip_debug_intrinsics_trial_timing: sweep, cost sweeps, solve + back-substitution, host waits
+  int intrinsics_trial_timing = 0;
   int world = 0;                   // ranks of the RCCL communicator (0 = none)
   int kf_rank = 0, kf_world = 1;   // keyframe sharding (bahip_context_set_keyframe_sharding): keyframe k lives on rank k % kf_world (1, 2, 4 or 8)
   int arithmetic = 0;              // BAHIP_ARITHMETIC_EXACT / _FAST: flavour of the sweeps (bahip_context_set_arithmetic), mirrored in in.fast_math
@@ -270,6 +274,21 @@ int run_pose_rounds(bahip_context* ctx, bool use_depth, bool use_desc, const KfE
                     device-driven loop hands over a phase that needs more rounds than it had queued) */,
                     const PoseLoopControl* loop_stats = nullptr /* keeps the loop's totals going (never ends a phase) */);
 int geometry_keyframe_sharded(bahip_context* ctx, bool use_depth, bool use_desc, const SurfelsView& v, long long activate_count);
+
+// ---- defined in capi_solvers.hip ------------------------------------------------------------------------------------------------
+// What the accumulate part of the intrinsics step leaves: the binary64 sums (after the exchange over the ranks) and the scratch of the
+// Schur complement, all inside ctx->intr_scratch; and what the record buffers' bookkeeping needs once the stream has been waited for.
+struct IntrinsicsSweep {
+  bool swept = false;   // false: nothing was swept (no surfels and no sharding); nothing below is set
+  int S = 0;            // sparse cells
+  double* glob_d = nullptr; double* cells_d = nullptr;
+  float* glob = nullptr; float* cells = nullptr; float* partials = nullptr;
+  uint32_t bin_capacity = 0;
+  int num_bins = 0, slices = 1;
+};
+int intrinsics_accumulate(bahip_context* ctx, int optimize_depth, int optimize_color, const bahip_surfels* surfels,
+                          bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a, IntrinsicsSweep* sweep);
+void intrinsics_accumulate_done(bahip_context* ctx, const IntrinsicsSweep& sweep);
 
 // ---- defined in capi_rccl.hip ---------------------------------------------------------------------------------------------------
 int reduce_over_ranks(bahip_context* ctx, void* buffer, size_t count, int dtype);

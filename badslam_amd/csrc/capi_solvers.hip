@@ -5,9 +5,13 @@
 using namespace bahip;
 using namespace bahip_capi;
 
-extern "C" {
-int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimize_color, const bahip_surfels* surfels,
-                              bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a) {
+namespace bahip_capi {
+// The accumulate part of the intrinsics step: argument checks, buffers, the sweep in its slices with the reduction of the binned
+// records, and the exchange over the ranks.  Afterwards the binary64 sums are in the context's scratch (sweep->glob_d, sweep->cells_d),
+// the stream has NOT been waited for, and timer 4 is still open.  sweep->swept == false: nothing to sweep, the out_* values stand.
+int intrinsics_accumulate(bahip_context* ctx, int optimize_depth, int optimize_color, const bahip_surfels* surfels,
+                          bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a, IntrinsicsSweep* sweep) {
+  *sweep = IntrinsicsSweep{};
   if (kf_sharded(ctx)) {
     // a rank sweeps whole classes of the global sums (kernels_intrinsics.hip: "DEFINITION"); the per-cell sums need nothing
     REQUIRE(is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator");
@@ -147,7 +151,31 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
   }
   if (reduce_over_ranks(ctx, glob_d, 64 + 8 * (size_t)S, BAHIP_SUM_F64)) return 1;
   ctx->intr_sums_cells = S;
-  launch_intrinsics_finish(ctx->stream, optimize_depth != 0, S, glob_d, cells_d, glob, cells, partials);
+  *sweep = IntrinsicsSweep{true, S, glob_d, cells_d, glob, cells, partials, bins.capacity, num_bins, slices};
+  return 0;
+}
+// After the host has waited for the stream: what the sweep's record counts say about the buffers of the next call.
+void intrinsics_accumulate_done(bahip_context* ctx, const IntrinsicsSweep& sweep) {
+  ctx->intr_bin_rows = sweep.bin_capacity ? sweep.slices : 0;
+  if (sweep.bin_capacity) {
+    uint32_t most = 0;
+    for (size_t b = 0; b < (size_t)sweep.num_bins * (size_t)sweep.slices; ++b) most = std::max(most, ctx->intr_bin_counts_host[b]);
+    if (most > sweep.bin_capacity) ctx->intr_bin_wanted = std::max(ctx->intr_bin_wanted, most + most / 4 + 1024);   // the next call regrows
+    ctx->intr_bin_last_overflow = most > sweep.bin_capacity ? 1 : 0;
+  }
+}
+}  // namespace bahip_capi
+
+extern "C" {
+int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimize_color, const bahip_surfels* surfels,
+                              bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a) {
+  IntrinsicsSweep sweep;
+  if (intrinsics_accumulate(ctx, optimize_depth, optimize_color, surfels, out_color_camera, out_depth_camera, out_a, &sweep)) return 1;
+  if (!sweep.swept) return 0;
+  const int S = sweep.S;
+  float* const glob = sweep.glob;
+  float* const cells = sweep.cells;
+  launch_intrinsics_finish(ctx->stream, optimize_depth != 0, S, sweep.glob_d, sweep.cells_d, glob, cells, sweep.partials);
   CHECK_LAUNCH();
   timer_end(ctx, 4);   // the sweep and the Schur complement; the 5x5 / 4x4 solves and the cfactor update that follow are tiny
   HIP_TRY(hipMemcpyAsync(ctx->pinned_f, glob, 34 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -156,15 +184,9 @@ int bahip_optimize_intrinsics(bahip_context* ctx, int optimize_depth, int optimi
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const double waited = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (host_timing && waited > 100.0) fprintf(stderr, "[intrinsics step] waited %.1f ms for the stream (capacity %u per buffer)\n", waited, bins.capacity);
+    if (host_timing && waited > 100.0) fprintf(stderr, "[intrinsics step] waited %.1f ms for the stream (capacity %u per buffer)\n", waited, sweep.bin_capacity);
   }
-  ctx->intr_bin_rows = bins.capacity ? slices : 0;
-  if (bins.capacity) {
-    uint32_t most = 0;
-    for (size_t b = 0; b < (size_t)num_bins * (size_t)slices; ++b) most = std::max(most, ctx->intr_bin_counts_host[b]);
-    if (most > bins.capacity) ctx->intr_bin_wanted = std::max(ctx->intr_bin_wanted, most + most / 4 + 1024);   // the next call regrows
-    ctx->intr_bin_last_overflow = most > bins.capacity ? 1 : 0;
-  }
+  intrinsics_accumulate_done(ctx, sweep);
   const float* g = ctx->pinned_f;
   if (optimize_depth) {
     double M[25], rhs[5], x[5];

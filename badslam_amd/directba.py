@@ -18,6 +18,9 @@ _F4 = C.c_float * 4
 _lib = None
 
 
+_CALLBACK = C.CFUNCTYPE(None, C.c_void_p)
+
+
 def _load():
     global _lib
     if _lib is None:
@@ -65,6 +68,13 @@ def _load():
         L.dba_get_pose_step_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float)]
         L.dba_set_geometry_step_control.argtypes = [C.c_void_p, C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_int]
         L.dba_get_geometry_step_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3 + [C.POINTER(C.c_int)]
+        # (an older build under A/B timing, scripts/ab_bench.sh, may lack these newer entry points: as capi.load)
+        if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_set_intrinsics_step_control"):
+            L.dba_set_intrinsics_step_control.argtypes = [C.c_void_p, C.c_int] + [C.c_float] * 3 + [C.c_int]
+            L.dba_set_intrinsics_updated_callback.argtypes = [C.c_void_p, _CALLBACK, C.c_void_p]
+            L.dba_get_intrinsics_step_drops.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+            L.dba_get_intrinsics_step_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float),
+                                                        C.POINTER(C.c_float)]
         L.dba_set_distributed_lifecycle.argtypes = [C.c_void_p, C.c_int]
         L.dba_set_ba_iteration_counts.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dba_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -388,6 +398,42 @@ class DirectBA:
         if self.L.dba_set_geometry_step_control(self.h, 1, v["lambda_initial"], v["lambda_up"], v["lambda_min"], v["lambda_max"],
                                                 int(v["max_trials"]), int(bool(v["guard_pairs"]))) != 0:
             raise RuntimeError("SetGeometryStepControl: a value is out of range")
+
+    def SetIntrinsicsStepControl(self, control=None, **fields):
+        """Step control of the intrinsics step of the alternating scheme (default off): damped trials up the ladder 0, lambda_first,
+        lambda_first * lambda_up, ... lambda_max; the first that lowers the objective strictly is kept, otherwise cameras, a and the
+        cfactor image come back bit for bit.  The damping factor persists across iterations and calls; the intrinsics-updated callback
+        fires only after an accepted step.  control: None / False = off, True = the defaults, or a dict; fields: lambda_first,
+        lambda_up, lambda_max, max_trials.  Allowed under either sharding; raises for values out of range."""
+        if control is None or control is False:
+            if self.L.dba_set_intrinsics_step_control(self.h, 0, 0.0, 0.0, 0.0, 0) != 0:
+                raise RuntimeError("SetIntrinsicsStepControl: could not be switched off")
+            return
+        v = dict(lambda_first=1.0, lambda_up=4.0, lambda_max=1e4, max_trials=4)
+        v.update(control if isinstance(control, dict) else {})
+        v.update(fields)
+        if self.L.dba_set_intrinsics_step_control(self.h, 1, v["lambda_first"], v["lambda_up"], v["lambda_max"], int(v["max_trials"])) != 0:
+            raise RuntimeError("SetIntrinsicsStepControl: a value is out of range")
+
+    def SetIntrinsicsUpdatedCallback(self, callback):
+        """DirectBA::SetIntrinsicsUpdatedCallback: `callback()` is called from BundleAdjustment after an intrinsics step has changed
+        the cameras or the depth parameters (with the step control on: after an accepted step only); None removes it."""
+        self._intrinsics_callback = _CALLBACK(lambda _user: callback()) if callback is not None else C.cast(None, _CALLBACK)
+        self.L.dba_set_intrinsics_updated_callback(self.h, self._intrinsics_callback, None)
+
+    def intrinsics_step_stats(self):
+        """(last_intrinsics_trials, last_intrinsics_accepted, last_intrinsics_lambda, intrinsics_lambda): trials run and steps accepted
+        by the intrinsics steps of the last BundleAdjustment call, the factor of its last accepted step (-1: none), and the factor
+        the next step starts with."""
+        trials, accepted, lam, nxt = C.c_int(), C.c_int(), C.c_float(), C.c_float()
+        self.L.dba_get_intrinsics_step_stats(self.h, C.byref(trials), C.byref(accepted), C.byref(lam), C.byref(nxt))
+        return trials.value, accepted.value, lam.value, nxt.value
+
+    def intrinsics_step_drops(self):
+        """(total, smallest): by how much the accepted intrinsics steps of the last BundleAdjustment call lowered the objective."""
+        total, smallest = C.c_double(), C.c_double()
+        self.L.dba_get_intrinsics_step_drops(self.h, C.byref(total), C.byref(smallest))
+        return total.value, smallest.value
 
     def geometry_step_stats(self):
         """(last_geometry_candidates, last_geometry_accepted, last_geometry_restored, last_geometry_trials): the totals over the geometry

@@ -12,13 +12,15 @@
 //          [--raw_to_float_depth S] [--pcg] [--intrinsics] [--incremental | --parallel_ba] [--save_state F] [--load_state F]
 //          [--ba_call_iterations N] [--baseline_fx F] [--spatial_sort_cell C] [--row_major_creation]
 //          [--bilateral_sigma_xy S] [--bilateral_sigma_inv_depth S] [--bilateral_radius_factor R] [--report_cost]
-//          [--pcg_step_control] [--pose_step_control] [--geometry_step_control]
+//          [--pcg_step_control] [--pose_step_control] [--geometry_step_control] [--intrinsics_step_control]
 //
 // --report_cost: prints the value of the BA objective (DirectBA::ComputeCost: total and the depth / descriptor sums and counts) before
 // the first and after the last BA call.
 // --pose_step_control: without --pcg, damped pose steps kept per keyframe only if its cost falls (DirectBA::SetPoseStepControl, its defaults)
 // --geometry_step_control: without --pcg, damped geometry steps kept per surfel only if its cost falls (DirectBA::SetGeometryStepControl, its
 // defaults)
+// --intrinsics_step_control: with --intrinsics and without --pcg, damped intrinsics steps kept only if the objective falls
+// (DirectBA::SetIntrinsicsStepControl, its defaults); the trials, the accepted steps and the damping factor are printed per BA call.
 // --pcg_step_control: with --pcg, damped steps that are kept only if the objective falls (DirectBA::SetPCGStepControl, its defaults);
 // the trial steps and the undone ones of the last BA call are printed at the end.
 // --ba_call_iterations N: every BA call runs exactly N iterations (min = max = N) instead of 1 .. 10; the remaining options set
@@ -100,6 +102,7 @@ int main(int argc, char** argv) {
   float baseline_fx = 40.f, spatial_sort_cell = -1.f;
   int ba_call_iterations = 0;
   bool row_major_creation = false, report_cost = false, pcg_step_control = false, pose_step_control = false, geometry_step_control = false;
+  bool intrinsics_step_control = false;
   bool use_pcg = false, intrinsics = false, incremental = false, parallel_ba = false;
   std::string save_state, load_state;
   PreprocessConfig config;
@@ -118,6 +121,7 @@ int main(int argc, char** argv) {
     else if (a == "--pcg_step_control") pcg_step_control = true;
     else if (a == "--pose_step_control") pose_step_control = true;
     else if (a == "--geometry_step_control") geometry_step_control = true;
+    else if (a == "--intrinsics_step_control") intrinsics_step_control = true;
     else if (a == "--bilateral_sigma_xy" && i + 1 < argc) config.bilateral_filter_sigma_xy = (float)atof(argv[++i]);
     else if (a == "--bilateral_sigma_inv_depth" && i + 1 < argc) config.bilateral_filter_sigma_inv_depth = (float)atof(argv[++i]);
     else if (a == "--bilateral_radius_factor" && i + 1 < argc) config.bilateral_filter_radius_factor = (float)atof(argv[++i]);
@@ -128,6 +132,10 @@ int main(int argc, char** argv) {
     else if (a == "--save_state" && i + 1 < argc) save_state = argv[++i];
     else if (a == "--load_state" && i + 1 < argc) load_state = argv[++i];
     else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
+  }
+  if (intrinsics_step_control && (!intrinsics || use_pcg)) {
+    fprintf(stderr, "--intrinsics_step_control needs --intrinsics and the alternating scheme (no --pcg)\n");
+    return 2;
   }
   if (bahip_device_count() <= 0) { fprintf(stderr, "no HIP device (there is no CPU fallback)\n"); return 99; }
 
@@ -153,6 +161,10 @@ int main(int argc, char** argv) {
     if (geometry_step_control) {
       const DirectBA::GeometryStepControl control;
       if (!ba.SetGeometryStepControl(&control)) return 2;
+    }
+    if (intrinsics_step_control) {
+      const DirectBA::IntrinsicsStepControl control;
+      if (!ba.SetIntrinsicsStepControl(&control)) return 2;
     }
     if (pcg_step_control) {
       const DirectBA::PCGStepControl control;
@@ -215,6 +227,10 @@ int main(int argc, char** argv) {
         if (geometry_step_control && !use_pcg)
           printf("  geometry step control: %lld candidate(s), %lld accepted, %lld restored, %d trial(s)\n", ba.last_geometry_candidates(),
                  ba.last_geometry_accepted(), ba.last_geometry_restored(), ba.last_geometry_trials());
+        if (intrinsics_step_control)
+          printf("  intrinsics step control: %d trial(s), %d accepted step(s), last accepted lambda %g, next lambda %g, objective lowered by %.9g "
+                 "(smallest drop %.9g)\n", ba.last_intrinsics_trials(), ba.last_intrinsics_accepted(), (double)ba.last_intrinsics_lambda(),
+                 (double)ba.intrinsics_lambda(), ba.last_intrinsics_cost_drop(), ba.last_intrinsics_smallest_drop());
         if (pcg_step_control && use_pcg)
           printf("  step control: %d trial step(s), %d undone, lambda %g\n", ba.last_pcg_trials(), ba.last_pcg_rejected_steps(), (double)ba.last_pcg_lambda());
       }

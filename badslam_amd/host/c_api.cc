@@ -314,6 +314,29 @@ int dba_get_geometry_step_stats(dba_handle* h, long long* candidates, long long*
   if (trials) *trials = h->ba->last_geometry_trials();
   return 0;
 }
+int dba_set_intrinsics_step_control(dba_handle* h, int enabled, float lambda_first, float lambda_up, float lambda_max, int max_trials) {
+  if (!enabled) return h->ba->SetIntrinsicsStepControl(nullptr) ? 0 : 1;
+  vis::DirectBA::IntrinsicsStepControl control;
+  control.lambda_first = lambda_first; control.lambda_up = lambda_up; control.lambda_max = lambda_max; control.max_trials = max_trials;
+  return h->ba->SetIntrinsicsStepControl(&control) ? 0 : 1;
+}
+int dba_set_intrinsics_updated_callback(dba_handle* h, void (*callback)(void*), void* user) {
+  if (callback) h->ba->SetIntrinsicsUpdatedCallback([callback, user]() { callback(user); });
+  else h->ba->SetIntrinsicsUpdatedCallback(std::function<void()>());
+  return 0;
+}
+int dba_get_intrinsics_step_drops(dba_handle* h, double* total, double* smallest) {
+  if (total) *total = h->ba->last_intrinsics_cost_drop();
+  if (smallest) *smallest = h->ba->last_intrinsics_smallest_drop();
+  return 0;
+}
+int dba_get_intrinsics_step_stats(dba_handle* h, int* trials, int* accepted, float* lambda_accepted, float* lambda_next) {
+  if (trials) *trials = h->ba->last_intrinsics_trials();
+  if (accepted) *accepted = h->ba->last_intrinsics_accepted();
+  if (lambda_accepted) *lambda_accepted = h->ba->last_intrinsics_lambda();
+  if (lambda_next) *lambda_next = h->ba->intrinsics_lambda();
+  return 0;
+}
 int dba_set_distributed_lifecycle(dba_handle* h, int enabled) { return h->ba->SetDistributedLifecycle(enabled != 0) ? 0 : 1; }
 int dba_last_stats(dba_handle* h, int* pose_rounds, int* pose_steps, int* pcg_inner_steps) {
   if (pose_rounds) *pose_rounds = h->ba->last_pose_rounds();

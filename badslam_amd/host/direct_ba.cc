@@ -300,6 +300,22 @@ bool DirectBA::SetGeometryStepControl(const GeometryStepControl* control) {
   return true;
 }
 
+bool DirectBA::SetIntrinsicsStepControl(const IntrinsicsStepControl* control) {
+  if (!control) {
+    intrinsics_step_control_on_ = false;
+    return true;
+  }
+  // (the checks of bahip_optimize_intrinsics_controlled, which would otherwise refuse in the middle of BundleAdjustment)
+  if (!(control->max_trials >= 1 && std::isfinite(control->lambda_first) && control->lambda_first > 0.f && std::isfinite(control->lambda_up) &&
+        control->lambda_up > 1.f && std::isfinite(control->lambda_max) && control->lambda_first <= control->lambda_max)) {
+    LOG(ERROR) << "SetIntrinsicsStepControl: needs max_trials >= 1, finite lambda_first > 0, finite lambda_up > 1, lambda_first <= finite lambda_max";
+    return false;
+  }
+  intrinsics_step_control_ = *control;
+  intrinsics_step_control_on_ = true;
+  return true;
+}
+
 bool DirectBA::SetDistributedLifecycle(bool enabled) {
   if (enabled && keyframe_shard_world_ > 1) {
     LOG(ERROR) << "SetDistributedLifecycle: keyframe sharding deals its lifecycle by keyframe already";
@@ -570,6 +586,9 @@ void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsi
   last_pose_rounds_ = last_pose_steps_ = last_pcg_inner_steps_ = last_pcg_trials_ = last_pcg_rejected_steps_ = last_pose_trials_ = last_pose_rejected_steps_ = 0;
   last_geometry_candidates_ = last_geometry_accepted_ = last_geometry_restored_ = 0;
   last_geometry_trials_ = 0;
+  last_intrinsics_trials_ = last_intrinsics_accepted_ = 0;
+  last_intrinsics_lambda_ = -1.f;
+  last_intrinsics_cost_drop_ = last_intrinsics_smallest_drop_ = 0;
   if (keyframe_shard_world_ > 1)
     CHECK(batched_creation_ || (!do_surfel_updates && !increase_ba_iteration_count))
         << "keyframe sharding runs the surfel lifecycle through the batched calls only (SetBatchedCreation(true))";
@@ -754,6 +773,8 @@ void DirectBA::BundleAdjustmentAlternating(hipStream_t stream, bool optimize_dep
               t_after_loop - t_before_loop, now() - t_after_loop);
   }
 
+  bool have_intrinsics_cost = false;   // intrinsics step control: the objective after the previous controlled step of this call
+  bahip_cost intrinsics_cost{};
   for (int iteration = 0; iteration < max_iterations && !device_loop_done; ++iteration) {
     if (progress_function) {
       apply_pending();   // the callback may look at the keyframes
@@ -917,7 +938,42 @@ void DirectBA::BundleAdjustmentAlternating(hipStream_t stream, bool optimize_dep
     }
 
     // --- intrinsics ---
-    if (optimize_depth_intrinsics || optimize_color_intrinsics) {
+    if ((optimize_depth_intrinsics || optimize_color_intrinsics) && intrinsics_step_control_on_) {
+      // the same step under step control: damped trials, the first that lowers the objective is kept (the backend context then holds
+      // the new cameras / depth parameters already), otherwise nothing changes
+      const bahip_intrinsics_step_control control{intrinsics_step_control_.lambda_first, intrinsics_step_control_.lambda_up,
+                                                  intrinsics_step_control_.lambda_max, intrinsics_step_control_.max_trials};
+      bahip_camera out_color, out_depth;
+      float out_a = depth_params_.a, lambda_accepted = 0.f;
+      int trials = 0, accepted = 0;
+      // the previous controlled step's cost_after is this step's cost_before only if nothing touched the state in between
+      const bool reuse_cost = have_intrinsics_cost && !optimize_poses && !optimize_geometry && !do_surfel_updates;
+      bahip_cost cost_before = intrinsics_cost, cost_after{};
+      const bahip_surfels s = SurfelsStruct();
+      BAHIP_CHECKED_CALL(bahip_optimize_intrinsics_controlled(ctx_, optimize_depth_intrinsics, optimize_color_intrinsics, use_depth_residuals_,
+                                                              use_descriptor_residuals_, &control, &s, &intrinsics_lambda_, &out_color, &out_depth,
+                                                              &out_a, reuse_cost ? 1 : 0, &cost_before, &cost_after, &trials, &accepted,
+                                                              &lambda_accepted));
+      intrinsics_cost = cost_after;
+      have_intrinsics_cost = true;
+      last_intrinsics_trials_ += trials;
+      if (accepted) {
+        const double drop = ((cost_before.depth + cost_before.descriptor_1) + cost_before.descriptor_2) -
+                            ((cost_after.depth + cost_after.descriptor_1) + cost_after.descriptor_2);
+        last_intrinsics_smallest_drop_ = last_intrinsics_accepted_ ? std::min(last_intrinsics_smallest_drop_, drop) : drop;
+        last_intrinsics_cost_drop_ += drop;
+        ++last_intrinsics_accepted_;
+        last_intrinsics_lambda_ = lambda_accepted;
+        Lock();
+        if (optimize_color_intrinsics) color_camera_ = PinholeCamera4f(out_color.width, out_color.height, &out_color.fx);
+        if (optimize_depth_intrinsics) {
+          depth_camera_ = PinholeCamera4f(out_depth.width, out_depth.height, &out_depth.fx);
+          depth_params_.a = out_a;
+        }
+        Unlock();
+        if (intrinsics_updated_callback_) { apply_pending(); intrinsics_updated_callback_(); }
+      }
+    } else if (optimize_depth_intrinsics || optimize_color_intrinsics) {
       bahip_camera out_color, out_depth;
       float out_a = depth_params_.a;
       const bahip_surfels s = SurfelsStruct();

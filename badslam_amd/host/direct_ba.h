@@ -211,6 +211,29 @@ class DirectBA {
   long long last_geometry_accepted() const { return last_geometry_accepted_; }
   long long last_geometry_restored() const { return last_geometry_restored_; }
   int last_geometry_trials() const { return last_geometry_trials_; }
+  // Step control of the intrinsics step of the alternating scheme (ours; default off = NULL: every update is applied, as the reference
+  // does).  On: the intrinsics step of BundleAdjustment(!use_pcg) is bahip_optimize_intrinsics_controlled -- damped trials up a ladder
+  // of factors (0, lambda_first, lambda_first * lambda_up, ... lambda_max), the first one that lowers the objective
+  // (bahip_evaluate_cost) strictly is kept, otherwise cameras, a and the cfactor image come back bit for bit; depth and colour updates
+  // are kept or undone together.  The factor persists across iterations and calls (an accepted step at l leaves l / lambda_up, a
+  // rejected ladder the next rung).  intrinsics_updated_callback is called only after an accepted step.  Allowed under either sharding
+  // (keyframe sharding: the plain step's condition on the class count).
+  struct IntrinsicsStepControl {
+    float lambda_first = 1.f, lambda_up = 4.f, lambda_max = 1e4f;
+    int max_trials = 4;
+  };
+  bool SetIntrinsicsStepControl(const IntrinsicsStepControl* control);
+  bool intrinsics_step_control() const { return intrinsics_step_control_on_; }
+  // over the intrinsics steps of the last BundleAdjustment() call: trials run, steps accepted, the factor of the last accepted step
+  // (-1: none was accepted); and the factor the next step starts with
+  int last_intrinsics_trials() const { return last_intrinsics_trials_; }
+  int last_intrinsics_accepted() const { return last_intrinsics_accepted_; }
+  float last_intrinsics_lambda() const { return last_intrinsics_lambda_; }
+  float intrinsics_lambda() const { return intrinsics_lambda_; }
+  // ... and by how much those accepted steps lowered the objective (depth + descriptor_1 + descriptor_2): in total, and the smallest
+  // drop of one step (0 when none was accepted; positive otherwise, by the accept rule)
+  double last_intrinsics_cost_drop() const { return last_intrinsics_cost_drop_; }
+  double last_intrinsics_smallest_drop() const { return last_intrinsics_smallest_drop_; }
   // Multi-GPU surfel sharding: sums of the per-keyframe normal equations go through this hook
   // (see include/badslam_hip.h, bahip_allreduce_fn).
   void SetAllReduce(bahip_allreduce_fn fn, void* user) { BAHIP_CHECKED_CALL(bahip_context_set_allreduce(ctx_, fn, user)); }
@@ -344,6 +367,12 @@ class DirectBA {
   GeometryStepControl geometry_step_control_;
   long long last_geometry_candidates_ = 0, last_geometry_accepted_ = 0, last_geometry_restored_ = 0;
   int last_geometry_trials_ = 0;
+  bool intrinsics_step_control_on_ = false;
+  IntrinsicsStepControl intrinsics_step_control_;
+  float intrinsics_lambda_ = 0.f;            // the factor the next controlled intrinsics step starts with
+  int last_intrinsics_trials_ = 0, last_intrinsics_accepted_ = 0;
+  float last_intrinsics_lambda_ = -1.f;
+  double last_intrinsics_cost_drop_ = 0, last_intrinsics_smallest_drop_ = 0;
   bool distributed_lifecycle_ = false;   // SetDistributedLifecycle
   int pcg_sum_classes_ = 1;        // (SetPCGSumClasses: the windowed scheme needs 1)
   int shard_rank_ = 0, shard_world_ = 1, whole_cloud_depth_ = 0;

@@ -476,6 +476,58 @@ class Scene:
             self.set_intrinsics()
         return cc, dc, a.value
 
+    INTRINSICS_STEP_CONTROL = dict(lambda_first=1.0, lambda_up=4.0, lambda_max=1e4, max_trials=4)
+
+    def optimize_intrinsics_controlled(self, lam, optimize_depth=True, optimize_color=True, use_depth=True, use_desc=True, control=None,
+                                       cost_before=None):
+        """One intrinsics step of the alternating scheme under step control (bahip_optimize_intrinsics_controlled) starting at the
+        damping factor `lam`; control: a dict overriding fields of INTRINSICS_STEP_CONTROL (the defaults of
+        DirectBA::IntrinsicsStepControl); cost_before: a capi.Cost of the current state, or None to have it evaluated.  Adopts the
+        cameras and a the call leaves (the context keeps them itself).  Returns a dict: lam (the next call's), accepted, trials,
+        lambda_accepted, color_camera / depth_camera (fx, fy, cx, cy as binary32), a (binary32), cost_before, cost_after (dicts like
+        evaluate_cost's) and cost_after_struct (to pass on as the next call's cost_before)."""
+        fields = dict(self.INTRINSICS_STEP_CONTROL)
+        fields.update(control or {})
+        ctl = capi.IntrinsicsStepControl(float(fields["lambda_first"]), float(fields["lambda_up"]), float(fields["lambda_max"]),
+                                         int(fields["max_trials"]))
+        cc, dc, a = capi.Camera(), capi.Camera(), C.c_float()
+        ran, accepted = C.c_int(), C.c_int()
+        lam_io, lam_accepted = C.c_float(float(lam)), C.c_float()
+        before = capi.Cost() if cost_before is None else cost_before
+        after = capi.Cost()
+        s = self.surfels_struct()
+        capi.check(self.lib.bahip_optimize_intrinsics_controlled(
+            self.ctx.handle, int(optimize_depth), int(optimize_color), int(use_depth), int(use_desc), C.byref(ctl), C.byref(s),
+            C.byref(lam_io), C.byref(cc), C.byref(dc), C.byref(a), int(cost_before is not None), C.byref(before), C.byref(after),
+            C.byref(ran), C.byref(accepted), C.byref(lam_accepted)))
+        if accepted.value:
+            if optimize_color:
+                self.color_cam = cc
+            if optimize_depth:
+                self.depth_cam = dc
+                self.dp.a = a.value
+        cam = lambda c: np.array([c.fx, c.fy, c.cx, c.cy], np.float32)
+        return {"lam": float(lam_io.value), "accepted": bool(accepted.value), "trials": ran.value,
+                "lambda_accepted": float(lam_accepted.value), "color_camera": cam(cc), "depth_camera": cam(dc),
+                "a": np.float32(a.value), "cost_before": cost_dict(before), "cost_after": cost_dict(after), "cost_after_struct": after}
+
+    def intrinsics_solve_damped(self, lam, optimize_depth=True, optimize_color=True, with_cells=True):
+        """The damped solves from the sums of the last intrinsics step (bahip_debug_intrinsics_solve_damped); nothing is applied.
+        Returns (x1[5], xc[4], cells[S, 8] or None) in binary32."""
+        x1, xc = np.zeros(5, np.float32), np.zeros(4, np.float32)
+        cells = np.zeros((self.cf_w * self.cf_h, 8), np.float32) if with_cells and optimize_depth else None
+        fp = lambda arr: arr.ctypes.data_as(C.POINTER(C.c_float))
+        capi.check(self.lib.bahip_debug_intrinsics_solve_damped(self.ctx.handle, int(optimize_depth), int(optimize_color), float(lam),
+                                                                 fp(x1), fp(xc), fp(cells) if cells is not None else None))
+        return x1, xc, cells
+
+    def intrinsics_trial_timing(self, enable):
+        """Switches the host wall-clock split of the controlled intrinsics step on or off and returns the last call's (milliseconds:
+        sweep, cost sweeps, solves + back-substitution + restore, waits for the read-backs; bahip_debug_intrinsics_trial_timing)."""
+        out = (C.c_double * 4)()
+        capi.check(self.lib.bahip_debug_intrinsics_trial_timing(self.ctx.handle, int(bool(enable)), out))
+        return [float(v) for v in out]
+
     def pcg_iteration(self, optimize_poses=True, optimize_geometry=True, optimize_depth_intrinsics=False,
                       optimize_color_intrinsics=False, use_depth=True, use_desc=True, max_inner_iterations=30, gauge_keyframe=0,
                       windowed=False):

@@ -119,6 +119,20 @@ int dba_get_pose_step_stats(dba_handle* h, int* trials, int* rejected_steps, int
 int dba_set_geometry_step_control(dba_handle* h, int enabled, float lambda_initial, float lambda_up, float lambda_min, float lambda_max,
                                   int max_trials, int guard_pairs);
 int dba_get_geometry_step_stats(dba_handle* h, long long* candidates, long long* accepted, long long* restored, int* trials);
+/* DirectBA::SetIntrinsicsStepControl (ours, default off): the intrinsics step of BundleAdjustment(!use_pcg) runs damped trials and keeps
+ * the first that lowers the objective, otherwise nothing changes (bahip_optimize_intrinsics_controlled; the fields are
+ * bahip_intrinsics_step_control's).  enabled = 0: off.  Allowed under either sharding; returns 1 (refused) for values out of range.
+ * The damping factor persists across iterations and calls.  The intrinsics-updated callback fires only after an accepted step.
+ * dba_get_intrinsics_step_stats: trials run and steps accepted in the last BundleAdjustment call, the factor of its last accepted step
+ * (-1: none), and the factor the next step starts with; any may be NULL. */
+int dba_set_intrinsics_step_control(dba_handle* h, int enabled, float lambda_first, float lambda_up, float lambda_max, int max_trials);
+int dba_get_intrinsics_step_stats(dba_handle* h, int* trials, int* accepted, float* lambda_accepted, float* lambda_next);
+/* By how much the accepted steps of the last BundleAdjustment call lowered the objective: in total, and the smallest drop of one step
+ * (both 0 when none was accepted; positive otherwise). */
+int dba_get_intrinsics_step_drops(dba_handle* h, double* total, double* smallest);
+/* DirectBA::SetIntrinsicsUpdatedCallback: called from BundleAdjustment after an intrinsics step has changed the cameras or the depth
+ * parameters (with the step control on: after an accepted step only); NULL removes it. */
+int dba_set_intrinsics_updated_callback(dba_handle* h, void (*callback)(void* user), void* user);
 /* DirectBA::SetSurfelSharding: this object holds rank `rank`'s chunk-cyclic shard of one surfel cloud (bahip_gather_surfel_shards) */
 int dba_set_surfel_sharding(dba_handle* h, int rank, int world, uint32_t chunk);
 /* DirectBA::SetDistributedLifecycle (ours, default off): under surfel sharding the lifecycle's sweeps are dealt over the ranks

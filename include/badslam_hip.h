@@ -763,6 +763,65 @@ int bahip_debug_read_geometry_sums(bahip_context* ctx, float* host_out);
  * for the stream): out[0] phases 1-2, [1] the cost sweeps, [2] snapshot, solve and decide launches, [3] the per-trial read-backs. */
 int bahip_debug_geometry_trial_timing(bahip_context* ctx, int enable, double out[4]);
 
+/* ---- step control for the intrinsics step of the alternating scheme (ours: the reference applies every update;
+ * kernels_intrinsics_trial.hip, DESIGN.md section 3, "Step control of the intrinsics step") ---------------------------------------------
+ * The objective is exactly bahip_evaluate_cost, as in the PCG control: it counts associated pairs only, both counts are returned, no
+ * correction is made.
+ * The ladder of damping factors, in binary32: up(l) = l == 0 ? lambda_first : min(l * lambda_up, lambda_max); down(l): t = l / lambda_up,
+ * t < lambda_first ? 0 : t.  Argument checks: lambda_first > 0, lambda_up > 1, lambda_first <= lambda_max, all finite, max_trials >= 1
+ * (error text, context usable).  Defaults of the upper layers: first 1, up 4, max 1e4, 4 trials.
+ * The damped system for lambda >= 0.  Per sparse cell, from the binary32-rounded cell record, D' = D + lambda * D (one product, one
+ * add, not contracted); everything the plain Schur complement does with D is done with D': the test 1 / D' < 1e12, D'^-1 b2, D'^-1 B,
+ * the 20 partial sums, the xor butterfly per wavefront and the ordered chain of wavefront partials added to the rounded global sums.
+ * On the host, after the prior on a has been added as in the plain step, M_ii <- M_ii + (double)lambda * M_ii for the five diagonal
+ * entries of the reduced 5 x 5 system and the four of the colour 4 x 4 system; then the plain step's LDL^T solves, its update formulas
+ * for the cameras and a, and the back-substitution cfactor = saved_cfactor - (D'^-1 b2 - sum_c D'^-1 B_c x_c), zero where a cell's
+ * observation count is 0.  lambda = 0: every output word equals the plain step's.
+ * One call:
+ *  1. *cost_before = bahip_evaluate_cost(use_depth, use_desc) of the current state -- or, with have_cost_before != 0, taken as the
+ *     caller gives it.
+ *  2. The plain step's sweep, once (its slices, its record buffers, its exchange over the ranks).  The binary64 sums stay in the
+ *     context's scratch (bahip_debug_read_intrinsics_sums); the trials read them and do not change them.
+ *  3. The cfactor plane is saved device to device (its cf_width x cf_height words, whatever the pitch), the cameras and a on the host.
+ *  4. Trials with l = *lambda_inout, then up(l), ...: the damped Schur complement and the read-back of 34 floats, the host solves, the
+ *     back-substitution from the SAVED plane into the live plane, the candidate cameras and a put into the context as
+ *     bahip_set_intrinsics does, and *cost_after = bahip_evaluate_cost.
+ *  5. With f(c) = (c.depth + c.descriptor_1) + c.descriptor_2 in binary64: the trial is accepted iff f(*cost_after) is finite and
+ *     f(*cost_after) < f(*cost_before).  Then *lambda_inout = down(l), *lambda_accepted_out = l, the out_* arguments hold the new values,
+ *     the context keeps them (unlike bahip_optimize_intrinsics, which leaves them to the caller), and the call returns.
+ *  6. Otherwise the plane and the context's intrinsics are written back bit for bit and the next rung runs; the call stops after
+ *     max_trials, or after a rejection at lambda_max.
+ *  7. Without an accepted trial: *accepted_out = 0, *cost_after = *cost_before, the out_* arguments are the context's unchanged values
+ *     and *lambda_inout = up(last l tried).
+ * An error inside a trial (a failed exchange, say) restores the state before it returns.  No bound keyframe, or surfels_size == 0
+ * without sharding: nothing is swept, *accepted_out = 0, *trials_out = 0.  Depth and colour updates of one call are accepted or rejected
+ * together.  Synchronises.
+ * Surfel sharding: the sums and the cost total have the same bits on every rank, so every rank takes the same branch and ends with one
+ * GPU's bits.  Keyframe sharding: under the plain step's own condition (bahip_context_set_intrinsics_sum_classes >= ranks).
+ * The sweep and the cost run in the context's arithmetic flavour; the per-cell kernels of the trials exist once, exact. */
+typedef struct bahip_intrinsics_step_control {
+  float lambda_first;   /* the first non-zero rung; finite, > 0 */
+  float lambda_up;      /* finite, > 1 */
+  float lambda_max;     /* finite, >= lambda_first */
+  int   max_trials;     /* >= 1 */
+} bahip_intrinsics_step_control;
+int bahip_optimize_intrinsics_controlled(bahip_context* ctx, int optimize_depth_intrinsics, int optimize_color_intrinsics,
+                                         int use_depth_residuals, int use_descriptor_residuals,
+                                         const bahip_intrinsics_step_control* control, const bahip_surfels* surfels, float* lambda_inout,
+                                         bahip_camera* out_color_camera, bahip_camera* out_depth_camera, float* out_a, int have_cost_before,
+                                         bahip_cost* cost_before, bahip_cost* cost_after, int* trials_out, int* accepted_out,
+                                         float* lambda_accepted_out);
+/* The damped solves from the sums the last intrinsics step (plain or controlled) left in the context, at the context's intrinsics:
+ * x1_out the update of the reduced 5 x 5 system, xc_out of the colour system (zeros for a system that is not optimised),
+ * cells_after_out (NULL or 8 S floats; depth only) the per-cell table after the damped Schur complement {D'^-1 B0..B4, D'^-1 b2 or NaN,
+ * b2, observation count}.  Nothing is applied. */
+int bahip_debug_intrinsics_solve_damped(bahip_context* ctx, int optimize_depth_intrinsics, int optimize_color_intrinsics, float lambda,
+                                        float x1_out[5], float xc_out[4], float* cells_after_out);
+/* Host wall-clock split of the last controlled call, in milliseconds, when on (off by default; each part is then followed by a wait
+ * for the stream): out[0] the sweep, [1] the cost sweeps, [2] Schur complement, solves, back-substitution and restore, [3] the waits
+ * for the per-trial read-backs. */
+int bahip_debug_intrinsics_trial_timing(bahip_context* ctx, int enable, double out[4]);
+
 /* ---- test hook --------------------------------------------------------------------------------------
  * Per-pair evaluation with the production device functions (association, the three raw residuals,
  * weights, pose Jacobians, image gradients) for `count` surfel indices against one frame; 40 floats
