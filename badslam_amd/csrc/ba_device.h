@@ -927,6 +927,35 @@ __device__ __forceinline__ Vec3 surfel_position(const SurfelsView& s, uint32_t i
 __device__ __forceinline__ Vec3 surfel_normal(const SurfelsView& s, uint32_t i) {
   return unpack_normal10(reinterpret_cast<const uint32_t*>(s.row(kSurfelNormal))[i]);
 }
+// What a lane of a pair sweep keeps of its surfel across the keyframes: surfel tile * 64 + lane.  A lane past the end computes on
+// surfel 0 and is marked out of range.  The descriptors and the tangent points' radius are read only where the sweep takes descriptor
+// residuals (radius 0 otherwise: the tangent points are then never looked at).
+struct TileSurfel {
+  uint32_t i;
+  bool in_range;
+  Vec3 gp, gn;
+  float d1, d2;
+  TangentPoints tp;
+};
+template <bool kUseDesc>
+__device__ __forceinline__ TileSurfel load_tile_surfel(const SurfelsView& s, uint32_t tile, int lane) {
+  TileSurfel t;
+  t.i = tile * 64u + lane;
+  t.in_range = t.i < s.size;
+  const uint32_t ii = t.in_range ? t.i : 0;
+  t.gp = surfel_position(s, ii);
+  t.gn = surfel_normal(s, ii);
+  float radius_sq = 0;
+  t.d1 = 0;
+  t.d2 = 0;
+  if (kUseDesc) {
+    radius_sq = s.row(kSurfelRadiusSquared)[ii];
+    t.d1 = s.row(kSurfelDescriptor1)[ii];
+    t.d2 = s.row(kSurfelDescriptor2)[ii];
+  }
+  t.tp = surfel_tangent_points(t.gp, t.gn, radius_sq);
+  return t;
+}
 
 }  // namespace bahip
 

@@ -1,11 +1,14 @@
-// cost_device.h -- the terms of the bundle-adjustment objective and the resolution of a keyframe's cost row, shared between the cost
-// sweep (kernels_cost.hip) and the fused sweep of the pose phase under step control (kernels_pose_trial.hip): one spelling, so that
-// both produce the same binary32 terms and the same resolved binary64 sums.
+// cost_device.h -- what the sweeps that evaluate the bundle-adjustment objective share: the terms, the traversal of one tile against
+// a keyframe range (cost_pairs: the cost sweep of kernels_cost.hip and the per-surfel sweep of kernels_surfel_cost.hip are this
+// traversal with two sinks), the row sink (CostRowSink: the cost sweep's, and what the fused sweep of the pose phase under step
+// control, kernels_pose_trial.hip, adds its terms through) and the resolution of a summed row.  One spelling, so that all of them
+// produce the same binary32 terms and the same resolved binary64 sums.
 #pragma once
 
 #include "ba_device.h"
 #include "ba_launch.h"
 #include "exact_sum.h"
+#include "wave_cull.h"
 
 BAHIP_FLAVOURED_BEGIN
 
@@ -32,6 +35,81 @@ __device__ __forceinline__ void cost_lds_add(long long* limbs, long long* flag, 
   } else if (s.limb == -2) {
     *flag = 1;   // (every writer stores the same value)
   }
+}
+
+// Where the terms of a (tile, keyframe) pair go in the sweeps that keep one row per keyframe: row `item` of the workgroup's table in
+// LDS ([items][kCostWords]: three exact cells, two counts, a flag), which all lanes and all wavefronts of the workgroup add to with
+// atomics.  The sink of cost_pairs in the cost sweep, and what the fused sweep of the controlled pose phase adds its terms through.
+template <bool kUseDepth>
+struct CostRowSink {
+  long long* table;
+  __device__ __forceinline__ long long* pair(int item) const { return table + (size_t)item * kCostWords; }
+  __device__ __forceinline__ void depth(long long* row, float raw) { cost_lds_add(row, row + kCostFlagWord, weighted_depth_cost(raw)); }
+  __device__ __forceinline__ void descriptors(long long* row, float raw1, float raw2) {
+    cost_lds_add(row + kExactLimbs, row + kCostFlagWord, weighted_descriptor_cost(raw1));
+    cost_lds_add(row + 2 * kExactLimbs, row + kCostFlagWord, weighted_descriptor_cost(raw2));
+  }
+  // every lane of the wavefront: the lanes with an association, and whether this one added descriptor terms
+  __device__ __forceinline__ void end(long long* row, unsigned long long associated, bool has_desc) {
+    const unsigned long long with_desc = __builtin_amdgcn_ballot_w64(has_desc);
+    if ((threadIdx.x & 63) == 0) {
+      if (kUseDepth) __hip_atomic_fetch_add(&row[kCostDepthCountWord], (long long)__popcll(associated), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (with_desc) __hip_atomic_fetch_add(&row[kCostPairCountWord], (long long)__popcll(with_desc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+};
+
+// The terms of one 64-surfel tile against the keyframes [kf_begin, kf_begin + kf_count) this rank holds: the pose sweep's traversal
+// without Jacobians -- the frustum cull of wave_cull.h, every gather of a pair in flight before the first wait, the production
+// association rule of ba_device.h.  For every pair with an associated lane the sink says where the pair's terms go (pair(item)) and gets, on
+// the lanes concerned, depth(where, raw) and descriptors(where, raw1, raw2) (only where the colour pixel is valid), then
+// end(where, associated, has_desc) on every lane.
+template <bool kUseDepth, bool kUseDesc, typename Sink>
+__device__ __forceinline__ void cost_pairs(const Intrinsics& in, const KfEntry* __restrict__ frames, int kf_begin, int kf_count, uint32_t owner_mask,
+                                           uint32_t owner_rank, const TileSurfel& t, Sink& sink) {
+  const WaveBounds wb = wave_bounds(t.gp, t.in_range && (t.gp.x == t.gp.x));
+  for_each_candidate(
+      kf_count,
+      [&](int item) {
+        const int k = kf_begin + item;
+        if (((uint32_t)k & owner_mask) != owner_rank) return false;   // keyframe sharding: another rank holds its images
+        float f[12];
+        load_candidate(frames[k].pose.F, nullptr, f, nullptr);
+        return sphere_may_project(in, f, wb);
+      },
+      [&](int item) {
+        // (asked first: behind the ballot even an EMPTY pair() cost the descriptor-only per-surfel sweep of the fast flavour a spilled
+        // register at its 72; here the cost sweep's code is what it was and nothing spills)
+        const auto where = sink.pair(item);
+        const KfEntry& kf = frames[kf_begin + item];
+        const float* F = kf.pose.F;
+        // every gather of the pair goes out before the first one is waited for (ba_device.h: project_surfel)
+        const Projected p = project_surfel(in, F, t.gp);
+        const PixelWords pix = load_pixel_words(in, kf.geom, p);
+        DescWords dw;
+        if (kUseDesc) dw = load_descriptor_words(in, kf.lumafp, F, t.tp, p);
+        Assoc r;
+        const bool visible = t.in_range && associate_from_words<false>(in, F, t.gn, p, pix, &r, nullptr);
+        if (kUseDesc) gathers_arrived(pix, dw);
+        else gathers_arrived(pix);
+        const unsigned long long associated = __builtin_amdgcn_ballot_w64(visible);
+        if (associated == 0ull) return;
+        bool has_desc = false;
+        if (visible) {
+          if (kUseDepth) {
+            const float inv_std = assoc_inv_std(in, r);
+            const Vec3 u = assoc_unproject(r);
+            sink.depth(where, inv_std * dot3(r.nl, u - r.local));
+          }
+          if (kUseDesc && dw.color_ok) {
+            DescEval e;
+            eval_descriptor_from_words(in, kf.lumafp, dw, t.d1, t.d2, &e);
+            sink.descriptors(where, e.r1, e.r2);
+            has_desc = true;
+          }
+        }
+        sink.end(where, associated, has_desc);
+      });
 }
 
 BAHIP_FLAVOURED_END

@@ -4,6 +4,8 @@
 // The reference evaluates it on the host only (and, behind a debug switch, as a side sum of its pose kernel: B/kernel_opt_pose.cu:
 // 373-380); the oracle's orc_evaluate_cost is the same sum over all pairs.  Here it is the pose sweep's traversal without Jacobians:
 // 64-surfel tiles, the frustum cull of wave_cull.h, association and residuals from ba_device.h, the heavy-first run order of the sweeps.
+// The traversal of a tile (cost_pairs) and the sink that adds into a keyframe's row (CostRowSink) are in cost_device.h; this unit
+// holds the kernel that deals the tiles and keeps the table, its launcher, and the resolution kernels.
 //
 // DEFINITION.  Per keyframe three sums -- depth terms 1 * Tukey cost (k = 10), and the two descriptor terms 1e-2 *
 // Huber cost (k = 10) of the pairs whose colour pixel is valid -- each the EXACT sum of its binary32 terms rounded once to binary64
@@ -25,73 +27,6 @@ static_assert(kCostCellWords == kExactLimbs, "a cost row holds three ExactCells"
 
 BAHIP_FLAVOURED_BEGIN
 
-// One 64-surfel tile against the keyframes [kf_begin, kf_begin + kf_count) this rank holds.
-template <bool kUseDepth, bool kUseDesc>
-__device__ __forceinline__ void cost_tile(const Intrinsics& in, const KfEntry* __restrict__ frames, int kf_begin, int kf_count,
-                                          uint32_t owner_mask, uint32_t owner_rank, const SurfelsView& s, uint32_t tile, long long* table) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t i = tile * 64u + lane;
-  const bool in_range = i < s.size;
-  const uint32_t ii = in_range ? i : 0;
-  const Vec3 gp = surfel_position(s, ii);
-  const Vec3 gn = surfel_normal(s, ii);
-  float radius_sq = 0, d1 = 0, d2 = 0;
-  if (kUseDesc) {
-    radius_sq = s.row(kSurfelRadiusSquared)[ii];
-    d1 = s.row(kSurfelDescriptor1)[ii];
-    d2 = s.row(kSurfelDescriptor2)[ii];
-  }
-  const TangentPoints tp = surfel_tangent_points(gp, gn, radius_sq);
-  const WaveBounds wb = wave_bounds(gp, in_range && (gp.x == gp.x));
-  for_each_candidate(
-      kf_count,
-      [&](int item) {
-        const int k = kf_begin + item;
-        if (((uint32_t)k & owner_mask) != owner_rank) return false;   // keyframe sharding: another rank holds its images
-        float f[12];
-        load_candidate(frames[k].pose.F, nullptr, f, nullptr);
-        return sphere_may_project(in, f, wb);
-      },
-      [&](int item) {
-        const KfEntry& kf = frames[kf_begin + item];
-        const float* F = kf.pose.F;
-        // every gather of the pair goes out before the first one is waited for (ba_device.h: project_surfel)
-        const Projected p = project_surfel(in, F, gp);
-        const PixelWords pix = load_pixel_words(in, kf.geom, p);
-        DescWords dw;
-        if (kUseDesc) dw = load_descriptor_words(in, kf.lumafp, F, tp, p);
-        Assoc r;
-        const bool visible = in_range && associate_from_words<false>(in, F, gn, p, pix, &r, nullptr);
-        if (kUseDesc) gathers_arrived(pix, dw);
-        else gathers_arrived(pix);
-        const unsigned long long associated = __builtin_amdgcn_ballot_w64(visible);
-        if (associated == 0ull) return;
-        long long* row = table + (size_t)item * kCostWords;
-        long long* flag = row + kCostFlagWord;
-        bool has_desc = false;
-        if (visible) {
-          if (kUseDepth) {
-            const float inv_std = assoc_inv_std(in, r);
-            const Vec3 u = assoc_unproject(r);
-            const float raw = inv_std * dot3(r.nl, u - r.local);
-            cost_lds_add(row, flag, weighted_depth_cost(raw));
-          }
-          if (kUseDesc && dw.color_ok) {
-            DescEval e;
-            eval_descriptor_from_words(in, kf.lumafp, dw, d1, d2, &e);
-            cost_lds_add(row + kExactLimbs, flag, weighted_descriptor_cost(e.r1));
-            cost_lds_add(row + 2 * kExactLimbs, flag, weighted_descriptor_cost(e.r2));
-            has_desc = true;
-          }
-        }
-        const unsigned long long with_desc = __builtin_amdgcn_ballot_w64(has_desc);
-        if (lane == 0) {
-          if (kUseDepth) __hip_atomic_fetch_add(&row[kCostDepthCountWord], (long long)__popcll(associated), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          if (with_desc) __hip_atomic_fetch_add(&row[kCostPairCountWord], (long long)__popcll(with_desc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      });
-}
-
 // Persistent workgroups of `blockDim.x / 64` wavefronts; wavefront w of workgroup b takes the run-order positions b * waves + w,
 // + gridDim.x * waves, ... (heavy tiles first when `sched` is given: wave_cull.h, scheduled_tile).
 template <bool kUseDepth, bool kUseDesc>
@@ -107,7 +42,9 @@ cost_kernel(Intrinsics in, const KfEntry* __restrict__ frames, int kf_begin, int
   for (uint32_t pos = blockIdx.x * waves + (threadIdx.x >> 6); pos < positions; pos += gridDim.x * waves) {
     uint32_t tile;
     if (!scheduled_tile(pos, padded_tiles, sched, &tile) || tile >= tiles) continue;
-    cost_tile<kUseDepth, kUseDesc>(in, frames, kf_begin, kf_count, owner_mask, owner_rank, s, tile, cost_table);
+    // the tile's terms into the rows of the table (cost_device.h: cost_pairs, CostRowSink)
+    CostRowSink<kUseDepth> sink{cost_table};
+    cost_pairs<kUseDepth, kUseDesc>(in, frames, kf_begin, kf_count, owner_mask, owner_rank, load_tile_surfel<kUseDesc>(s, tile, threadIdx.x & 63), sink);
   }
   __syncthreads();
   long long* dst = out + (size_t)kf_begin * kCostWords;

@@ -33,14 +33,8 @@ namespace bahip {
 // ---- the accumulate sweep: compiled once per arithmetic flavour (ba_launch.h) -----------------------------------------------------
 BAHIP_FLAVOURED_BEGIN
 
-// tile_bounds: one bounding sphere per 64-surfel tile.  The first Gauss-Newton round of a pose phase (stored_bounds == 0)
-// computes them from the positions and stores them; the later rounds -- which iterate only the few keyframes that have not
-// converged, yet launch one wavefront (or several) per tile all the same -- read the sphere back (one scalar load), test it
-// against the remaining work items and return at once if none can see the tile, before any surfel is loaded.  Positions do
-// not change between the rounds of a phase, so the stored sphere is the one that would be recomputed.
+// The tile body of both sweeps is pose_tile (pose_device.h); the experiment builds' counters it keeps are declared there.
 #ifdef BAHIP_COUNT_CANDIDATES
-// experiment build only: (surfel tile, keyframe) candidates the cull lets through / with at least one associated lane / lanes
-__device__ unsigned long long g_candidate_counters[4];
 void pose_counters_dump() {
   unsigned long long c[4];
   if (hipMemcpyFromSymbol(c, HIP_SYMBOL(g_candidate_counters), sizeof(c)) == hipSuccess)
@@ -50,7 +44,6 @@ void pose_counters_dump() {
 #ifdef BAHIP_TILE_TIMELINE
 // experiment build only: start / end of every tile of the last FULL round of the persistent pose sweep, by draw position
 __device__ unsigned long long g_pose_timeline[65536][4];   // start, end, tile, (candidates visited << 32) | candidates with an association
-__device__ unsigned int g_pose_tile_stats[65536][2];
 void pose_timeline_dump(const char* path) {
   static unsigned long long host[65536][4];
   if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_pose_timeline), sizeof(host)) != hipSuccess) return;
@@ -103,180 +96,6 @@ struct GlobalSink {
   __device__ __forceinline__ void finish() { flush(); }
 };
 
-// One 64-surfel tile against the work items still iterating (every `parts`-th of them, starting at `part`).
-template <bool kUseDepth, bool kUseDesc, typename Sink>
-__device__ __forceinline__ void pose_tile(const Intrinsics& in, const KfEntry* __restrict__ frames, const PoseWork* __restrict__ work,
-                                          int num_work, const SurfelsView& s, WaveBounds* __restrict__ tile_bounds, int stored_bounds,
-                                          int num_listed, uint32_t tile, int parts, int part, Sink& sink, uint32_t* __restrict__ tile_cost,
-                                          int item_begin = 0, int item_count = -1) {
-  const int lane = threadIdx.x & 63;
-  // Later rounds (stored_bounds): the items are the num_listed entries of the list behind the counter records -- the work
-  // items still iterating -- instead of all num_work work items.  A launch may cover a slice of the items only
-  // ([item_begin, item_begin + item_count): the LDS form cuts lists longer than its table); `item` below counts from the
-  // slice's start.
-  const int* __restrict__ listed = reinterpret_cast<const int*>(work + num_work + kPoseTailRecords) + item_begin;
-  const int num_items = item_count >= 0 ? item_count : (stored_bounds ? num_listed : num_work);
-  auto work_item_of = [&](int item) { return stored_bounds ? load_global(listed + item) : item_begin + item; };
-  WaveBounds wb;
-  if (stored_bounds) {
-    wb = tile_bounds[tile];     // wave-uniform address: scalar loads
-    if (wb.r < 0.f) return;
-    bool any = false;
-    for (int base = part; base < num_items && !any; base += 64 * parts) {
-      const int item = base + lane * parts;
-      bool sees = false;
-      if (item < num_items) {
-        float f[12];
-        load_candidate(work[work_item_of(item)].F, nullptr, f, nullptr);
-        sees = sphere_may_project(in, f, wb);
-      }
-      any = __any(sees) != 0;
-    }
-    if (!any) return;
-  }
-  const uint32_t i = tile * kPoseBlock + lane;
-  const bool in_range = i < s.size;
-  const uint32_t ii = in_range ? i : 0;
-  const Vec3 gp = surfel_position(s, ii);
-  const Vec3 gn = surfel_normal(s, ii);
-  float radius_sq = 0, d1 = 0, d2 = 0;
-  if (kUseDesc) {
-    radius_sq = s.row(kSurfelRadiusSquared)[ii];
-    d1 = s.row(kSurfelDescriptor1)[ii];
-    d2 = s.row(kSurfelDescriptor2)[ii];
-  }
-  const TangentPoints tp = surfel_tangent_points(gp, gn, radius_sq);
-
-  // Only the work items whose frustum can contain this wavefront's surfels are visited (wave_cull.h).
-  if (!stored_bounds) {
-    wb = wave_bounds(gp, in_range && (gp.x == gp.x));
-    if (part == 0 && lane == 0) tile_bounds[tile] = wb;
-  }
-  int my_w = 0;   // the work item of this lane's candidate item in the current chunk of 64 (read back by lane in the body)
-#ifdef BAHIP_TILE_TIMELINE
-  uint32_t with_association = 0;
-#endif
-  uint32_t visited = 0;   // wave-uniform: candidates this wavefront visits = what the tile costs (feeds tile_order_kernel)
-  for_each_candidate(
-      num_items,
-      [&](int item) {
-        const int w = work_item_of(item);
-        my_w = w;
-        float f[12];
-        int32_t done;
-        load_candidate(work[w].F, &work[w].skip, f, &done);   // skip = done, or the keyframe's images live on another rank
-        return !done && sphere_may_project(in, f, wb);
-      },
-      [&](int item) {
-    // item = base + lane' * parts for the lane' that tested it: its w comes from that lane's register, not from memory
-    // (a list lookup here was a dependent load and a wait at the top of every candidate of the later rounds)
-    const int w = __builtin_amdgcn_readfirstlane(stored_bounds ? __builtin_amdgcn_readlane(my_w, ((item - part) / parts) & 63) : item_begin + item);
-    const float* F = work[w].F;
-    ++visited;
-    // (the entry of the frame table that provides the images: today every writer binds work item w to entry w, but the field is what
-    // pose_solve honours too, and reading frames[w] directly measured no gain over this dependent scalar load: ADVICE r5)
-    const KfEntry& kf = frames[__builtin_amdgcn_readfirstlane(load_global(&work[w].kf_index))];
-    // every gather of the pair goes out before the first one is waited for (ba_device.h: project_surfel)
-    const Projected p = project_surfel(in, F, gp);
-    const PixelWords pix = load_pixel_words(in, kf.geom, p);
-    DescWords dw;
-    if (kUseDesc) dw = load_descriptor_words(in, kf.lumafp, F, tp, p);   // (issued after the association instead: pose sweep +7 %)
-    Assoc r;
-    const bool visible = in_range && associate_from_words<false>(in, F, gn, p, pix, &r, nullptr);
-    // every gather has arrived from here on, on every path (a load still pending at the loop's back edge would make the
-    // compiler wait for it - and, vmcnt being in-order, for the atomics behind it - at the top of the next candidate)
-    if (kUseDesc) gathers_arrived(pix, dw);
-    else gathers_arrived(pix);
-    sink.gathers_done();
-#ifdef BAHIP_COUNT_CANDIDATES
-    {
-      const unsigned long long associated_lanes = __ballot(visible);
-      if (!stored_bounds && lane == 0) {
-        atomicAdd(&g_candidate_counters[0], 1ull);
-        atomicAdd(&g_candidate_counters[1], associated_lanes ? 1ull : 0ull);
-        atomicAdd(&g_candidate_counters[2], (unsigned long long)__popcll(associated_lanes));
-      }
-    }
-#endif
-    if (__builtin_amdgcn_ballot_w64(visible) == 0ull) return;   // (a scalar compare on the mask; __any costs a select and a compare per lane)
-#ifdef BAHIP_TILE_TIMELINE
-    ++with_association;
-#endif
-
-    float acc[28];   // 21 H + 6 b + 1 pad (kHbCoefficients)
-    // The depth residual opens the 27 sums as plain products, in every lane: a lane without an association computes on whatever its
-    // Assoc holds (no memory is touched), and eight selects then give it J = 0, weight 0, residual 0, so that its products are
-    // zeros -- instead of 27 cleared accumulators + 27 fused multiply-adds onto them under the lanes' mask.  Same bits where it
-    // matters: fma(a, b, +0) and a * b differ in the sign of a zero product only, a zero addend never changes a non-zero sum, and a
-    // total that is a zero of either sign is the fixed-point 0 (hb_split).  (Not applicable to the lanes' garbage directly: their
-    // Jacobians may be infinite or NaN, and 0 * inf is not 0.)
-    if (kUseDepth) {
-      float J[6];
-      const float inv_std = assoc_inv_std(in, r);
-      const Vec3 u = assoc_unproject(r);
-      float raw = inv_std * dot3(r.nl, u - r.local);
-      jac_depth_pose(r.nl, u, inv_std, J);
-      float wgt = depth_residual_weight(raw);
-#pragma unroll
-      for (int c = 0; c < 6; ++c) J[c] = visible ? J[c] : 0.f;
-      wgt = visible ? wgt : 0.f;
-      raw = visible ? raw : 0.f;
-      int q = 0;
-#pragma unroll
-      for (int row = 0; row < 6; ++row) {
-        const float wj = wgt * J[row];
-#pragma unroll
-        for (int col = row; col < 6; ++col, ++q) acc[q] = wj * J[col];
-      }
-      const float wr = wgt * raw;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) acc[21 + c] = wr * J[c];
-      acc[27] = 0.f;
-    } else {
-#pragma unroll
-      for (int q = 0; q < 28; ++q) acc[q] = 0.f;
-    }
-
-    if (visible) {
-      float J[6];
-      if (kUseDesc) {
-        // B/kernel_opt_pose.cu:303-353: nothing is added when the colour-pixel transform fails.
-        if (dw.color_ok) {
-          DescEval e;
-          eval_descriptor_from_words(in, kf.lumafp, dw, d1, d2, &e);
-          // B/kernel_opt_pose.cu:96-142
-          const Vec3 ls = r.local;
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const float gx = (t ? e.gx2 : e.gx1) * in.cfx;
-            const float gy = (t ? e.gy2 : e.gy1) * in.cfy;
-            const float raw = t ? e.r2 : e.r1;
-            jac_descriptor_pose(ls, r.inv_z, gx, gy, J);
-            const float wgt = descriptor_residual_weight(raw);
-            accumulate_jtj(acc, J, wgt, raw);
-          }
-        }
-      }
-    }
-
-    // wave64 halving reduction (wave_reduce.h: a fixed tree over the 64 lanes), then two 64-bit integer adds per scalar
-    // per wave on the fixed-point limbs: order-free, hence deterministic
-    float total = wave_reduce28(acc, lane);
-    // The cross-lane steps of the reduction must run with every lane enabled: a DPP / permlane source lane that EXEC has
-    // switched off reads as zero.  The totals are consumed under `this lane holds one` (27 lanes), and the compiler sank the
-    // last DPP add into that branch -- rows of the LDS table then received totals that lacked their odd neighbour's half.
-    // The empty asm pins the finished value in uniform control flow.
-    asm volatile("" : "+v"(total));
-    sink.add(item, w, total);
-  }, parts, part);
-  sink.finish();
-  // first round of a phase over the keyframe table: the tile's cost for the run order of the next launches (wave_cull.h)
-  if (tile_cost && !stored_bounds && lane == 0 && visited) atomicAdd(&tile_cost[tile], visited);
-#ifdef BAHIP_TILE_TIMELINE
-  if (!stored_bounds && lane == 0 && tile < 65536) { g_pose_tile_stats[tile][0] = visited; g_pose_tile_stats[tile][1] = with_association; }
-#endif
-}
-
 // One wavefront per workgroup and tile; gridDim.y wavefronts share a tile's work items (shards of a multi-GPU run, and work
 // item tables too large for the LDS form below).
 template <bool kUseDepth, bool kUseDesc>
@@ -299,8 +118,8 @@ pose_accumulate_kernel(Intrinsics in, const KfEntry* __restrict__ frames, const 
   GlobalSink sink{Hb, invalid, 0.f, -1, (slot >= 0 && slot < 27) ? slot * kHbLimbs * (int)sizeof(HbFixed) : -1};
   uint32_t tile;   // heavy work first (wave_cull.h: scheduled_tile)
   if (!scheduled_tile(blockIdx.x, gridDim.x - (sched ? kHeavySlots : 0u), sched, &tile)) return;
-  pose_tile<kUseDepth, kUseDesc>(in, frames, work, num_work, s, tile_bounds, stored_bounds, num_listed, tile, (int)gridDim.y, (int)blockIdx.y, sink,
-                                 tile_cost);
+  pose_tile<kUseDepth, kUseDesc>(in, frames, work, pose_work_list(work, num_work), num_work, s, tile_bounds, stored_bounds, num_listed, tile,
+                                 (int)gridDim.y, (int)blockIdx.y, sink, tile_cost);
 }
 
 // Persistent form: one workgroup of 16 wavefronts per compute unit keeps the normal equations of every work item in LDS
@@ -405,8 +224,8 @@ pose_accumulate_lds_kernel(Intrinsics in, const KfEntry* __restrict__ frames, co
 #ifdef BAHIP_TILE_TIMELINE
       const unsigned long long t0 = wall_clock64();
 #endif
-      pose_tile<kUseDepth, kUseDesc>(in, frames, work, num_work, s, tile_bounds, stored_bounds, num_listed, tile, parts, part, sink, tile_cost,
-                                     item_begin, kSlice ? num_items : -1);
+      pose_tile<kUseDepth, kUseDesc>(in, frames, work, pose_work_list(work, num_work), num_work, s, tile_bounds, stored_bounds, num_listed, tile,
+                                     parts, part, sink, tile_cost, item_begin, kSlice ? num_items : -1);
 #ifdef BAHIP_TILE_TIMELINE
       if (!stored_bounds && lane == 0 && position < 65536 && tile < 65536) {
         g_pose_timeline[position][0] = t0; g_pose_timeline[position][1] = wall_clock64(); g_pose_timeline[position][2] = tile;
@@ -416,7 +235,7 @@ pose_accumulate_lds_kernel(Intrinsics in, const KfEntry* __restrict__ frames, co
     }
   }
   __syncthreads();
-  const int* __restrict__ listed = reinterpret_cast<const int*>(work + num_work + kPoseTailRecords);
+  const int* __restrict__ listed = pose_work_list(work, num_work);
   for (int e = threadIdx.x; e < num_items * kHbStride; e += blockDim.x) {
     const HbFixed v = table[e];
     if (v != 0) {

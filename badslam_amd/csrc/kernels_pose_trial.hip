@@ -5,8 +5,9 @@
 // pose in round 0, the candidate afterwards), the normal equations AND the cost row: the pose sweep and the cost sweep walk the same
 // tiles, cull against the same frusta and make the same gathers and the same association test, so one traversal yields both --
 // H, b as the two-limb fixed point of the plain phase (pose_device.h: LdsSink), the cost as the row kernels_cost.hip keeps (three
-// exact cells, two counts, a flag; cost_device.h).  Persistent workgroups hold both tables of their items in LDS and add the
-// non-zero words to global memory once.  The CONTROLLED SOLVE, one lane per item, resolves the row (exact_sum.h: exact_value),
+// exact cells, two counts, a flag; cost_device.h).  The tile body is the plain sweeps' (pose_device.h: pose_tile); what this unit
+// adds to it is the per-pair policy below, which puts the cost terms through the cost sweep's row sink (cost_device.h: CostRowSink).
+// Persistent workgroups hold both tables of their items in LDS and add the non-zero words to global memory once.  The CONTROLLED SOLVE, one lane per item, resolves the row (exact_sum.h: exact_value),
 // decides, keeps the accepted (H, b), pose and cost in the item's record, and derives the next candidate from the stored equations.
 #include "ba_device.h"
 #include "ba_launch.h"
@@ -29,162 +30,28 @@ constexpr size_t kPoseTrialItemBytes = sizeof(HbFixed) * kHbStride + sizeof(long
 // ---- the fused sweep: compiled once per arithmetic flavour (ba_launch.h) -----------------------------------------------------------
 BAHIP_FLAVOURED_BEGIN
 
-// One 64-surfel tile against the items [item_begin, item_begin + num_items) -- of the list `listed` (the items still iterating), or
-// of all work items when it is NULL (round 0) -- every `parts`-th of them, starting at `part`.  The traversal is pose_tile's
-// (kernels_pose.hip): stored tile bounds in the later rounds, the frustum cull, every gather of a pair in flight before the first
-// wait; the accumulation of H, b is its chain word for word, the cost terms are cost_tile's (kernels_cost.hip).
-template <bool kUseDepth, bool kUseDesc>
-__device__ __forceinline__ void pose_trial_tile(const Intrinsics& in, const KfEntry* __restrict__ frames, const PoseWork* __restrict__ work,
-                                                const int* __restrict__ listed, int item_begin, int num_items, const SurfelsView& s,
-                                                WaveBounds* __restrict__ tile_bounds, int stored_bounds, uint32_t tile, int parts, int part,
-                                                LdsSink& sink, long long* cost_table) {
-  const int lane = threadIdx.x & 63;
-  auto work_item_of = [&](int item) { return listed ? load_global(listed + item_begin + item) : item_begin + item; };
+// What the fused sweep does per pair besides H, b (pose_device.h: pose_tile's per-pair policy): the pair's three cost terms and two
+// counts into the item's row of the workgroup's cost table, through the row sink of the cost sweep (cost_device.h).
+template <bool kUseDepth>
+struct TrialPairTerms {
+  CostRowSink<kUseDepth> cost;
+  long long* row;
+  bool has_desc;
   // The frustum test derives four norms from the intrinsics (wave_cull.h: sphere_may_project).  Hoisted out of the loops they live in
   // vector registers across the candidate body -- the plain sweep has exactly its 128, this one carries the cost row besides and
   // spilled them.  Taken through an opaque scalar copy per test they are recomputed per chunk of 64 items (four square roots) instead.
   // The copy is an empty inline-asm statement: an optimisation barrier that emits no instruction (DESIGN.md section 3 names it as the
-  // unit's exception to "plain C++ only", with the barrier of the reduction below).
-  auto cull_intrinsics = [&]() {
+  // unit's exception to "plain C++ only", with the barrier of pose_tile's reduction).
+  __device__ __forceinline__ Intrinsics cull_intrinsics(const Intrinsics& in) const {
     Intrinsics c = in;
     asm volatile("" : "+s"(c.fx), "+s"(c.fy), "+s"(c.cx), "+s"(c.cy));
     return c;
-  };
-  WaveBounds wb;
-  if (stored_bounds) {
-    wb = tile_bounds[tile];     // wave-uniform address: scalar loads
-    if (wb.r < 0.f) return;
-    bool any = false;
-    for (int base = part; base < num_items && !any; base += 64 * parts) {
-      const int item = base + lane * parts;
-      bool sees = false;
-      if (item < num_items) {
-        float f[12];
-        load_candidate(work[work_item_of(item)].F, nullptr, f, nullptr);
-        sees = sphere_may_project(cull_intrinsics(), f, wb);
-      }
-      any = __any(sees) != 0;
-    }
-    if (!any) return;
   }
-  const uint32_t i = tile * kPoseBlock + lane;
-  const bool in_range = i < s.size;
-  const uint32_t ii = in_range ? i : 0;
-  const Vec3 gp = surfel_position(s, ii);
-  const Vec3 gn = surfel_normal(s, ii);
-  float radius_sq = 0, d1 = 0, d2 = 0;
-  if (kUseDesc) {
-    radius_sq = s.row(kSurfelRadiusSquared)[ii];
-    d1 = s.row(kSurfelDescriptor1)[ii];
-    d2 = s.row(kSurfelDescriptor2)[ii];
-  }
-  const TangentPoints tp = surfel_tangent_points(gp, gn, radius_sq);
-  if (!stored_bounds) {
-    wb = wave_bounds(gp, in_range && (gp.x == gp.x));
-    if (part == 0 && lane == 0) tile_bounds[tile] = wb;
-  }
-  int my_w = 0;   // the work item of this lane's candidate item in the current chunk of 64 (read back by lane in the body)
-  for_each_candidate(
-      num_items,
-      [&](int item) {
-        const int w = work_item_of(item);
-        my_w = w;
-        float f[12];
-        int32_t done;
-        load_candidate(work[w].F, &work[w].skip, f, &done);
-        return !done && sphere_may_project(cull_intrinsics(), f, wb);
-      },
-      [&](int item) {
-    const int w = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane(my_w, ((item - part) / parts) & 63));
-    const float* F = work[w].F;
-    const KfEntry& kf = frames[__builtin_amdgcn_readfirstlane(load_global(&work[w].kf_index))];
-    // every gather of the pair goes out before the first one is waited for (ba_device.h: project_surfel)
-    const Projected p = project_surfel(in, F, gp);
-    const PixelWords pix = load_pixel_words(in, kf.geom, p);
-    DescWords dw;
-    if (kUseDesc) dw = load_descriptor_words(in, kf.lumafp, F, tp, p);
-    Assoc r;
-    const bool visible = in_range && associate_from_words<false>(in, F, gn, p, pix, &r, nullptr);
-    if (kUseDesc) gathers_arrived(pix, dw);
-    else gathers_arrived(pix);
-    sink.gathers_done();
-    const unsigned long long associated = __builtin_amdgcn_ballot_w64(visible);
-    if (associated == 0ull) return;
-    long long* row = cost_table + (size_t)item * kCostWords;
-    long long* flag = row + kCostFlagWord;
-
-    float acc[28];   // 21 H + 6 b + 1 pad (kHbCoefficients)
-    // (the depth residual opens the 27 sums as plain products in every lane, the lanes without an association through selected
-    // zeros: kernels_pose.hip, pose_tile, says why these are the bits of the fused multiply-adds onto cleared accumulators)
-    if (kUseDepth) {
-      float J[6];
-      const float inv_std = assoc_inv_std(in, r);
-      const Vec3 u = assoc_unproject(r);
-      float raw = inv_std * dot3(r.nl, u - r.local);
-      jac_depth_pose(r.nl, u, inv_std, J);
-      float wgt = depth_residual_weight(raw);
-#pragma unroll
-      for (int c = 0; c < 6; ++c) J[c] = visible ? J[c] : 0.f;
-      wgt = visible ? wgt : 0.f;
-      raw = visible ? raw : 0.f;
-      int q = 0;
-#pragma unroll
-      for (int row6 = 0; row6 < 6; ++row6) {
-        const float wj = wgt * J[row6];
-#pragma unroll
-        for (int col = row6; col < 6; ++col, ++q) acc[q] = wj * J[col];
-      }
-      const float wr = wgt * raw;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) acc[21 + c] = wr * J[c];
-      acc[27] = 0.f;
-      // (behind the products, where `raw` dies: on a visible lane the selected value is the residual itself)
-      if (visible) cost_lds_add(row, flag, weighted_depth_cost(raw));
-    } else {
-#pragma unroll
-      for (int q = 0; q < 28; ++q) acc[q] = 0.f;
-    }
-
-    bool has_desc = false;
-    if (visible) {
-      float J[6];
-      if (kUseDesc) {
-        // B/kernel_opt_pose.cu:303-353: nothing is added when the colour-pixel transform fails.
-        if (dw.color_ok) {
-          DescEval e;
-          eval_descriptor_from_words(in, kf.lumafp, dw, d1, d2, &e);
-          has_desc = true;
-          // B/kernel_opt_pose.cu:96-142
-          const Vec3 ls = r.local;
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const float gx = (t ? e.gx2 : e.gx1) * in.cfx;
-            const float gy = (t ? e.gy2 : e.gy1) * in.cfy;
-            const float raw = t ? e.r2 : e.r1;
-            jac_descriptor_pose(ls, r.inv_z, gx, gy, J);
-            const float wgt = descriptor_residual_weight(raw);
-            accumulate_jtj(acc, J, wgt, raw);
-          }
-          // (behind the Jacobians, whose registers are free again)
-          cost_lds_add(row + kExactLimbs, flag, weighted_descriptor_cost(e.r1));
-          cost_lds_add(row + 2 * kExactLimbs, flag, weighted_descriptor_cost(e.r2));
-        }
-      }
-    }
-    const unsigned long long with_desc = __builtin_amdgcn_ballot_w64(has_desc);
-    if (lane == 0) {
-      if (kUseDepth) __hip_atomic_fetch_add(&row[kCostDepthCountWord], (long long)__popcll(associated), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (with_desc) __hip_atomic_fetch_add(&row[kCostPairCountWord], (long long)__popcll(with_desc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-
-    // wave64 halving reduction (wave_reduce.h), then two 64-bit integer adds per scalar on the fixed-point limbs in LDS; the empty asm
-    // keeps the last cross-lane step in uniform control flow (kernels_pose.hip, pose_tile)
-    float total = wave_reduce28(acc, lane);
-    asm volatile("" : "+v"(total));
-    sink.add(item, w, total);
-  }, parts, part);
-  sink.finish();
-}
+  __device__ __forceinline__ void begin(int item) { row = cost.pair(item); has_desc = false; }
+  __device__ __forceinline__ void depth(bool visible, float raw) { if (visible) cost.depth(row, raw); }   // (on a visible lane the selected value is the residual itself)
+  __device__ __forceinline__ void descriptors(const DescEval& e) { cost.descriptors(row, e.r1, e.r2); has_desc = true; }
+  __device__ __forceinline__ void end(unsigned long long associated) { cost.end(row, associated, has_desc); }
+};
 
 // Persistent workgroups of blockDim.x / 64 wavefronts; the units (run-order position x part; heavy tiles first when `sched` is
 // given: wave_cull.h) are dealt to the wavefronts statically, as the cost sweep and the short later rounds of the plain sweep deal
@@ -209,8 +76,10 @@ pose_trial_sweep_kernel(Intrinsics in, const KfEntry* __restrict__ frames, const
   for (uint32_t unit = blockIdx.x * waves + (threadIdx.x >> 6); unit < units; unit += gridDim.x * waves) {
     uint32_t tile;
     if (!scheduled_tile(unit >> parts_shift, padded_tiles, sched, &tile) || tile >= tiles) continue;
-    pose_trial_tile<kUseDepth, kUseDesc>(in, frames, work, listed, item_begin, num_items, s, tile_bounds, stored_bounds, tile, 1 << parts_shift,
-                                         (int)(unit & ((1u << parts_shift) - 1u)), sink, cost_table);
+    // (the plain sweeps' tile: `listed` is non-NULL exactly when the bounds are stored -- round 0 has neither --, no tile census)
+    pose_tile<kUseDepth, kUseDesc>(in, frames, work, listed, num_work, s, tile_bounds, stored_bounds, num_items, tile, 1 << parts_shift,
+                                   (int)(unit & ((1u << parts_shift) - 1u)), sink, nullptr, item_begin, num_items,
+                                   TrialPairTerms<kUseDepth>{{cost_table}, nullptr, false});
   }
   __syncthreads();
   for (int e = threadIdx.x; e < words; e += blockDim.x) {

@@ -2,10 +2,9 @@
 // robust descriptor costs over every bound keyframe it is associated with, and the two counts ("The objective per
 // surfel").  With the poses frozen -- the geometry phase of the alternating scheme -- a surfel's cost depends on that surfel only.
 //
-// The traversal is the cost sweep's (kernels_cost.hip: cost_tile): 64-surfel tiles, one wavefront per tile, persistent workgroups, the
-// heavy-first run order, the frustum cull of wave_cull.h, every gather of a pair in flight before the first wait, the production
-// association rule of ba_device.h, the terms of cost_device.h.  The sink is not: where the cost sweep adds every term with an LDS atomic
-// into one row per keyframe that all 64 lanes (and all wavefronts of the workgroup) contend for, here each lane owns the three exact
+// A tile's pairs are walked by cost_pairs (cost_device.h), as the cost sweep's are; this unit holds the sink, the
+// tile's epilogue, the kernel and its launcher.  Where the cost sweep adds every term with an LDS atomic into one row per keyframe
+// that all 64 lanes (and all wavefronts of the workgroup) contend for (CostRowSink), here each lane owns the three exact
 // accumulators of its own surfel -- 3 x kExactLimbs columns of the wavefront's [limb][64] block in LDS (exact_sum.h: exact_lds_add's
 // layout; the limb index is data dependent, so registers cannot hold them), plain read-modify-write, no atomic anywhere.  The counts
 // and the non-finite flag are registers.  Integer limbs: keyframe order, launch shape, tile order and sharding cannot move a bit.
@@ -50,6 +49,27 @@ __device__ __forceinline__ void surfel_cost_add(long long* cell, int lane, float
   }
 }
 
+// The sink of cost_pairs (cost_device.h) per lane: the terms into the lane's own columns of `acc` (3 x [kExactLimbs][64] words, a
+// wave-uniform address), the counts and the non-finite flag in registers.
+struct SurfelCostLaneSink {
+  long long* acc;
+  int lane;
+  uint32_t &depth_count, &pair_count;
+  bool& bad;
+  struct Here {};   // (the lane's own columns, whatever the keyframe)
+  __device__ __forceinline__ Here pair(int /*k*/) const { return {}; }
+  __device__ __forceinline__ void depth(Here, float raw) {
+    surfel_cost_add(acc, lane, weighted_depth_cost(raw), &bad);
+    ++depth_count;
+  }
+  __device__ __forceinline__ void descriptors(Here, float raw1, float raw2) {
+    surfel_cost_add(acc + kExactLimbs * 64, lane, weighted_descriptor_cost(raw1), &bad);
+    surfel_cost_add(acc + 2 * kExactLimbs * 64, lane, weighted_descriptor_cost(raw2), &bad);
+    ++pair_count;
+  }
+  __device__ __forceinline__ void end(Here, unsigned long long /*associated*/, bool /*has_desc*/) {}
+};
+
 // One 64-surfel tile against the keyframes this rank holds.  `acc`: the wavefront's 3 x [kExactLimbs][64] words, zero on entry and on
 // return.  rows != NULL: the row epilogue (keyframe sharding), into the staging planes of the slice that begins at surfel `slice_begin`
 // (a branch in the epilogue, not a second instantiation: two copies of the candidate loop in one kernel double what the compiler hoists
@@ -60,59 +80,13 @@ __device__ __forceinline__ void surfel_cost_tile(const Intrinsics& in, const KfE
                                                  const SurfelCostPlanes& out, long long* __restrict__ rows, uint32_t slice_begin,
                                                  uint32_t row_stride) {
   const int lane = threadIdx.x & 63;
-  const uint32_t i = tile * 64u + lane;
-  const bool in_range = i < s.size;
-  const uint32_t ii = in_range ? i : 0;
-  const Vec3 gp = surfel_position(s, ii);
-  const Vec3 gn = surfel_normal(s, ii);
-  float radius_sq = 0, d1 = 0, d2 = 0;
-  if (kUseDesc) {
-    radius_sq = s.row(kSurfelRadiusSquared)[ii];
-    d1 = s.row(kSurfelDescriptor1)[ii];
-    d2 = s.row(kSurfelDescriptor2)[ii];
-  }
-  const TangentPoints tp = surfel_tangent_points(gp, gn, radius_sq);
-  const WaveBounds wb = wave_bounds(gp, in_range && (gp.x == gp.x));
+  const TileSurfel t = load_tile_surfel<kUseDesc>(s, tile, lane);
+  const uint32_t i = t.i;
+  const bool in_range = t.in_range;
   uint32_t depth_count = 0, pair_count = 0;
   bool bad = false;
-  for_each_candidate(
-      num_kfs,
-      [&](int k) {
-        if (((uint32_t)k & owner_mask) != owner_rank) return false;   // keyframe sharding: another rank holds its images
-        float f[12];
-        load_candidate(frames[k].pose.F, nullptr, f, nullptr);
-        return sphere_may_project(in, f, wb);
-      },
-      [&](int k) {
-        const KfEntry& kf = frames[k];
-        const float* F = kf.pose.F;
-        // every gather of the pair goes out before the first one is waited for (ba_device.h: project_surfel)
-        const Projected p = project_surfel(in, F, gp);
-        const PixelWords pix = load_pixel_words(in, kf.geom, p);
-        DescWords dw;
-        if (kUseDesc) dw = load_descriptor_words(in, kf.lumafp, F, tp, p);
-        Assoc r;
-        const bool visible = in_range && associate_from_words<false>(in, F, gn, p, pix, &r, nullptr);
-        if (kUseDesc) gathers_arrived(pix, dw);
-        else gathers_arrived(pix);
-        if (__builtin_amdgcn_ballot_w64(visible) == 0ull) return;
-        if (visible) {
-          if (kUseDepth) {
-            const float inv_std = assoc_inv_std(in, r);
-            const Vec3 u = assoc_unproject(r);
-            const float raw = inv_std * dot3(r.nl, u - r.local);
-            surfel_cost_add(acc, lane, weighted_depth_cost(raw), &bad);
-            ++depth_count;
-          }
-          if (kUseDesc && dw.color_ok) {
-            DescEval e;
-            eval_descriptor_from_words(in, kf.lumafp, dw, d1, d2, &e);
-            surfel_cost_add(acc + kExactLimbs * 64, lane, weighted_descriptor_cost(e.r1), &bad);
-            surfel_cost_add(acc + 2 * kExactLimbs * 64, lane, weighted_descriptor_cost(e.r2), &bad);
-            ++pair_count;
-          }
-        }
-      });
+  SurfelCostLaneSink sink{acc, lane, depth_count, pair_count, bad};
+  cost_pairs<kUseDepth, kUseDesc>(in, frames, 0, num_kfs, owner_mask, owner_rank, t, sink);
   // One cell after the other (a loop that is not unrolled: nine limbs in registers at a time, one copy of exact_value, so that the
   // epilogue does not set the kernel's register count): the lane's limbs back into registers, zeros left behind for the next tile
   // (its own columns: no barrier), then resolved and stored, or staged.
