@@ -84,6 +84,22 @@ class SurfelCosts(C.Structure):    # bahip_surfel_costs: device planes of the ob
                 ("depth_residuals", C.c_void_p), ("descriptor_pairs", C.c_void_p)]
 
 
+RENDER_POINT, RENDER_DISC = 0, 1
+
+
+class RenderOptions(C.Structure):  # bahip_render_options: what bahip_render_surfels draws (defaults: discs of at most 4 px, culled, any depth)
+    _fields_ = [("mode", C.c_int32), ("max_radius_px", C.c_int32), ("cull_backfaces", C.c_int32),
+                ("radius_factor", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float), ("index_base", C.c_uint32)]
+
+    def __init__(self, mode=RENDER_DISC, max_radius_px=4, cull_backfaces=1, radius_factor=1.0, min_depth=0.0, max_depth=float("inf"),
+                 index_base=0):
+        super().__init__(int(mode), int(max_radius_px), int(cull_backfaces), radius_factor, min_depth, max_depth, int(index_base))
+
+
+class RenderOut(C.Structure):      # bahip_render_out: device planes of a rendered view (bahip_render_surfels)
+    _fields_ = [("key", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p), ("normal", C.c_void_p), ("color", C.c_void_p)]
+
+
 class PoseStepControl(C.Structure):   # bahip_pose_step_control: step control of the pose phase (bahip_estimate_keyframe_poses_controlled)
     _fields_ = [("lambda_up", C.c_float), ("lambda_down", C.c_float), ("lambda_min", C.c_float), ("lambda_max", C.c_float),
                 ("max_trials", C.c_int)]
@@ -246,6 +262,12 @@ SIGNATURES = {
     "bahip_debug_intrinsics_solve_damped": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                       C.POINTER(C.c_float)]),
     "bahip_debug_intrinsics_trial_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "bahip_render_surfels": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.POINTER(Camera), C.POINTER(C.c_float), C.POINTER(RenderOptions),
+                                       C.POINTER(RenderOut)]),
+    "bahip_debug_set_render_shape": (C.c_int, [C.c_int, C.c_int]),
+    "bahip_debug_set_render_stages": (C.c_int, [C.c_int]),
+    "bahip_debug_render_census": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.POINTER(Camera), C.POINTER(C.c_float), C.POINTER(RenderOptions),
+                                            C.POINTER(C.c_ulonglong)]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

@@ -559,4 +559,33 @@ void launch_intrinsics_trial_backsub(hipStream_t st, int cf_width, int S, const 
                                      uint32_t src_pitch, float* dst, uint32_t dst_pitch);
 void launch_intrinsics_trial_plane_copy(hipStream_t st, int width, int height, const float* src, uint32_t src_pitch, float* dst, uint32_t dst_pitch);
 
+// kernels_render.hip: the surfel map rendered into a camera view (exists once: exact arithmetic under either flavour).  The view camera
+// travels as an Intrinsics of which only the depth camera's members are filled (make_intrinsics of the view for both cameras).
+constexpr int kRenderMaxWaves = 8, kRenderMaxRadiusPx = 16;
+constexpr int kRenderDefaultWaves = 4, kRenderWorkgroupsPerUnit = 16;
+struct RenderParams {
+  float F[12];               // frame_T_global
+  int mode, max_radius_px, cull_backfaces;
+  float radius_factor, min_depth, max_depth;
+  float max_focal;           // max(fx, fy) of the view camera
+  uint32_t index_base;
+};
+struct RenderPlanes {        // device, dense row-major width x height; any may be NULL
+  unsigned long long* key;
+  float* depth;
+  uint32_t* index;
+  float* normal;             // three floats per pixel
+  uint32_t* color;           // the winner's row-5 word
+};
+struct RenderShape {
+  int waves, workgroups;
+};
+void launch_render_clear(hipStream_t stream, unsigned long long* keys, uint32_t pixels);
+// one lane per surfel, atomic minima into `keys`; counters != NULL: the census variant, which adds the candidate tests to counters[0]
+// and the candidates that contributed a key (each one atomic) to counters[1]
+void launch_render_splat(hipStream_t stream, const Intrinsics& view, const RenderParams& rp, const SurfelsView& s, const RenderShape& shape,
+                         unsigned long long* keys, unsigned long long* counters);
+void launch_render_resolve(hipStream_t stream, const RenderParams& rp, const SurfelsView& s, const unsigned long long* keys, uint32_t pixels,
+                           const RenderPlanes& out);
+
 }  // namespace bahip

@@ -46,6 +46,8 @@ def _load():
         L.dba_bundle_adjustment.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
         L.dba_compute_cost.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(capi.Cost), C.POINTER(capi.Cost)]
         L.dba_compute_surfel_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+        L.dba_render_surfels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float),
+                                         C.POINTER(capi.RenderOptions)] + [C.c_void_p] * 4 + [C.POINTER(C.c_float)]
         L.dba_surfel_count.restype = C.c_uint32
         L.dba_surfel_count.argtypes = [C.c_void_p]
         L.dba_surfels_size.restype = C.c_uint32
@@ -258,6 +260,27 @@ class DirectBA:
         out = {name: np.zeros(n, np.float64) for name in ("depth", "descriptor_1", "descriptor_2")}
         out.update({name: np.zeros(n, np.uint32) for name in ("depth_residuals", "descriptor_pairs")})
         assert self.L.dba_compute_surfel_costs(self.h, self.stream, n, *[a.ctypes.data for a in out.values()]) == 0
+        return out
+
+    def render_surfels(self, keyframe=None, view_camera=None, width=None, height=None, global_T_frame=None, options=None):
+        """DirectBA::RenderKeyframeView (keyframe: an id -- the depth camera at that keyframe's pose) or DirectBA::RenderSurfels (the
+        camera fx, fy, cx, cy of width x height pixels at the pose global_T_frame, 7 floats): the surfel map seen from that camera.
+        options: a capi.RenderOptions (default: discs of at most 4 px, back faces culled).  Returns a dict of numpy arrays of height x
+        width pixels -- depth (float32, 0 where empty), index (uint32, 0xFFFFFFFF where empty), normal (x 3, float32), color (x 4,
+        uint8) -- and frame_T_global, the 12 floats the render used."""
+        if keyframe is not None:
+            width, height, cam, pose, keyframe = self.width, self.height, None, None, int(keyframe)
+        else:
+            cam = _F4(*[float(v) for v in view_camera])
+            pose = (C.c_float * 7)(*[float(v) for v in global_T_frame])
+            width, height, keyframe = int(width), int(height), -1
+        out = dict(depth=np.zeros((height, width), np.float32), index=np.zeros((height, width), np.uint32),
+                   normal=np.zeros((height, width, 3), np.float32), color=np.zeros((height, width, 4), np.uint8))
+        F = (C.c_float * 12)()
+        opt = options if options is not None else capi.RenderOptions()
+        assert self.L.dba_render_surfels(self.h, self.stream, keyframe, cam, width, height, pose, C.byref(opt),
+                                         *[a.ctypes.data for a in out.values()], F) == 0
+        out["frame_T_global"] = np.array(list(F), np.float32)
         return out
 
     def BundleAdjustment(self, optimize_depth_intrinsics=False, optimize_color_intrinsics=False, do_surfel_updates=False,

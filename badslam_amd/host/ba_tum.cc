@@ -13,7 +13,12 @@
 //          [--ba_call_iterations N] [--baseline_fx F] [--spatial_sort_cell C] [--row_major_creation]
 //          [--bilateral_sigma_xy S] [--bilateral_sigma_inv_depth S] [--bilateral_radius_factor R] [--report_cost]
 //          [--pcg_step_control] [--pose_step_control] [--geometry_step_control] [--intrinsics_step_control]
+//          [--render_dir DIR [--render_mode point|disc] [--render_max_radius N] [--render_radius_factor F]]
 //
+// --render_dir DIR: after the last BA call the map as every keyframe sees it (DirectBA::RenderKeyframeView: the depth camera at the
+// keyframe's final pose; discs of at most 4 px unless the --render_* options say otherwise), two files per keyframe id in the existing
+// directory DIR: render_%06d_color.ppm (binary P6: the surfels' colours, black where no surfel is seen) and render_%06d_depth.pgm (binary
+// P5, 16 bit, big-endian, in the unit of the input depth images: min(65534, (int)(depth / raw_to_float_depth + 0.5f)), 0 = no surfel).
 // --report_cost: prints the value of the BA objective (DirectBA::ComputeCost: total and the depth / descriptor sums and counts) before
 // the first and after the last BA call.
 // --pose_step_control: without --pcg, damped pose steps kept per keyframe only if its cost falls (DirectBA::SetPoseStepControl, its defaults)
@@ -88,6 +93,37 @@ static int DecodePng(const char* path, const char* kind, const char* out_path) {
   return 0;
 }
 
+// --render_dir: the two PNM files of one rendered keyframe view (rgbd_io has no PNG encoder)
+static bool WriteRenderedView(const std::string& dir, int id, const DirectBA::RenderedView& view, float raw_to_float_depth) {
+  const size_t n = (size_t)view.width * view.height;
+  char name[64];
+  snprintf(name, sizeof(name), "/render_%06d_color.ppm", id);
+  FILE* f = fopen((dir + name).c_str(), "wb");
+  if (!f) return false;
+  vector<unsigned char> rgb(3 * n);
+  for (size_t p = 0; p < n; ++p)
+    for (int c = 0; c < 3; ++c) rgb[3 * p + c] = view.color[4 * p + c];
+  fprintf(f, "P6\n%d %d\n255\n", view.width, view.height);
+  bool ok = fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
+  ok = (fclose(f) == 0) && ok;
+  snprintf(name, sizeof(name), "/render_%06d_depth.pgm", id);
+  f = fopen((dir + name).c_str(), "wb");
+  if (!f) return false;
+  vector<unsigned char> depth(2 * n);
+  for (size_t p = 0; p < n; ++p) {
+    unsigned value = 0;
+    if (view.index[p] != 0xFFFFFFFFu) {
+      const float units = view.depth[p] / raw_to_float_depth + 0.5f;
+      value = units >= 65534.f ? 65534u : (unsigned)(int)units;
+    }
+    depth[2 * p] = (unsigned char)(value >> 8);
+    depth[2 * p + 1] = (unsigned char)(value & 0xff);
+  }
+  fprintf(f, "P5\n%d %d\n65535\n", view.width, view.height);
+  ok = (fwrite(depth.data(), 1, depth.size(), f) == depth.size()) && ok;
+  return (fclose(f) == 0) && ok;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 3 && !strcmp(argv[1], "--check-dataset")) return CheckDataset(argv[2], argc > 3 ? argv[3] : nullptr);
   if (argc == 5 && !strcmp(argv[1], "--decode-png")) return DecodePng(argv[2], argv[3], argv[4]);
@@ -104,7 +140,8 @@ int main(int argc, char** argv) {
   bool row_major_creation = false, report_cost = false, pcg_step_control = false, pose_step_control = false, geometry_step_control = false;
   bool intrinsics_step_control = false;
   bool use_pcg = false, intrinsics = false, incremental = false, parallel_ba = false;
-  std::string save_state, load_state;
+  std::string save_state, load_state, render_dir;
+  DirectBA::RenderOptions render_options;
   PreprocessConfig config;
   for (int i = 4; i < argc; ++i) {
     const std::string a = argv[i];
@@ -131,10 +168,18 @@ int main(int argc, char** argv) {
     else if (a == "--parallel_ba") incremental = parallel_ba = true;
     else if (a == "--save_state" && i + 1 < argc) save_state = argv[++i];
     else if (a == "--load_state" && i + 1 < argc) load_state = argv[++i];
+    else if (a == "--render_dir" && i + 1 < argc) render_dir = argv[++i];
+    else if (a == "--render_mode" && i + 1 < argc && (!strcmp(argv[i + 1], "point") || !strcmp(argv[i + 1], "disc"))) render_options.disc = !strcmp(argv[++i], "disc");
+    else if (a == "--render_max_radius" && i + 1 < argc) render_options.max_radius_px = atoi(argv[++i]);
+    else if (a == "--render_radius_factor" && i + 1 < argc) render_options.radius_factor = (float)atof(argv[++i]);
     else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
   if (intrinsics_step_control && (!intrinsics || use_pcg)) {
     fprintf(stderr, "--intrinsics_step_control needs --intrinsics and the alternating scheme (no --pcg)\n");
+    return 2;
+  }
+  if (render_options.max_radius_px < 0 || render_options.max_radius_px > 16 || !(render_options.radius_factor > 0.f)) {
+    fprintf(stderr, "--render_max_radius takes 0 .. 16, --render_radius_factor a factor > 0\n");
     return 2;
   }
   if (bahip_device_count() <= 0) { fprintf(stderr, "no HIP device (there is no CPU fallback)\n"); return 99; }
@@ -252,6 +297,18 @@ int main(int argc, char** argv) {
     if (!SaveCalibration(stream, ba, out)) return 1;
     if (!SavePointCloudAsPLY(stream, ba, out + ".ply")) return 1;
     printf("wrote %s.{poses.txt,depth_intrinsics.txt,color_intrinsics.txt,deformation.txt,ply}\n", out.c_str());
+    if (!render_dir.empty()) {
+      int views = 0;
+      for (const shared_ptr<Keyframe>& kf : ba.keyframes()) {
+        if (!kf) continue;
+        DirectBA::RenderedView view;
+        ba.RenderKeyframeView(stream, (int)kf->id(), render_options, &view);
+        if (!WriteRenderedView(render_dir, (int)kf->id(), view, raw_to_float_depth)) { fprintf(stderr, "cannot write the rendered views to %s\n", render_dir.c_str()); return 1; }
+        ++views;
+      }
+      printf("wrote %d rendered view(s) (%s, at most %d px) to %s\n", views, render_options.disc ? "discs" : "points", render_options.max_radius_px,
+             render_dir.c_str());
+    }
   }
   bahip_stream_destroy(stream);
   return 0;

@@ -171,6 +171,38 @@ int dba_compute_surfel_costs(dba_handle* h, void* stream, uint32_t capacity, dou
   return 0;
 }
 
+int dba_render_surfels(dba_handle* h, void* stream, int keyframe_id, const float view_camera[4], int width, int height,
+                       const float global_T_frame[7], const bahip_render_options* options, float* depth, uint32_t* index, float* normal,
+                       uint8_t* color, float frame_T_global_out[12]) {
+  if (!options) return 1;
+  DirectBA::RenderOptions o;
+  o.disc = options->mode == BAHIP_RENDER_DISC;
+  o.max_radius_px = options->max_radius_px;
+  o.cull_backfaces = options->cull_backfaces != 0;
+  o.radius_factor = options->radius_factor;
+  o.min_depth = options->min_depth;
+  o.max_depth = options->max_depth;
+  o.index_base = options->index_base;
+  DirectBA::RenderedView view;
+  SE3f pose;
+  if (keyframe_id >= 0) {
+    Keyframe* kf = get_kf(h, keyframe_id);
+    if (!kf) return 1;
+    pose = kf->global_T_frame();
+    h->ba->RenderKeyframeView(static_cast<hipStream_t>(stream), keyframe_id, o, &view);
+  } else {
+    if (!view_camera || !global_T_frame || width < 1 || height < 1) return 1;
+    pose = SE3f(global_T_frame);
+    h->ba->RenderSurfels(static_cast<hipStream_t>(stream), PinholeCamera4f(width, height, view_camera), pose, o, &view);
+  }
+  if (depth) std::copy(view.depth.begin(), view.depth.end(), depth);
+  if (index) std::copy(view.index.begin(), view.index.end(), index);
+  if (normal) std::copy(view.normal.begin(), view.normal.end(), normal);
+  if (color) std::copy(view.color.begin(), view.color.end(), color);
+  if (frame_T_global_out) pose.inverse().matrix3x4(frame_T_global_out);
+  return 0;
+}
+
 uint32_t dba_surfel_count(dba_handle* h) { return h->ba->surfel_count(); }
 uint32_t dba_surfels_size(dba_handle* h) { return h->ba->surfels_size(); }
 int dba_set_surfel_count(dba_handle* h, uint32_t surfel_count, uint32_t surfels_size) {

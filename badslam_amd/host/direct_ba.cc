@@ -569,6 +569,47 @@ void DirectBA::ComputeSurfelCosts(hipStream_t stream, SurfelCosts* out) {
   BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
 }
 
+void DirectBA::RenderSurfels(hipStream_t stream, const PinholeCamera4f& view, const SE3f& global_T_frame, const RenderOptions& options,
+                             RenderedView* out) {
+  BAHIP_CHECKED_CALL(bahip_context_set_stream(ctx_, stream));
+  const bahip_surfels s = SurfelsStruct(/*with_active*/ false);
+  const bahip_camera cam = ToBahipCamera(view);
+  CHECK_GE(cam.width, 1); CHECK_GE(cam.height, 1);
+  const size_t n = (size_t)cam.width * (size_t)cam.height;
+  float F[12];
+  global_T_frame.inverse().matrix3x4(F);
+  bahip_render_options o{};
+  o.mode = options.disc ? BAHIP_RENDER_DISC : BAHIP_RENDER_POINT;
+  o.max_radius_px = options.max_radius_px;
+  o.cull_backfaces = options.cull_backfaces ? 1 : 0;
+  o.radius_factor = options.radius_factor;
+  o.min_depth = options.min_depth;
+  o.max_depth = options.max_depth;
+  o.index_base = options.index_base;
+  // one device block for the four planes: depth, index, three words of normal and one of colour per pixel
+  CUDABuffer<uint32_t> planes(1, (int)(6 * n));
+  uint32_t* base = planes.ToCUDA().address();
+  bahip_render_out dev{};
+  dev.depth = reinterpret_cast<float*>(base);
+  dev.index = base + n;
+  dev.normal = reinterpret_cast<float*>(base + 2 * n);
+  dev.color = reinterpret_cast<uint8_t*>(base + 5 * n);
+  BAHIP_CHECKED_CALL(bahip_render_surfels(ctx_, &s, &cam, F, &o, &dev));
+  out->width = cam.width; out->height = cam.height;
+  out->depth.resize(n); out->index.resize(n); out->normal.resize(3 * n); out->color.resize(4 * n);
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->depth.data(), dev.depth, sizeof(float) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->index.data(), dev.index, sizeof(uint32_t) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->normal.data(), dev.normal, sizeof(float) * 3 * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->color.data(), dev.color, 4 * n, 2));
+  BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
+}
+
+void DirectBA::RenderKeyframeView(hipStream_t stream, int keyframe_index, const RenderOptions& options, RenderedView* out) {
+  CHECK_GE(keyframe_index, 0); CHECK_LT(keyframe_index, (int)keyframes_.size());
+  CHECK(keyframes_[keyframe_index] != nullptr);
+  RenderSurfels(stream, depth_camera_, keyframes_[keyframe_index]->global_T_frame(), options, out);
+}
+
 void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsics, bool optimize_color_intrinsics,
                                 bool do_surfel_updates, bool optimize_poses, bool optimize_geometry, int min_iterations,
                                 int max_iterations, bool use_pcg, int active_keyframe_window_start,

@@ -11,6 +11,8 @@
 //   - SetRunParallel is declared but never defined in the reference (B/direct_ba.h:172): omitted.
 #pragma once
 
+#include <limits>
+
 #include "camera_frustum.h"
 #include "keyframe.h"
 
@@ -63,6 +65,28 @@ class DirectBA {
     vector<uint32_t> depth_residuals, descriptor_pairs;
   };
   void ComputeSurfelCosts(hipStream_t stream, SurfelCosts* out);
+  // The surfel map seen from a camera (bahip_render_surfels; DESIGN.md section 3, "Rendered views of the map"): per pixel of `view` at
+  // pose global_T_frame the nearest surfel's depth, buffer index, normal in the view's frame and colour, row-major.  Empty pixels hold
+  // depth 0, index 0xFFFFFFFF, normal (0, 0, 0), colour 0.  Binds nothing; under surfel sharding the view of this rank's shard.  Waits
+  // for the stream.
+  struct RenderOptions {
+    bool disc = true;              // false: one pixel per surfel
+    int max_radius_px = 4;         // 0 .. 16: half-width of a disc's candidate box (part of the definition of the image)
+    bool cull_backfaces = true;
+    float radius_factor = 1.f;
+    float min_depth = 0.f, max_depth = std::numeric_limits<float>::infinity();
+    uint32_t index_base = 0;
+  };
+  struct RenderedView {
+    int width = 0, height = 0;
+    vector<float> depth;           // width * height
+    vector<uint32_t> index;        // width * height
+    vector<float> normal;          // 3 * width * height
+    vector<uint8_t> color;         // 4 * width * height: the surfels' colour row as stored (r, g, b, the fourth byte)
+  };
+  void RenderSurfels(hipStream_t stream, const PinholeCamera4f& view, const SE3f& global_T_frame, const RenderOptions& options, RenderedView* out);
+  // ... from keyframe `keyframe_index` (an id; it must exist): the depth camera at that keyframe's pose
+  void RenderKeyframeView(hipStream_t stream, int keyframe_index, const RenderOptions& options, RenderedView* out);
   void UpdateKeyframeCoVisibility(const shared_ptr<Keyframe>& keyframe);
   // B/direct_ba.h:167, B/direct_ba.cc:456-459: surfel colours := mean of their observations in all keyframes (before an export).
   void AssignColors(hipStream_t stream);

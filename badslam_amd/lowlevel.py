@@ -24,6 +24,17 @@ def live_allocations(lib=None):
     return int(count.value), int(nbytes.value)
 
 
+def split_render_key(key):
+    """A key plane of bahip_render_surfels (uint64: bits(depth) << 32 | index, all ones where empty) as (depth float32, index uint32) with
+    the empty pixels as the call's own depth and index planes have them: +0.0 and 0xFFFFFFFF.  The elementwise minimum of the key planes
+    of several renders (shards, clouds with their own index_base) is the key plane of their union."""
+    key = np.ascontiguousarray(key, np.uint64)
+    empty = key == np.uint64(0xFFFFFFFFFFFFFFFF)
+    depth = np.where(empty, np.uint32(0), (key >> np.uint64(32)).astype(np.uint32)).astype(np.uint32).view(np.float32)
+    index = (key & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    return depth, index
+
+
 class DeviceBuffer2D:
     """libvis CUDABuffer<T> semantics: (height, width) pitched device allocation."""
 
@@ -641,6 +652,33 @@ class Scene:
             out = capi.SurfelCosts(*[bufs[name].ptr if name in bufs else None for name, _ in self.SURFEL_COST_PLANES])
             capi.check(self.lib.bahip_evaluate_surfel_costs(self.ctx.handle, int(use_depth), int(use_desc), C.byref(s), C.byref(out)))
             return {name: b.download()[0, :n].copy() for name, b in bufs.items()}
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    RENDER_PLANES = (("key", np.uint64, 1), ("depth", np.float32, 1), ("index", np.uint32, 1), ("normal", np.float32, 3), ("color", np.uint8, 4))
+
+    def render_surfels(self, view_cam, frame_T_global, options=None, planes=None, prefill=None):
+        """The surfel buffer seen from the camera `view_cam` (capi.Camera) at frame_T_global (12 floats): bahip_render_surfels.  A dict
+        of numpy arrays of the view's height x width pixels -- key (uint64), depth (float32), index (uint32), normal (x 3, float32),
+        color (x 4, uint8).  options: a capi.RenderOptions (default: its defaults); planes: the names to ask for (the others are passed
+        as NULL and left out of the dict); prefill: a byte value the device planes are filled with before the call (tests: an entry the
+        call did not write shows).  Needs no bound keyframes."""
+        w, h = int(view_cam.width), int(view_cam.height)
+        n = max(1, w * h)
+        wanted = [name for name, _, _ in self.RENDER_PLANES] if planes is None else list(planes)
+        bufs = {name: DeviceBuffer2D(self.ctx, 1, n, dtype, channels) for name, dtype, channels in self.RENDER_PLANES if name in wanted}
+        try:
+            if prefill is not None:
+                for b in bufs.values():
+                    b.clear(prefill)
+            F = (C.c_float * 12)(*[float(v) for v in frame_T_global])
+            s = self.surfels_struct()
+            opt = options if options is not None else capi.RenderOptions()
+            out = capi.RenderOut(*[bufs[name].ptr if name in bufs else None for name, _, _ in self.RENDER_PLANES])
+            capi.check(self.lib.bahip_render_surfels(self.ctx.handle, C.byref(s), C.byref(view_cam), F, C.byref(opt), C.byref(out)))
+            shapes = {name: (h, w) if channels == 1 else (h, w, channels) for name, _, channels in self.RENDER_PLANES}
+            return {name: b.download()[0, :w * h].reshape(shapes[name]).copy() for name, b in bufs.items()}
         finally:
             for b in bufs.values():
                 b.free()

@@ -69,6 +69,14 @@ int dba_compute_cost(dba_handle* h, void* hip_stream, bahip_cost* total, bahip_c
  * unsharded values on every rank; surfel sharding: this rank's shard.  Returns non-zero when capacity is too small. */
 int dba_compute_surfel_costs(dba_handle* h, void* hip_stream, uint32_t capacity, double* depth, double* descriptor_1, double* descriptor_2,
                              uint32_t* depth_residuals, uint32_t* descriptor_pairs);
+/* DirectBA::RenderSurfels / RenderKeyframeView (ours): the surfel map seen from a camera (bahip_render_surfels), row-major host planes
+ * of width * height pixels, any may be NULL: depth, index, normal (3 floats per pixel), color (4 bytes per pixel).  keyframe_id >= 0:
+ * the depth camera at that keyframe's pose (view_camera, width, height and global_T_frame are ignored; the planes have the depth
+ * image's size); keyframe_id < 0: the camera (fx, fy, cx, cy; pixel-corner convention) and pose given.  options->mode: BAHIP_RENDER_POINT
+ * or BAHIP_RENDER_DISC.  frame_T_global_out: NULL or the 3 x 4 matrix the render used.  Returns non-zero on a bad argument. */
+int dba_render_surfels(dba_handle* h, void* hip_stream, int keyframe_id, const float view_camera[4], int width, int height,
+                       const float global_T_frame[7], const bahip_render_options* options, float* depth, uint32_t* index, float* normal,
+                       uint8_t* color, float frame_T_global_out[12]);
 
 /* accessors */
 uint32_t dba_surfel_count(dba_handle* h);

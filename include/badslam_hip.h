@@ -627,6 +627,56 @@ int bahip_evaluate_surfel_costs(bahip_context* ctx, int use_depth, int use_desc,
  * one; 0 / -1 = the default. */
 int bahip_debug_set_surfel_cost_shape(int waves, int workgroups, int slice_surfels, int tile_order);
 
+/* ---- rendered views of the map (kernels_render.hip; DESIGN.md section 3, "Rendered views of the map") ------------------------------
+ * The surfel buffer seen from the camera `view` at frame_T_global (3 x 4 row-major, as bahip_evaluate_frame_cost takes it): per pixel
+ * the nearest surfel.  `view` follows the depth camera's conventions (pixel-corner projection; pixel-centre unprojection with
+ * fx_inv = 1 / fx, cx_inv = -(cx - 0.5) / fx); it need not be a camera of the context.  Activation flags are ignored.
+ * Per surfel i with a finite position (binary32, nothing contracted, either arithmetic flavour of the context): local = F p, nl = R n,
+ * local.z > 0; nd = nl . local < 0 (the surfel faces the camera); pxx = fx local.x / local.z + cx, pxy likewise, both below 1e6 in
+ * magnitude; (px, py) = their floors.  mode BAHIP_RENDER_POINT: the one candidate pixel (px, py) if inside the image, at depth
+ * t = local.z.  mode BAHIP_RENDER_DISC (r^2 finite and > 0): rs2 = radius_factor^2 r^2, half-width h = min(max_radius_px,
+ * (int)(max(fx, fy) sqrt(rs2) / local.z) + 1); the candidates are the pixels of [px - h, px + h] x [py - h, py + h] inside the image
+ * (the centre pixel itself may lie outside); candidate (x, y) with the ray d through its centre is covered when den = nl . d < 0 and
+ * the point t d of the surfel's plane, t = nd / den, lies within sqrt(rs2) of the surfel: |t d - local|^2 <= rs2.  A pixel outside the
+ * box is not covered: max_radius_px (0 .. 16) is part of the definition.  cull_backfaces = 0 drops the two sign tests and requires
+ * t > 0 instead.  A candidate with min_depth <= t <= max_depth contributes the key (bits(t) << 32) | (index_base + i); a pixel holds the
+ * minimum key over its candidates -- the nearest surfel, the lower index among equal depths, whatever the launch shape, the surfel
+ * order or the order of arrival -- and all ones when it has none.
+ * Output planes: device memory, dense row-major width x height, borrowed for the call, any may be NULL.  key: as above; depth: t
+ * (+0.0 where empty); index: index_base + i (0xFFFFFFFF where empty); normal: three floats per pixel, the winner's nl (0, 0, 0 where
+ * empty); color: four bytes per pixel, the winner's colour row as stored (0 where empty; aligned to 4 bytes).  Every entry of every
+ * non-NULL plane is written by every successful call; with no surfels every pixel is empty.
+ * The call fails when width or height < 1, width * height > 2^26, mode is neither, max_radius_px is outside 0 .. 16, radius_factor is
+ * not > 0, min_depth > max_depth, or index_base + surfels_size would reach 0xFFFFFFFF; a failed call launches nothing.
+ * Asynchronous on the context's stream.  Needs no bound keyframe and no bahip_set_intrinsics.  Either sharding: nothing is exchanged;
+ * a surfel shard renders the shard it is given.  Shards (or several clouds) are combined by the caller: render each with its own
+ * index_base and take the elementwise minimum of the key planes. */
+#define BAHIP_RENDER_POINT 0
+#define BAHIP_RENDER_DISC 1
+typedef struct bahip_render_options {
+  int32_t mode, max_radius_px, cull_backfaces;
+  float radius_factor, min_depth, max_depth;
+  uint32_t index_base;
+} bahip_render_options;
+typedef struct bahip_render_out {        /* device pointers, borrowed; width * height pixels each; any may be NULL */
+  uint64_t* key;
+  float* depth;
+  uint32_t* index;
+  float* normal;
+  uint8_t* color;
+} bahip_render_out;
+int bahip_render_surfels(bahip_context* ctx, const bahip_surfels* surfels, const bahip_camera* view, const float frame_T_global[12],
+                         const bahip_render_options* options, const bahip_render_out* out);
+/* Launch shape of the splat (test hook; results never depend on it): wavefronts per workgroup 1 .. 8, workgroups >= 1; 0 = the default. */
+int bahip_debug_set_render_shape(int waves, int workgroups);
+/* The kernels bahip_render_surfels launches (scripts/render_eval.py takes their times by difference): 1 clear, 2 splat, 4 resolve,
+ * or-ed; 0 = all.  With a stage missing the planes are not a rendered view. */
+int bahip_debug_set_render_stages(int stages);
+/* One clear and one counting splat of the same view, then a wait: counts_out = candidate tests, candidates that contributed a key
+ * (one atomic each), covered pixels. */
+int bahip_debug_render_census(bahip_context* ctx, const bahip_surfels* surfels, const bahip_camera* view, const float frame_T_global[12],
+                              const bahip_render_options* options, unsigned long long counts_out[3]);
+
 /* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
  * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
  * e = 1e-8 + prior(u) as before and t = lambda * M[u] (one binary32 product), the preconditioner divides by ((M[u] + 1e-8) + prior(u))
