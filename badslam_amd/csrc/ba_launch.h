@@ -588,4 +588,13 @@ void launch_render_splat(hipStream_t stream, const Intrinsics& view, const Rende
 void launch_render_resolve(hipStream_t stream, const RenderParams& rp, const SurfelsView& s, const unsigned long long* keys, uint32_t pixels,
                            const RenderPlanes& out);
 
+// kernels_ingest.hip: a frame brought to the BA's pyramid level (exists once: integer rules and one correctly rounded division, the same
+// under either flavour).  The callers have checked sizes and pitches; the downscale's blocks are at most kIngestMaxBlock on a side.
+constexpr int kIngestMaxBlock = 9, kIngestMaxLevels = 3;
+void launch_median_densify(hipStream_t stream, const uint16_t* in, uint32_t in_pitch, uint16_t* out, uint32_t out_pitch, int w, int h);
+void launch_downscale_depth_median(hipStream_t stream, const uint16_t* in, uint32_t in_pitch, int in_w, int in_h, uint16_t* out,
+                                   uint32_t out_pitch, int out_w, int out_h);
+// non-zero: levels outside 1 .. kIngestMaxLevels
+int launch_downscale_rgb_half(hipStream_t stream, const uint8_t* in, uint32_t in_pitch, int w, int h, int levels, uint8_t* out, uint32_t out_pitch);
+
 }  // namespace bahip

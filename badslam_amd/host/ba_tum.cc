@@ -14,7 +14,14 @@
 //          [--bilateral_sigma_xy S] [--bilateral_sigma_inv_depth S] [--bilateral_radius_factor R] [--report_cost]
 //          [--pcg_step_control] [--pose_step_control] [--geometry_step_control] [--intrinsics_step_control]
 //          [--render_dir DIR [--render_mode point|disc] [--render_max_radius N] [--render_radius_factor F]]
+//          [--pyramid_level_for_depth N] [--pyramid_level_for_color N] [--median_filter_and_densify_iterations N]
 //
+// --pyramid_level_for_depth N / --pyramid_level_for_color N (0 .. 3): the BA runs on depth / colour images of 2^-N the dataset's size, with
+// the dataset's cameras Scaled(1 / 2^N) (B/main.cc:457-460); every frame's depth goes through the median downscale and its colour through
+// N halvings on the GPU (CreateKeyframeFromFrame).  --median_filter_and_densify_iterations N: that many rounds of the 3 x 3 median
+// filter and densification on the raw depth first; not together with a depth level > 0 (as in the reference).  The calibration files
+// are written from the BA cameras as they are, i.e. at the pyramid level (as B/io.cc does).  A run resumed with --load_state needs the
+// options of the run that saved.
 // --render_dir DIR: after the last BA call the map as every keyframe sees it (DirectBA::RenderKeyframeView: the depth camera at the
 // keyframe's final pose; discs of at most 4 px unless the --render_* options say otherwise), two files per keyframe id in the existing
 // directory DIR: render_%06d_color.ppm (binary P6: the surfels' colours, black where no surfel is seen) and render_%06d_depth.pgm (binary
@@ -172,6 +179,9 @@ int main(int argc, char** argv) {
     else if (a == "--render_mode" && i + 1 < argc && (!strcmp(argv[i + 1], "point") || !strcmp(argv[i + 1], "disc"))) render_options.disc = !strcmp(argv[++i], "disc");
     else if (a == "--render_max_radius" && i + 1 < argc) render_options.max_radius_px = atoi(argv[++i]);
     else if (a == "--render_radius_factor" && i + 1 < argc) render_options.radius_factor = (float)atof(argv[++i]);
+    else if (a == "--pyramid_level_for_depth" && i + 1 < argc) config.pyramid_level_for_depth = atoi(argv[++i]);
+    else if (a == "--pyramid_level_for_color" && i + 1 < argc) config.pyramid_level_for_color = atoi(argv[++i]);
+    else if (a == "--median_filter_and_densify_iterations" && i + 1 < argc) config.median_filter_and_densify_iterations = atoi(argv[++i]);
     else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
   if (intrinsics_step_control && (!intrinsics || use_pcg)) {
@@ -182,12 +192,22 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--render_max_radius takes 0 .. 16, --render_radius_factor a factor > 0\n");
     return 2;
   }
+  std::string refusal;
+  if (!ValidatePreprocessConfig(config, &refusal)) {
+    fprintf(stderr, "%s\n", refusal.c_str());
+    return 2;
+  }
   if (bahip_device_count() <= 0) { fprintf(stderr, "no HIP device (there is no CPU fallback)\n"); return 99; }
 
   RGBDVideo<Vec3u8, u16> video;
   if (!ReadTUMRGBDDatasetAssociatedAndCalibrated(dataset.c_str(), trajectory.c_str(), &video)) return 1;
   printf("read %zu frames, %d x %d\n", (size_t)video.frame_count(), video.depth_camera()->width(), video.depth_camera()->height());
   if (video.frame_count() == 0) return 1;
+  // B/main.cc:457-460, B/bad_slam.cc:125-142: the BA's cameras are the video's at the pyramid levels
+  const PinholeCamera4f ba_depth_camera = video.depth_camera()->Scaled(1.0 / (1 << config.pyramid_level_for_depth));
+  const PinholeCamera4f ba_color_camera = video.color_camera()->Scaled(1.0 / (1 << config.pyramid_level_for_color));
+  printf("BA resolution: depth %d x %d (pyramid level %d), colour %d x %d (pyramid level %d)\n", ba_depth_camera.width(), ba_depth_camera.height(),
+         config.pyramid_level_for_depth, ba_color_camera.width(), ba_color_camera.height(), config.pyramid_level_for_color);
 
   hipStream_t stream = nullptr;
   BAHIP_CHECKED_CALL(bahip_stream_create(&stream));
@@ -195,7 +215,7 @@ int main(int argc, char** argv) {
     // B/bad_slam.cc:125-142 with the defaults of B/bad_slam_config.h
     DirectBA ba(/*max_surfel_count*/ 25 * 1000 * 1000, raw_to_float_depth, baseline_fx, cell, /*surfel_merge_dist_factor*/ 0.8f,
                 /*min_observation_count_while_bootstrapping_1*/ 1, /*min_observation_count_while_bootstrapping_2*/ 2, /*min_observation_count*/ 2,
-                *video.color_camera(), *video.depth_camera(), /*pyramid_level_for_color*/ 0, /*use_depth_residuals*/ true,
+                ba_color_camera, ba_depth_camera, config.pyramid_level_for_color, /*use_depth_residuals*/ true,
                 /*use_descriptor_residuals*/ true, nullptr, SE3f());
     if (spatial_sort_cell >= 0.f) ba.SetSpatialSortCellSize(spatial_sort_cell);
     if (row_major_creation) ba.SetRowMajorCreation(true);
@@ -238,6 +258,7 @@ int main(int argc, char** argv) {
         const SE3f last_kf_tr_this_kf = (f == 0) ? SE3f() : previous_keyframe_pose.inverse() * initial_pose;
         previous_keyframe_pose = initial_pose;
         shared_ptr<Keyframe> kf = CreateKeyframeFromFrame(stream, config, ba, video, (int)f);
+        if (!kf) return 2;
         const u32 newest_frame = (u32)std::min<usize>(f + interval - 1, video.frame_count() - 1);
         scheduler.SetLastFrameIndex((int)newest_frame);
         scheduler.AddKeyframe(kf, last_kf_tr_this_kf);
@@ -254,7 +275,11 @@ int main(int argc, char** argv) {
         printf("loaded %s: %zu keyframes, %u surfels, BA iteration count %d\n", load_state.c_str(), ba.keyframes().size(), ba.surfel_count(),
                ba.ba_iteration_count());
       } else {
-        for (usize f = 0; f < video.frame_count(); f += interval) ba.AddKeyframe(CreateKeyframeFromFrame(stream, config, ba, video, (int)f));
+        for (usize f = 0; f < video.frame_count(); f += interval) {
+          shared_ptr<Keyframe> kf = CreateKeyframeFromFrame(stream, config, ba, video, (int)f);
+          if (!kf) return 2;
+          ba.AddKeyframe(kf);
+        }
       }
       printf("%zu keyframes\n", ba.keyframes().size());
       RememberKeyframePoses(&ba, &original_keyframe_T_global);   // B/bad_slam.cc:1230 (before the BA that moves them)

@@ -109,6 +109,13 @@ class PinholeCamera4f {
   int width() const { return width_; }
   int height() const { return height_; }
   const float* parameters() const { return p_; }
+  // L/camera.h:1696-1705 with ScaleParameters (:1086-1096): all four parameters times the factor (pixel-corner convention: cx and cy
+  // scale with the image), width and height rounded to the nearest.  The camera a pyramid level is adjusted with: Scaled(1 / 2^level).
+  PinholeCamera4f Scaled(double factor) const {
+    const float f = (float)factor;
+    const float scaled[4] = {p_[0] * f, p_[1] * f, p_[2] * f, p_[3] * f};
+    return PinholeCamera4f((int)(factor * width_ + 0.5f), (int)(factor * height_ + 0.5f), scaled);
+  }
   // Direction (z = 1) through a pixel given in the pixel-centre / pixel-corner convention.
   void UnprojectFromPixelCenterConv(float x, float y, float out[3]) const {
     out[0] = (x - (p_[2] - 0.5f)) / p_[0]; out[1] = (y - (p_[3] - 0.5f)) / p_[1]; out[2] = 1.f;

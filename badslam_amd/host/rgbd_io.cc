@@ -405,37 +405,89 @@ void ExtrapolateAndInterpolateKeyframePoseChanges(u32 start_frame, u32 end_frame
 }
 
 // ---- frame -> keyframe --------------------------------------------------------------------------------------------------
+bool ValidatePreprocessConfig(const PreprocessConfig& config, std::string* message) {
+  std::string reason;
+  if (config.pyramid_level_for_depth < 0 || config.pyramid_level_for_depth > 3 || config.pyramid_level_for_color < 0 || config.pyramid_level_for_color > 3)
+    reason = "pyramid_level_for_depth and pyramid_level_for_color must be in 0 .. 3";
+  else if (config.median_filter_and_densify_iterations < 0)
+    reason = "median_filter_and_densify_iterations must not be negative";
+  else if (config.pyramid_level_for_depth > 0 && config.median_filter_and_densify_iterations > 0)
+    reason = "Simultaneous downscaling and median filtering of depth maps is not implemented.";   // B/bad_slam.cc:672
+  if (message) *message = reason;
+  return reason.empty();
+}
+
 shared_ptr<Keyframe> CreateKeyframeFromFrame(hipStream_t stream, const PreprocessConfig& config, DirectBA& direct_ba,
                                              RGBDVideo<Vec3u8, u16>& rgbd_video, int frame_index) {
+  std::string refusal;
+  if (!ValidatePreprocessConfig(config, &refusal)) {
+    LOG(ERROR) << refusal;
+    return nullptr;
+  }
   shared_ptr<Image<u16>> depth_image = rgbd_video.depth_frame_mutable(frame_index)->GetImage();
   shared_ptr<Image<Vec3u8>> rgb_image = rgbd_video.color_frame_mutable(frame_index)->GetImage();
   CHECK(depth_image && rgb_image) << "cannot load the images of frame " << frame_index;
-  const int W = depth_image->width(), H = depth_image->height();
   const PinholeCamera4f depth_camera = direct_ba.depth_camera();
   const PinholeCamera4f color_camera = direct_ba.color_camera();
   const DepthParameters depth_params = direct_ba.depth_params();
   const float raw_to_float_depth = depth_params.raw_to_float_depth;
-  // the kernels address the images with the cameras' dimensions
-  CHECK(W == depth_camera.width() && H == depth_camera.height())
-      << "frame " << frame_index << ": depth image is " << W << " x " << H << ", the depth camera " << depth_camera.width() << " x " << depth_camera.height();
-  CHECK((int)rgb_image->width() == color_camera.width() && (int)rgb_image->height() == color_camera.height())
-      << "frame " << frame_index << ": colour image is " << rgb_image->width() << " x " << rgb_image->height() << ", the colour camera "
-      << color_camera.width() << " x " << color_camera.height();
+  const int W = depth_camera.width(), H = depth_camera.height();
+  const int full_W = depth_image->width(), full_H = depth_image->height();
+  const int color_W = color_camera.width(), color_H = color_camera.height();
+  const int full_color_W = rgb_image->width(), full_color_H = rgb_image->height();
+  // the kernels address the images with the cameras' dimensions: the frame at its pyramid level has them (the sizes as
+  // PinholeCamera4f::Scaled rounds them; at level 0 the frame's own)
+  const PinholeCamera4f zero_camera;
+  const PinholeCamera4f depth_level = PinholeCamera4f(full_W, full_H, zero_camera.parameters()).Scaled(1.0 / (1 << config.pyramid_level_for_depth));
+  const PinholeCamera4f color_level = PinholeCamera4f(full_color_W, full_color_H, zero_camera.parameters()).Scaled(1.0 / (1 << config.pyramid_level_for_color));
+  CHECK(depth_level.width() == W && depth_level.height() == H)
+      << "frame " << frame_index << ": depth image is " << full_W << " x " << full_H << " (" << depth_level.width() << " x " << depth_level.height()
+      << " at pyramid level " << config.pyramid_level_for_depth << "), the depth camera " << W << " x " << H;
+  CHECK(color_level.width() == color_W && color_level.height() == color_H)
+      << "frame " << frame_index << ": colour image is " << full_color_W << " x " << full_color_H << " (" << color_level.width() << " x "
+      << color_level.height() << " at pyramid level " << config.pyramid_level_for_color << "), the colour camera " << color_W << " x " << color_H;
 
   bahip_context* ctx = UtilityContext(stream);
   CUDABuffer<u16> depth_buffer(H, W), filtered_A(H, W), filtered_B(H, W), normals_buffer(H, W), radius_buffer(H, W);
-  CUDABuffer<u8> rgb_buffer(rgb_image->height(), rgb_image->width() * 3);
-  CUDABuffer<uchar4> color_buffer(rgb_image->height(), rgb_image->width());
-  depth_buffer.UploadAsync(stream, *depth_image);
-  rgb_buffer.UploadAsync(stream, reinterpret_cast<const u8*>(rgb_image->data()));
+  CUDABuffer<u8> rgb_buffer(color_H, color_W * 3);
+  CUDABuffer<uchar4> color_buffer(color_H, color_W);
+  // B/bad_slam.cc:657-689, on the device
+  const CUDABuffer<u16>* raw_depth = &depth_buffer;
+  if (config.pyramid_level_for_depth > 0) {
+    CUDABuffer<u16> full_depth(full_H, full_W);
+    full_depth.UploadAsync(stream, *depth_image);
+    BAHIP_CHECKED_CALL(bahip_downscale_depth_median(ctx, full_depth.ToCUDA().address(), (uint32_t)full_depth.ToCUDA().pitch(), full_W, full_H,
+                                                    depth_buffer.ToCUDA().address(), (uint32_t)depth_buffer.ToCUDA().pitch(), W, H));
+    BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));   // full_depth goes out of scope
+  } else {
+    depth_buffer.UploadAsync(stream, *depth_image);
+    // ping-pong between depth_buffer and filtered_B (free until the normals are computed)
+    CUDABuffer<u16>* target = &filtered_B;
+    CUDABuffer<u16>* source = &depth_buffer;
+    for (int iteration = 0; iteration < config.median_filter_and_densify_iterations; ++iteration) {
+      BAHIP_CHECKED_CALL(bahip_median_filter_and_densify(ctx, source->ToCUDA().address(), (uint32_t)source->ToCUDA().pitch(),
+                                                         target->ToCUDA().address(), (uint32_t)target->ToCUDA().pitch(), W, H));
+      std::swap(source, target);
+    }
+    raw_depth = source;
+  }
+  if (config.pyramid_level_for_color > 0) {
+    CUDABuffer<u8> full_rgb(full_color_H, full_color_W * 3);
+    full_rgb.UploadAsync(stream, reinterpret_cast<const u8*>(rgb_image->data()));
+    BAHIP_CHECKED_CALL(bahip_downscale_rgb_half(ctx, full_rgb.ToCUDA().address(), (uint32_t)full_rgb.ToCUDA().pitch(), full_color_W, full_color_H,
+                                                config.pyramid_level_for_color, rgb_buffer.ToCUDA().address(), (uint32_t)rgb_buffer.ToCUDA().pitch()));
+    BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));   // full_rgb goes out of scope
+  } else {
+    rgb_buffer.UploadAsync(stream, reinterpret_cast<const u8*>(rgb_image->data()));
+  }
   // B/bad_slam.cc:691-706
   BAHIP_CHECKED_CALL(bahip_compute_brightness(ctx, rgb_buffer.ToCUDA().address(), (uint32_t)rgb_buffer.ToCUDA().pitch(),
                                               reinterpret_cast<uint8_t*>(color_buffer.ToCUDA().address()), (uint32_t)color_buffer.ToCUDA().pitch(),
-                                              rgb_image->width(), rgb_image->height()));
+                                              color_W, color_H));
   BAHIP_CHECKED_CALL(bahip_bilateral_filtering_and_depth_cutoff(
       ctx, config.bilateral_filter_sigma_xy, config.bilateral_filter_sigma_inv_depth, config.bilateral_filter_radius_factor,
-      (uint16_t)(config.max_depth / raw_to_float_depth), raw_to_float_depth, depth_buffer.ToCUDA().address(),
-      (uint32_t)depth_buffer.ToCUDA().pitch(), filtered_A.ToCUDA().address(), (uint32_t)filtered_A.ToCUDA().pitch(), W, H));
+      (uint16_t)(config.max_depth / raw_to_float_depth), raw_to_float_depth, raw_depth->ToCUDA().address(),
+      (uint32_t)raw_depth->ToCUDA().pitch(), filtered_A.ToCUDA().address(), (uint32_t)filtered_A.ToCUDA().pitch(), W, H));
   // :716-722, :754-760
   const bahip_camera cam = ToBahipCamera(depth_camera);
   const bahip_depth_params dp = ToBahipDepthParams(depth_params);
@@ -725,6 +777,10 @@ bool LoadState(hipStream_t stream, const PreprocessConfig& config, RGBDVideo<Vec
     const KeyframeRecord& k = keyframe_records[i];
     if (k.id < 0) { direct_ba->keyframes_mutable()->push_back(nullptr); continue; }
     shared_ptr<Keyframe> keyframe = CreateKeyframeFromFrame(stream, config, *direct_ba, *rgbd_video, k.frame_index);
+    if (!keyframe) {   // a config CreateKeyframeFromFrame refuses (it has said why)
+      roll_back();
+      return false;
+    }
     direct_ba->AddKeyframe(keyframe);
     CHECK_EQ(keyframe->id(), k.id);
   }

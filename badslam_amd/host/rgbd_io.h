@@ -116,9 +116,21 @@ struct PreprocessConfig {            // defaults of B/bad_slam_config.h:96-122
   float bilateral_filter_sigma_xy = 1.5f;
   float bilateral_filter_radius_factor = 2.0f;
   float bilateral_filter_sigma_inv_depth = 0.005f;
+  // What a keyframe is made from (B/bad_slam_config.h; B/bad_slam.cc:657-689).  The BA's cameras are the video's cameras
+  // Scaled(1 / 2^level); levels are 0 .. 3 (the blocks of the depth downscale stay within what a binary32 sum holds exactly).
+  int pyramid_level_for_depth = 0;
+  int pyramid_level_for_color = 0;
+  int median_filter_and_densify_iterations = 0;
 };
-// Uploads the frame's depth and colour, computes luma, filtered depth, normals, radii (isolated pixels removed) and the
-// depth range, and builds the keyframe with the frame's current pose.
+// Levels outside 0 .. 3, a negative iteration count, or -- as in the reference (B/bad_slam.cc:671-673) -- a depth level > 0 together
+// with median iterations > 0: false, with the reason in *message.
+bool ValidatePreprocessConfig(const PreprocessConfig& config, std::string* message);
+// Uploads the frame's depth and colour; on the device: the median filter and densification iterations (ping-pong), at a depth level > 0
+// the median downscale to the depth camera's size, at a colour level > 0 the repeated halving to the colour camera's size
+// (bahip_median_filter_and_densify, bahip_downscale_depth_median, bahip_downscale_rgb_half); then luma, filtered depth, normals, radii
+// (isolated pixels removed) and the depth range; builds the keyframe with the frame's current pose.  The images scaled by 2^-level
+// (PinholeCamera4f::Scaled's rounding) must have the BA cameras' sizes (checked).  A config that ValidatePreprocessConfig refuses gives
+// a null pointer and an error message, nothing else.
 shared_ptr<Keyframe> CreateKeyframeFromFrame(hipStream_t stream, const PreprocessConfig& config, DirectBA& direct_ba,
                                              RGBDVideo<Vec3u8, u16>& rgbd_video, int frame_index);
 
@@ -129,7 +141,10 @@ shared_ptr<Keyframe> CreateKeyframeFromFrame(hipStream_t stream, const Preproces
 // thresholds, merge factor).  The front-end sections (motion model, queued keyframes, BadSlamConfig) have no counterpart
 // here and are not written, so the container announces itself as "BADSLAM" with version 101: a reference build refuses it
 // ("Unknown file format version") instead of misreading it.  Keyframe images are not stored (as in the reference): on
-// loading, every keyframe is rebuilt from its video frame by CreateKeyframeFromFrame, with the loaded pose.
+// loading, every keyframe is rebuilt from its video frame by CreateKeyframeFromFrame, with the loaded pose -- and with the config of
+// THIS run: a resumed run needs the pyramid levels and the median iterations of the run that saved.  Other levels are caught by the
+// sizes (the stored cameras must have the live cameras' sizes, and the frames scaled by the levels the BA cameras'); the state file
+// does not record the median iterations or the bilateral parameters, so nothing catches a mismatch there.
 bool SaveState(hipStream_t stream, const RGBDVideo<Vec3u8, u16>& rgbd_video, DirectBA& direct_ba, const std::string& path);
 // progress_function(keyframes_done, keyframe_count) may return false to abort (B/io.cc:396-403).
 bool LoadState(hipStream_t stream, const PreprocessConfig& config, RGBDVideo<Vec3u8, u16>* rgbd_video, DirectBA* direct_ba,

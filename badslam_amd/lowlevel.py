@@ -113,9 +113,51 @@ def bilateral_filtering_and_depth_cutoff(ctx, depth_u16, sigma_xy, sigma_value, 
     return dst.download()
 
 
+def median_filter_and_densify(ctx, depth_u16, iterations=1):
+    """`iterations` rounds of BadSlam::PreprocessFrame's median filter and densification (bahip_median_filter_and_densify) on a host
+    image of raw depth (0 = no measurement): upload, ping-pong between two device images, download."""
+    d = np.ascontiguousarray(depth_u16, np.uint16)
+    src = DeviceBuffer2D(ctx, d.shape[0], d.shape[1], np.uint16).upload(d)
+    dst = DeviceBuffer2D(ctx, d.shape[0], d.shape[1], np.uint16)
+    for _ in range(int(iterations)):
+        capi.check(ctx.lib.bahip_median_filter_and_densify(ctx.handle, src.ptr, src.pitch, dst.ptr, dst.pitch, d.shape[1], d.shape[0]))
+        src, dst = dst, src
+    return src.download()
+
+
+def downscale_depth_median(ctx, depth_u16, out_width, out_height):
+    """Image<u16>::DownscaleUsingMedianWhileExcluding(0, ...) on a host image (bahip_downscale_depth_median)."""
+    d = np.ascontiguousarray(depth_u16, np.uint16)
+    src = DeviceBuffer2D(ctx, d.shape[0], d.shape[1], np.uint16).upload(d)
+    dst = DeviceBuffer2D(ctx, max(1, int(out_height)), max(1, int(out_width)), np.uint16)
+    capi.check(ctx.lib.bahip_downscale_depth_median(ctx.handle, src.ptr, src.pitch, d.shape[1], d.shape[0], dst.ptr, dst.pitch,
+                                                    int(out_width), int(out_height)))
+    return dst.download()
+
+
+def downscale_rgb_half(ctx, rgb_u8, levels):
+    """Image<Vec3u8>::DownscaleToHalfSize applied `levels` times to a host (H, W, 3) image (bahip_downscale_rgb_half)."""
+    c = np.ascontiguousarray(rgb_u8, np.uint8)
+    h, w = c.shape[:2]
+    src = DeviceBuffer2D(ctx, h, w, np.uint8, 3).upload(c)
+    dst = DeviceBuffer2D(ctx, max(1, h >> max(0, int(levels))), max(1, w >> max(0, int(levels))), np.uint8, 3)
+    capi.check(ctx.lib.bahip_downscale_rgb_half(ctx.handle, src.ptr, src.pitch, w, h, int(levels), dst.ptr, dst.pitch))
+    return dst.download()
+
+
 def make_camera(params, width, height):
     p = np.asarray(params, dtype=np.float32)
     return capi.Camera(float(p[0]), float(p[1]), float(p[2]), float(p[3]), int(width), int(height))
+
+
+def scaled_camera(cam, level):
+    """PinholeCamera4f::Scaled(1 / 2^level): the four parameters (pixel-corner convention) times the factor in binary32, width and
+    height int(factor * size + 0.5) -- the camera the BA runs with at a pyramid level."""
+    if not 0 <= int(level) <= 3:
+        raise ValueError("pyramid levels are 0 .. 3")
+    factor = np.float32(1.0) / np.float32(1 << int(level))
+    p = [float(np.float32(v) * factor) for v in (cam.fx, cam.fy, cam.cx, cam.cy)]
+    return capi.Camera(p[0], p[1], p[2], p[3], int(float(factor) * cam.width + 0.5), int(float(factor) * cam.height + 0.5))
 
 
 class Scene:
@@ -147,15 +189,22 @@ class Scene:
 
     # Keyframe ctor #2 (B/keyframe.cc:81-158)
     def add_keyframe(self, depth_u16, rgb_u8, global_T_frame):
+        ctx = self.ctx
+        W, H = self.depth_cam.width, self.depth_cam.height
+        cw, ch = self.color_cam.width, self.color_cam.height
+        rgb = DeviceBuffer2D(ctx, ch, cw, np.uint8, 3).upload(rgb_u8)
+        raw = DeviceBuffer2D(ctx, H, W, np.uint16).upload(depth_u16)
+        return self._add_keyframe_from_device(raw, rgb, global_T_frame)
+
+    def _add_keyframe_from_device(self, raw, rgb, global_T_frame):
+        """The keyframe from device images of the cameras' sizes (both are freed)."""
         ctx, lib, h = self.ctx, self.lib, self.ctx.handle
         W, H = self.depth_cam.width, self.depth_cam.height
         cw, ch = self.color_cam.width, self.color_cam.height
         kf = dict(depth=DeviceBuffer2D(ctx, H, W, np.uint16), normals=DeviceBuffer2D(ctx, H, W, np.uint16),
                   radius=DeviceBuffer2D(ctx, H, W, np.uint16).clear(0), color=DeviceBuffer2D(ctx, ch, cw, np.uint8, 4),
                   pose=np.asarray(global_T_frame, dtype=np.float32).copy(), activation=capi.KF_ACTIVE)
-        rgb = DeviceBuffer2D(ctx, ch, cw, np.uint8, 3).upload(rgb_u8)
         capi.check(lib.bahip_compute_brightness(h, rgb.ptr, rgb.pitch, kf["color"].ptr, kf["color"].pitch, cw, ch))
-        raw = DeviceBuffer2D(ctx, H, W, np.uint16).upload(depth_u16)
         tmp = DeviceBuffer2D(ctx, H, W, np.uint16)
         capi.check(lib.bahip_compute_normals(h, C.byref(self.depth_cam), C.byref(self.dp), raw.ptr, raw.pitch, tmp.ptr, tmp.pitch,
                                              kf["normals"].ptr, kf["normals"].pitch))
@@ -170,6 +219,60 @@ class Scene:
             b.free()
         self.keyframes.append(kf)
         return len(self.keyframes) - 1
+
+    def add_frame(self, depth_full, rgb_full, global_T_frame, pyramid_level_for_depth=0, pyramid_level_for_color=0, median_iterations=0,
+                  bilateral=None):
+        """BadSlam::PreprocessFrame (B/bad_slam.cc:657-706) + the keyframe constructor on a full-resolution frame: raw depth (0 = no
+        measurement) through `median_iterations` rounds of the median filter and densification or, at a depth level > 0, the median
+        downscale to the depth camera's size; colour halved `pyramid_level_for_color` times to the colour camera's size; then, with
+        bilateral = (sigma_xy, sigma_inv_depth, radius_factor, max_depth_raw), the bilateral filter and depth cut-off; then what
+        add_keyframe does.  All on the device.  The scene's cameras are the scaled ones (scaled_camera)."""
+        ctx, lib, h = self.ctx, self.lib, self.ctx.handle
+        ld, lc, iterations = int(pyramid_level_for_depth), int(pyramid_level_for_color), int(median_iterations)
+        if not (0 <= ld <= 3 and 0 <= lc <= 3):
+            raise ValueError("pyramid levels are 0 .. 3")
+        if ld > 0 and iterations > 0:
+            raise ValueError("Simultaneous downscaling and median filtering of depth maps is not implemented.")
+        d = np.ascontiguousarray(depth_full, np.uint16)
+        c = np.ascontiguousarray(rgb_full, np.uint8)
+        W, H = self.depth_cam.width, self.depth_cam.height
+        cw, ch = self.color_cam.width, self.color_cam.height
+        scale = lambda size, level: int(float(np.float32(1.0) / np.float32(1 << level)) * size + 0.5)
+        if (scale(d.shape[1], ld), scale(d.shape[0], ld)) != (W, H):
+            raise ValueError(f"a {d.shape[1]} x {d.shape[0]} depth image at level {ld} is not the depth camera's {W} x {H}")
+        if (scale(c.shape[1], lc), scale(c.shape[0], lc)) != (cw, ch):
+            raise ValueError(f"a {c.shape[1]} x {c.shape[0]} colour image at level {lc} is not the colour camera's {cw} x {ch}")
+        raw = DeviceBuffer2D(ctx, d.shape[0], d.shape[1], np.uint16).upload(d)
+        if iterations > 0:
+            other = DeviceBuffer2D(ctx, H, W, np.uint16)
+            for _ in range(iterations):
+                capi.check(lib.bahip_median_filter_and_densify(h, raw.ptr, raw.pitch, other.ptr, other.pitch, W, H))
+                raw, other = other, raw
+            ctx.synchronize()
+            other.free()
+        if ld > 0:
+            small = DeviceBuffer2D(ctx, H, W, np.uint16)
+            capi.check(lib.bahip_downscale_depth_median(h, raw.ptr, raw.pitch, d.shape[1], d.shape[0], small.ptr, small.pitch, W, H))
+            ctx.synchronize()
+            raw.free()
+            raw = small
+        rgb = DeviceBuffer2D(ctx, c.shape[0], c.shape[1], np.uint8, 3).upload(c)
+        if lc > 0:
+            small = DeviceBuffer2D(ctx, ch, cw, np.uint8, 3)
+            capi.check(lib.bahip_downscale_rgb_half(h, rgb.ptr, rgb.pitch, c.shape[1], c.shape[0], lc, small.ptr, small.pitch))
+            ctx.synchronize()
+            rgb.free()
+            rgb = small
+        if bilateral is not None:
+            sigma_xy, sigma_value, radius_factor, max_depth = bilateral
+            filtered = DeviceBuffer2D(ctx, H, W, np.uint16)
+            capi.check(lib.bahip_bilateral_filtering_and_depth_cutoff(h, sigma_xy, sigma_value, radius_factor, int(max_depth),
+                                                                      self.dp.raw_to_float_depth, raw.ptr, raw.pitch, filtered.ptr,
+                                                                      filtered.pitch, W, H))
+            ctx.synchronize()
+            raw.free()
+            raw = filtered
+        return self._add_keyframe_from_device(raw, rgb, global_T_frame)
 
     def frame_struct(self, i):
         kf = self.keyframes[i]

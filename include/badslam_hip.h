@@ -275,6 +275,27 @@ int bahip_bilateral_filtering_and_depth_cutoff(bahip_context* ctx, float sigma_x
                                                uint16_t max_depth, float raw_to_float_depth, const uint16_t* in_depth,
                                                uint32_t in_pitch_bytes, uint16_t* out_depth, uint32_t out_pitch_bytes, int width,
                                                int height);
+/* What PreprocessFrame does ahead of that filter when the BA runs at a pyramid level (B/bad_slam.cc:657-689; the reference runs these
+ * on the CPU).  Integer rules, the reference's results bit for bit, the same under either arithmetic flavour.  All three: ordered on
+ * the context's stream, not in place, pitches in bytes; a refused call returns non-zero (bahip_last_error) and writes nothing.
+ * The median rule: of n non-zero values sorted ascending, s[n/2] for odd n; for even n, with low = s[n/2 - 1], high = s[n/2] and
+ * average = float(sum) / float(n) in binary32, low if |average - low| < |average - high| and high otherwise (a tie gives high).
+ *
+ * One iteration of MedianFilterAndDensifyDepthMap (B/preprocessing.cc:40-85): the rule on the non-zero values of the 3 x 3 window
+ * clipped to the image; with fewer than 2 of them the pixel is copied.  A zero pixel with two valid neighbours is filled. */
+int bahip_median_filter_and_densify(bahip_context* ctx, const uint16_t* in_depth, uint32_t in_pitch_bytes, uint16_t* out_depth,
+                                    uint32_t out_pitch_bytes, int width, int height);
+/* Image<u16>::DownscaleUsingMedianWhileExcluding(0, ...) (L/image.h:1003-1053): output pixel (x, y) is the rule on the non-zero values of
+ * input columns [(W x) / ow, (W (x + 1)) / ow) and rows [(H y) / oh, (H (y + 1)) / oh) (unsigned division), 0 if there are none.
+ * Refused unless 1 <= ow <= W, 1 <= oh <= H, W, H <= 65535 and ceil(W / ow), ceil(H / oh) <= 9: at most 81 values, whose binary32
+ * sum is exact (81 * 65535 < 2^24) and so does not depend on the order of summation. */
+int bahip_downscale_depth_median(bahip_context* ctx, const uint16_t* in_depth, uint32_t in_pitch_bytes, int in_width, int in_height,
+                                 uint16_t* out_depth, uint32_t out_pitch_bytes, int out_width, int out_height);
+/* Image<Vec3u8>::DownscaleToHalfSize (L/image.h:929-948) applied `levels` times (1 .. 3), as ImagePyramid does: per channel
+ * a / 4 + b / 4 + c / 4 + d / 4, every quotient truncated (four 3s give 0, four 255s give 252).  The output is (width >> levels) x
+ * (height >> levels); refused unless width and height are divisible by 2^levels. */
+int bahip_downscale_rgb_half(bahip_context* ctx, const uint8_t* rgb_in, uint32_t in_pitch_bytes, int width, int height, int levels,
+                             uint8_t* rgb_out, uint32_t out_pitch_bytes);
 
 /* ---- keyframe preprocessing (Keyframe ctor #2, B/keyframe.cc:96-144) ------------------------- */
 /* B/cuda_image_processing.cu:165-193 ComputeBrightnessCUDA: uchar3 RGB -> uchar4 (R,G,B,luma). */
