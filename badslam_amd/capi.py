@@ -100,6 +100,21 @@ class RenderOut(C.Structure):      # bahip_render_out: device planes of a render
     _fields_ = [("key", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p), ("normal", C.c_void_p), ("color", C.c_void_p)]
 
 
+RESIDUAL_BEST, RESIDUAL_WORST = 0, 1
+
+
+class ResidualImageOptions(C.Structure):  # bahip_residual_image_options: which pair of a pixel wins (smallest / largest |raw|), and the index offset
+    _fields_ = [("select", C.c_int32), ("index_base", C.c_uint32)]
+
+    def __init__(self, select=RESIDUAL_BEST, index_base=0):
+        super().__init__(int(select), int(index_base))
+
+
+class ResidualImageOut(C.Structure):      # bahip_residual_image_out: device planes of a residual image (bahip_frame_residual_image)
+    _fields_ = [("key", C.c_void_p), ("pairs", C.c_void_p), ("index", C.c_void_p), ("depth_residual", C.c_void_p),
+                ("inv_stddev", C.c_void_p), ("desc_residual", C.c_void_p), ("color_valid", C.c_void_p)]
+
+
 class PoseStepControl(C.Structure):   # bahip_pose_step_control: step control of the pose phase (bahip_estimate_keyframe_poses_controlled)
     _fields_ = [("lambda_up", C.c_float), ("lambda_down", C.c_float), ("lambda_min", C.c_float), ("lambda_max", C.c_float),
                 ("max_trials", C.c_int)]
@@ -271,6 +286,10 @@ SIGNATURES = {
     "bahip_debug_set_render_stages": (C.c_int, [C.c_int]),
     "bahip_debug_render_census": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.POINTER(Camera), C.POINTER(C.c_float), C.POINTER(RenderOptions),
                                             C.POINTER(C.c_ulonglong)]),
+    "bahip_frame_residual_image": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
+                                             C.POINTER(ResidualImageOptions), C.POINTER(ResidualImageOut)]),
+    "bahip_debug_set_residual_image_shape": (C.c_int, [C.c_int, C.c_int]),
+    "bahip_debug_set_residual_image_stages": (C.c_int, [C.c_int]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

@@ -588,6 +588,34 @@ void launch_render_splat(hipStream_t stream, const Intrinsics& view, const Rende
 void launch_render_resolve(hipStream_t stream, const RenderParams& rp, const SurfelsView& s, const unsigned long long* keys, uint32_t pixels,
                            const RenderPlanes& out);
 
+// kernels_residual_image.hip: a frame's depth and descriptor residuals per pixel (exists once: the exact flavour's association under
+// either flavour).  What the kernels need of the frame; the planes (device, dense row-major width x height of the depth camera, any of
+// the resolve's may be NULL); the sweep's launch shape.
+constexpr int kResidualImageMaxWaves = 8;
+constexpr int kResidualImageDefaultWaves = 4, kResidualImageWorkgroupsPerUnit = 16;
+struct ResidualFrame {
+  float F[12];               // frame_T_global
+  const uint32_t* geom;      // the frame's tiled BA planes (KfEntry::geom, ::lumafp)
+  const uint32_t* lumafp;
+};
+struct ResidualImagePlanes {
+  uint32_t* index;
+  float* depth_residual;
+  float* inv_stddev;
+  float* desc_residual;      // two floats per pixel
+  uint8_t* color_valid;
+};
+struct ResidualImageShape {
+  int waves, workgroups;
+};
+void launch_residual_image_clear(hipStream_t stream, unsigned long long* keys, uint32_t* counts, uint32_t pixels);
+// one lane per surfel: on associated lanes an atomic minimum into `keys` and an atomic add into `counts`; select 0 = best, 1 = worst
+void launch_residual_image_sweep(hipStream_t stream, const Intrinsics& in, const ResidualFrame& frame, const SurfelsView& s, int select,
+                                 uint32_t index_base, const ResidualImageShape& shape, unsigned long long* keys, uint32_t* counts);
+// the planes from the winning keys; descriptors are evaluated only when desc_residual or color_valid is asked for
+void launch_residual_image_resolve(hipStream_t stream, const Intrinsics& in, const ResidualFrame& frame, const SurfelsView& s, uint32_t index_base,
+                                   const unsigned long long* keys, uint32_t pixels, const ResidualImagePlanes& out);
+
 // kernels_ingest.hip: a frame brought to the BA's pyramid level (exists once: integer rules and one correctly rounded division, the same
 // under either flavour).  The callers have checked sizes and pitches; the downscale's blocks are at most kIngestMaxBlock on a side.
 constexpr int kIngestMaxBlock = 9, kIngestMaxLevels = 3;

@@ -9,6 +9,7 @@
 //   capi_cost.hip       the value of the BA objective (bahip_evaluate_cost, bahip_evaluate_frame_cost)
 //   capi_surfel_cost.hip the value of the BA objective per surfel (bahip_evaluate_surfel_costs)
 //   capi_render.hip     the surfel map rendered into a camera view (bahip_render_surfels)
+//   capi_residual_image.hip a frame's residuals per pixel (bahip_frame_residual_image)
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
 //   capi_geometry_trial.hip step control of the geometry phase of the alternating scheme
@@ -216,6 +217,9 @@ struct bahip_context {
   DeviceBuffer<long long> dev_surfel_cost_rows;   // keyframe sharding: staged words of one slice of the per-surfel cost sweep (kernels_surfel_cost.hip)
   DeviceBuffer<unsigned long long> render_keys;   // bahip_render_surfels: the dense width x height key plane the splat takes its minima in (kernels_render.hip)
   DeviceBuffer<unsigned long long> render_counters;   // bahip_debug_render_census: two counters
+  // bahip_frame_residual_image: the dense key and pair-count planes of the sweep, when the caller passes NULL for them (kernels_residual_image.hip)
+  DeviceBuffer<unsigned long long> residual_keys;
+  DeviceBuffer<uint32_t> residual_counts;
   // dealing the lifecycle under surfel sharding (bahip_context_set_lifecycle_dealing): the switch, and the surfel partition of the
   // whole-cloud phase in progress -- set by bahip_gather_surfel_shards, cleared by bahip_extract_surfel_shard (deal_world 1: none) --
   // with the gathered cloud it belongs to: lifecycle calls on any other buffer are not dealt

@@ -48,6 +48,10 @@ def _load():
         L.dba_compute_surfel_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
         L.dba_render_surfels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float),
                                          C.POINTER(capi.RenderOptions)] + [C.c_void_p] * 4 + [C.POINTER(C.c_float)]
+        # (an older build under A/B timing, scripts/ab_bench.sh, may lack this newer entry point: as capi.load)
+        if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_keyframe_residual_image"):
+            L.dba_keyframe_residual_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float),
+                                                      C.POINTER(capi.ResidualImageOptions)] + [C.c_void_p] * 7 + [C.POINTER(C.c_float)]
         L.dba_surfel_count.restype = C.c_uint32
         L.dba_surfel_count.argtypes = [C.c_void_p]
         L.dba_surfels_size.restype = C.c_uint32
@@ -280,6 +284,24 @@ class DirectBA:
         opt = options if options is not None else capi.RenderOptions()
         assert self.L.dba_render_surfels(self.h, self.stream, keyframe, cam, width, height, pose, C.byref(opt),
                                          *[a.ctypes.data for a in out.values()], F) == 0
+        out["frame_T_global"] = np.array(list(F), np.float32)
+        return out
+
+    def keyframe_residual_image(self, keyframe, global_T_frame=None, select=capi.RESIDUAL_BEST, index_base=0):
+        """DirectBA::KeyframeResidualImage (keyframe: an id, at its own pose) or, with global_T_frame (7 floats), DirectBA::
+        FrameResidualImage on that keyframe's images at the pose given: per pixel of the depth image the associated surfel with the
+        smallest (capi.RESIDUAL_BEST) or largest (RESIDUAL_WORST) |depth residual| and its residuals.  Returns a dict of numpy arrays
+        of height x width pixels -- key (uint64), pairs, index (uint32), depth_residual, inv_stddev (float32), desc_residual (x 2,
+        float32), color_valid (uint8) -- and frame_T_global, the 12 floats the call used."""
+        h, w = self.height, self.width
+        out = dict(key=np.zeros((h, w), np.uint64), pairs=np.zeros((h, w), np.uint32), index=np.zeros((h, w), np.uint32),
+                   depth_residual=np.zeros((h, w), np.float32), inv_stddev=np.zeros((h, w), np.float32),
+                   desc_residual=np.zeros((h, w, 2), np.float32), color_valid=np.zeros((h, w), np.uint8))
+        pose = None if global_T_frame is None else (C.c_float * 7)(*[float(v) for v in global_T_frame])
+        F = (C.c_float * 12)()
+        opt = capi.ResidualImageOptions(select, index_base)
+        assert self.L.dba_keyframe_residual_image(self.h, self.stream, int(keyframe), pose, C.byref(opt),
+                                                  *[a.ctypes.data for a in out.values()], F) == 0
         out["frame_T_global"] = np.array(list(F), np.float32)
         return out
 

@@ -14,6 +14,7 @@
 //          [--bilateral_sigma_xy S] [--bilateral_sigma_inv_depth S] [--bilateral_radius_factor R] [--report_cost]
 //          [--pcg_step_control] [--pose_step_control] [--geometry_step_control] [--intrinsics_step_control]
 //          [--render_dir DIR [--render_mode point|disc] [--render_max_radius N] [--render_radius_factor F]]
+//          [--residual_dir DIR [--residual_select best|worst]]
 //          [--pyramid_level_for_depth N] [--pyramid_level_for_color N] [--median_filter_and_densify_iterations N]
 //
 // --pyramid_level_for_depth N / --pyramid_level_for_color N (0 .. 3): the BA runs on depth / colour images of 2^-N the dataset's size, with
@@ -26,6 +27,12 @@
 // keyframe's final pose; discs of at most 4 px unless the --render_* options say otherwise), two files per keyframe id in the existing
 // directory DIR: render_%06d_color.ppm (binary P6: the surfels' colours, black where no surfel is seen) and render_%06d_depth.pgm (binary
 // P5, 16 bit, big-endian, in the unit of the input depth images: min(65534, (int)(depth / raw_to_float_depth + 0.5f)), 0 = no surfel).
+// --residual_dir DIR: after the last BA call (and after the saved state, the output files and the rendered views) every keyframe's residual
+// image (DirectBA::KeyframeResidualImage: per pixel the associated surfel with the smallest |depth residual|, or the largest with
+// --residual_select worst), in the existing directory DIR: residual_%06d_depth.pgm (binary P5, 16 bit, big-endian: 0 = no pair, else
+// clamp(32768 + (int)floorf(raw * 1024 + 0.5f), 1, 65535), raw in standard deviations), residual_%06d_pairs.pgm (binary P5, 8 bit:
+// min(pairs, 255)) and residuals.txt, one line per keyframe: id, explained pixels, pairs, pixels with two or more pairs, mean and RMS of
+// the winners' raw (accumulated in binary64 in row-major order, printed with 17 digits).
 // --report_cost: prints the value of the BA objective (DirectBA::ComputeCost: total and the depth / descriptor sums and counts) before
 // the first and after the last BA call.
 // --pose_step_control: without --pcg, damped pose steps kept per keyframe only if its cost falls (DirectBA::SetPoseStepControl, its defaults)
@@ -45,6 +52,8 @@
 // trajectory file), plans max_num_ba_iterations_per_keyframe iterations, and these run either right away (sequential) or
 // on the BA thread while the next keyframe is being prepared.  --save_state writes the backend state after BA;
 // --load_state starts from such a file instead of creating keyframes and surfels (checkpoint / resume, rgbd_io.h).
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -100,22 +109,26 @@ static int DecodePng(const char* path, const char* kind, const char* out_path) {
   return 0;
 }
 
-// --render_dir: the two PNM files of one rendered keyframe view (rgbd_io has no PNG encoder)
+// One binary PNM file (rgbd_io has no PNG encoder): "P5" (grey) or "P6" (RGB) with the samples as given -- one byte each for max_value
+// 255, two bytes big-endian for 65535.
+static bool WritePNM(const std::string& path, const char* magic, int width, int height, int max_value, const vector<unsigned char>& samples) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  fprintf(f, "%s\n%d %d\n%d\n", magic, width, height, max_value);
+  const bool ok = fwrite(samples.data(), 1, samples.size(), f) == samples.size();
+  return (fclose(f) == 0) && ok;
+}
+
+// --render_dir: the two PNM files of one rendered keyframe view
 static bool WriteRenderedView(const std::string& dir, int id, const DirectBA::RenderedView& view, float raw_to_float_depth) {
   const size_t n = (size_t)view.width * view.height;
   char name[64];
   snprintf(name, sizeof(name), "/render_%06d_color.ppm", id);
-  FILE* f = fopen((dir + name).c_str(), "wb");
-  if (!f) return false;
   vector<unsigned char> rgb(3 * n);
   for (size_t p = 0; p < n; ++p)
     for (int c = 0; c < 3; ++c) rgb[3 * p + c] = view.color[4 * p + c];
-  fprintf(f, "P6\n%d %d\n255\n", view.width, view.height);
-  bool ok = fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
-  ok = (fclose(f) == 0) && ok;
+  if (!WritePNM(dir + name, "P6", view.width, view.height, 255, rgb)) return false;
   snprintf(name, sizeof(name), "/render_%06d_depth.pgm", id);
-  f = fopen((dir + name).c_str(), "wb");
-  if (!f) return false;
   vector<unsigned char> depth(2 * n);
   for (size_t p = 0; p < n; ++p) {
     unsigned value = 0;
@@ -126,9 +139,40 @@ static bool WriteRenderedView(const std::string& dir, int id, const DirectBA::Re
     depth[2 * p] = (unsigned char)(value >> 8);
     depth[2 * p + 1] = (unsigned char)(value & 0xff);
   }
-  fprintf(f, "P5\n%d %d\n65535\n", view.width, view.height);
-  ok = (fwrite(depth.data(), 1, depth.size(), f) == depth.size()) && ok;
-  return (fclose(f) == 0) && ok;
+  return WritePNM(dir + name, "P5", view.width, view.height, 65535, depth);
+}
+
+// --residual_dir: the two PGM files of one keyframe's residual image and its line of residuals.txt -- the keyframe id, the explained
+// pixels, the pairs, the pixels with two or more pairs, and the mean and RMS of the winners' raw (binary64, row-major order)
+static bool WriteResidualImage(const std::string& dir, int id, const DirectBA::ResidualImage& image, FILE* summary) {
+  const size_t n = (size_t)image.width * image.height;
+  vector<unsigned char> depth(2 * n), pairs(n);
+  unsigned long long explained = 0, total_pairs = 0, multi = 0;
+  double sum = 0, sum_sq = 0;
+  for (size_t p = 0; p < n; ++p) {
+    unsigned value = 0;
+    if (image.index[p] != 0xFFFFFFFFu) {
+      const float raw = image.depth_residual[p];
+      const float scaled = floorf(raw * 1024 + 0.5f);
+      // (a NaN or a value beyond the int range would not convert: clamped as floats first)
+      value = !(scaled > -32767.f) ? 1u : (scaled >= 32767.f ? 65535u : (unsigned)(32768 + (int)scaled));
+      ++explained;
+      sum += (double)raw;
+      sum_sq += (double)raw * (double)raw;
+    }
+    depth[2 * p] = (unsigned char)(value >> 8);
+    depth[2 * p + 1] = (unsigned char)(value & 0xff);
+    pairs[p] = (unsigned char)std::min<uint32_t>(image.pairs[p], 255u);
+    total_pairs += image.pairs[p];
+    multi += image.pairs[p] >= 2 ? 1 : 0;
+  }
+  char name[64];
+  snprintf(name, sizeof(name), "/residual_%06d_depth.pgm", id);
+  if (!WritePNM(dir + name, "P5", image.width, image.height, 65535, depth)) return false;
+  snprintf(name, sizeof(name), "/residual_%06d_pairs.pgm", id);
+  if (!WritePNM(dir + name, "P5", image.width, image.height, 255, pairs)) return false;
+  const double mean = explained ? sum / (double)explained : 0.0, rms = explained ? sqrt(sum_sq / (double)explained) : 0.0;
+  return fprintf(summary, "%d %llu %llu %llu %.17g %.17g\n", id, explained, total_pairs, multi, mean, rms) > 0;
 }
 
 int main(int argc, char** argv) {
@@ -147,8 +191,9 @@ int main(int argc, char** argv) {
   bool row_major_creation = false, report_cost = false, pcg_step_control = false, pose_step_control = false, geometry_step_control = false;
   bool intrinsics_step_control = false;
   bool use_pcg = false, intrinsics = false, incremental = false, parallel_ba = false;
-  std::string save_state, load_state, render_dir;
+  std::string save_state, load_state, render_dir, residual_dir;
   DirectBA::RenderOptions render_options;
+  DirectBA::ResidualImageOptions residual_options;
   PreprocessConfig config;
   for (int i = 4; i < argc; ++i) {
     const std::string a = argv[i];
@@ -179,6 +224,8 @@ int main(int argc, char** argv) {
     else if (a == "--render_mode" && i + 1 < argc && (!strcmp(argv[i + 1], "point") || !strcmp(argv[i + 1], "disc"))) render_options.disc = !strcmp(argv[++i], "disc");
     else if (a == "--render_max_radius" && i + 1 < argc) render_options.max_radius_px = atoi(argv[++i]);
     else if (a == "--render_radius_factor" && i + 1 < argc) render_options.radius_factor = (float)atof(argv[++i]);
+    else if (a == "--residual_dir" && i + 1 < argc) residual_dir = argv[++i];
+    else if (a == "--residual_select" && i + 1 < argc && (!strcmp(argv[i + 1], "best") || !strcmp(argv[i + 1], "worst"))) residual_options.worst = !strcmp(argv[++i], "worst");
     else if (a == "--pyramid_level_for_depth" && i + 1 < argc) config.pyramid_level_for_depth = atoi(argv[++i]);
     else if (a == "--pyramid_level_for_color" && i + 1 < argc) config.pyramid_level_for_color = atoi(argv[++i]);
     else if (a == "--median_filter_and_densify_iterations" && i + 1 < argc) config.median_filter_and_densify_iterations = atoi(argv[++i]);
@@ -333,6 +380,22 @@ int main(int argc, char** argv) {
       }
       printf("wrote %d rendered view(s) (%s, at most %d px) to %s\n", views, render_options.disc ? "discs" : "points", render_options.max_radius_px,
              render_dir.c_str());
+    }
+    if (!residual_dir.empty()) {
+      FILE* summary = fopen((residual_dir + "/residuals.txt").c_str(), "w");
+      if (!summary) { fprintf(stderr, "cannot write the residual images to %s\n", residual_dir.c_str()); return 1; }
+      int images = 0;
+      bool ok = true;
+      for (const shared_ptr<Keyframe>& kf : ba.keyframes()) {
+        if (!kf || !ok) continue;
+        DirectBA::ResidualImage image;
+        ba.KeyframeResidualImage(stream, (int)kf->id(), residual_options, &image);
+        ok = WriteResidualImage(residual_dir, (int)kf->id(), image, summary);
+        ++images;
+      }
+      ok = (fclose(summary) == 0) && ok;
+      if (!ok) { fprintf(stderr, "cannot write the residual images to %s\n", residual_dir.c_str()); return 1; }
+      printf("wrote %d residual image(s) (%s pair per pixel) to %s\n", images, residual_options.worst ? "worst" : "best", residual_dir.c_str());
     }
   }
   bahip_stream_destroy(stream);

@@ -203,6 +203,35 @@ int dba_render_surfels(dba_handle* h, void* stream, int keyframe_id, const float
   return 0;
 }
 
+int dba_keyframe_residual_image(dba_handle* h, void* stream, int keyframe_id, const float global_T_frame[7],
+                                const bahip_residual_image_options* options, uint64_t* key, uint32_t* pairs, uint32_t* index,
+                                float* depth_residual, float* inv_stddev, float* desc_residual, uint8_t* color_valid,
+                                float frame_T_global_out[12]) {
+  if (!options || (options->select != BAHIP_RESIDUAL_BEST && options->select != BAHIP_RESIDUAL_WORST)) return 1;
+  Keyframe* kf = get_kf(h, keyframe_id);
+  if (!kf) return 1;
+  DirectBA::ResidualImageOptions o;
+  o.worst = options->select == BAHIP_RESIDUAL_WORST;
+  o.index_base = options->index_base;
+  DirectBA::ResidualImage image;
+  SE3f pose = kf->global_T_frame();
+  if (global_T_frame) {
+    pose = SE3f(global_T_frame);
+    h->ba->FrameResidualImage(static_cast<hipStream_t>(stream), *kf, pose, o, &image);
+  } else {
+    h->ba->KeyframeResidualImage(static_cast<hipStream_t>(stream), keyframe_id, o, &image);
+  }
+  if (key) std::copy(image.key.begin(), image.key.end(), key);
+  if (pairs) std::copy(image.pairs.begin(), image.pairs.end(), pairs);
+  if (index) std::copy(image.index.begin(), image.index.end(), index);
+  if (depth_residual) std::copy(image.depth_residual.begin(), image.depth_residual.end(), depth_residual);
+  if (inv_stddev) std::copy(image.inv_stddev.begin(), image.inv_stddev.end(), inv_stddev);
+  if (desc_residual) std::copy(image.desc_residual.begin(), image.desc_residual.end(), desc_residual);
+  if (color_valid) std::copy(image.color_valid.begin(), image.color_valid.end(), color_valid);
+  if (frame_T_global_out) pose.inverse().matrix3x4(frame_T_global_out);
+  return 0;
+}
+
 uint32_t dba_surfel_count(dba_handle* h) { return h->ba->surfel_count(); }
 uint32_t dba_surfels_size(dba_handle* h) { return h->ba->surfels_size(); }
 int dba_set_surfel_count(dba_handle* h, uint32_t surfel_count, uint32_t surfels_size) {

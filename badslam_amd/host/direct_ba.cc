@@ -610,6 +610,52 @@ void DirectBA::RenderKeyframeView(hipStream_t stream, int keyframe_index, const 
   RenderSurfels(stream, depth_camera_, keyframes_[keyframe_index]->global_T_frame(), options, out);
 }
 
+void DirectBA::FrameResidualImage(hipStream_t stream, const Keyframe& frame, const SE3f& global_T_frame, const ResidualImageOptions& options,
+                                  ResidualImage* out) {
+  BAHIP_CHECKED_CALL(bahip_context_set_stream(ctx_, stream));
+  const bahip_camera cc = ToBahipCamera(color_camera_), dc = ToBahipCamera(depth_camera_);
+  const bahip_depth_params dp = ToBahipDepthParams(depth_params_);
+  BAHIP_CHECKED_CALL(bahip_set_intrinsics(ctx_, &cc, &dc, &dp));
+  const bahip_surfels s = SurfelsStruct(/*with_active*/ false);
+  const bahip_frame f = frame.ToBahipFrame();
+  const size_t n = (size_t)dc.width * (size_t)dc.height;
+  float F[12];
+  global_T_frame.inverse().matrix3x4(F);
+  bahip_residual_image_options o{};
+  o.select = options.worst ? BAHIP_RESIDUAL_WORST : BAHIP_RESIDUAL_BEST;
+  o.index_base = options.index_base;
+  // one device block for the seven planes: two words of key, then pairs, index, the two depth planes, two words of descriptor
+  // residuals and (a byte each, in the last quarter of a word's worth) color_valid per pixel
+  CUDABuffer<uint32_t> planes(1, (int)(8 * n + (n + 3) / 4));
+  uint32_t* base = planes.ToCUDA().address();
+  bahip_residual_image_out dev{};
+  dev.key = reinterpret_cast<uint64_t*>(base);
+  dev.pairs = base + 2 * n;
+  dev.index = base + 3 * n;
+  dev.depth_residual = reinterpret_cast<float*>(base + 4 * n);
+  dev.inv_stddev = reinterpret_cast<float*>(base + 5 * n);
+  dev.desc_residual = reinterpret_cast<float*>(base + 6 * n);
+  dev.color_valid = reinterpret_cast<uint8_t*>(base + 8 * n);
+  BAHIP_CHECKED_CALL(bahip_frame_residual_image(ctx_, &f, F, &s, &o, &dev));
+  out->width = dc.width; out->height = dc.height;
+  out->key.resize(n); out->pairs.resize(n); out->index.resize(n); out->depth_residual.resize(n); out->inv_stddev.resize(n);
+  out->desc_residual.resize(2 * n); out->color_valid.resize(n);
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->key.data(), dev.key, sizeof(uint64_t) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->pairs.data(), dev.pairs, sizeof(uint32_t) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->index.data(), dev.index, sizeof(uint32_t) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->depth_residual.data(), dev.depth_residual, sizeof(float) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->inv_stddev.data(), dev.inv_stddev, sizeof(float) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->desc_residual.data(), dev.desc_residual, sizeof(float) * 2 * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->color_valid.data(), dev.color_valid, n, 2));
+  BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
+}
+
+void DirectBA::KeyframeResidualImage(hipStream_t stream, int keyframe_index, const ResidualImageOptions& options, ResidualImage* out) {
+  CHECK_GE(keyframe_index, 0); CHECK_LT(keyframe_index, (int)keyframes_.size());
+  CHECK(keyframes_[keyframe_index] != nullptr);
+  FrameResidualImage(stream, *keyframes_[keyframe_index], keyframes_[keyframe_index]->global_T_frame(), options, out);
+}
+
 void DirectBA::BundleAdjustment(hipStream_t stream, bool optimize_depth_intrinsics, bool optimize_color_intrinsics,
                                 bool do_surfel_updates, bool optimize_poses, bool optimize_geometry, int min_iterations,
                                 int max_iterations, bool use_pcg, int active_keyframe_window_start,

@@ -87,6 +87,30 @@ class DirectBA {
   void RenderSurfels(hipStream_t stream, const PinholeCamera4f& view, const SE3f& global_T_frame, const RenderOptions& options, RenderedView* out);
   // ... from keyframe `keyframe_index` (an id; it must exist): the depth camera at that keyframe's pose
   void RenderKeyframeView(hipStream_t stream, int keyframe_index, const RenderOptions& options, RenderedView* out);
+  // The objective in image space (bahip_frame_residual_image; DESIGN.md section 3, "Residual images"): per pixel of a frame's depth
+  // image, row-major, the surfel the BA's association rule pairs with it -- the one with the smallest (worst = false) or largest |depth
+  // residual| among the pixel's pairs -- and that pair's residuals, with this object's cameras, depth parameters and cfactor image.
+  // Empty pixels hold key all ones, pairs 0, index 0xFFFFFFFF, residuals +0.0, color_valid 0.  Binds nothing; under surfel sharding the
+  // image of this rank's shard, as RenderSurfels.  Waits for the stream.
+  struct ResidualImageOptions {
+    bool worst = false;
+    uint32_t index_base = 0;
+  };
+  struct ResidualImage {
+    int width = 0, height = 0;
+    vector<uint64_t> key;            // width * height: (magnitude word << 32) | index
+    vector<uint32_t> pairs, index;   // width * height
+    vector<float> depth_residual;    // width * height: signed, in standard deviations
+    vector<float> inv_stddev;        // width * height: depth_residual / inv_stddev is metres
+    vector<float> desc_residual;     // 2 * width * height
+    vector<uint8_t> color_valid;     // width * height
+  };
+  // keyframe `keyframe_index` (an id; it must exist) at its own pose
+  void KeyframeResidualImage(hipStream_t stream, int keyframe_index, const ResidualImageOptions& options, ResidualImage* out);
+  // any frame with this object's image sizes at any pose; it need not be part of the map (a held-out frame made with
+  // CreateKeyframeFromFrame, say)
+  void FrameResidualImage(hipStream_t stream, const Keyframe& frame, const SE3f& global_T_frame, const ResidualImageOptions& options,
+                          ResidualImage* out);
   void UpdateKeyframeCoVisibility(const shared_ptr<Keyframe>& keyframe);
   // B/direct_ba.h:167, B/direct_ba.cc:456-459: surfel colours := mean of their observations in all keyframes (before an export).
   void AssignColors(hipStream_t stream);

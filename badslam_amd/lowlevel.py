@@ -35,6 +35,60 @@ def split_render_key(key):
     return depth, index
 
 
+def split_residual_key(key, select=capi.RESIDUAL_BEST):
+    """A key plane of bahip_frame_residual_image (uint64: magnitude word << 32 | index, all ones where empty) as (|raw| float32, index
+    uint32): the magnitude word is bits(|raw|) under RESIDUAL_BEST and 0x7fffffff - bits(|raw|) under RESIDUAL_WORST; empty pixels
+    give +0.0 and 0xFFFFFFFF, as the call's own planes have them.  The sign of raw is in the depth_residual plane only.  The
+    elementwise minimum of the key planes of several shards (each with its own index_base) is the key plane of their union."""
+    key = np.ascontiguousarray(key, np.uint64)
+    empty = key == np.uint64(0xFFFFFFFFFFFFFFFF)
+    high = (key >> np.uint64(32)).astype(np.uint32)
+    if int(select) == capi.RESIDUAL_WORST:
+        high = np.uint32(0x7FFFFFFF) - np.where(empty, np.uint32(0x7FFFFFFF), high)
+    magnitude = np.where(empty, np.uint32(0), high).astype(np.uint32).view(np.float32)
+    index = (key & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    return magnitude, index
+
+
+RESIDUAL_IMAGE_PLANES = (("key", np.uint64, 1), ("pairs", np.uint32, 1), ("index", np.uint32, 1), ("depth_residual", np.float32, 1),
+                         ("inv_stddev", np.float32, 1), ("desc_residual", np.float32, 2), ("color_valid", np.uint8, 1))
+
+
+def frame_residual_image(ctx, frame, frame_T_global, surfels, width, height, select=capi.RESIDUAL_BEST, index_base=0, planes=None,
+                         prefill=None):
+    """bahip_frame_residual_image for one frame (capi.Frame, or None) at frame_T_global (12 floats) over `surfels` (capi.Surfels): a
+    dict of numpy arrays of height x width pixels of the depth camera -- key (uint64), pairs, index (uint32), depth_residual,
+    inv_stddev (float32), desc_residual (x 2, float32), color_valid (uint8).  planes: the names to ask for (the others are passed as
+    NULL and left out of the dict); prefill: a byte value the device planes are filled with before the call (tests: an entry the call
+    did not write shows; after a refused call the planes come back as filled).  Raises capi.BackendError when the call is refused --
+    the dict of the untouched planes is then the exception's `planes` attribute when prefill was given."""
+    w, h = int(width), int(height)
+    n = max(1, w * h)
+    wanted = [name for name, _, _ in RESIDUAL_IMAGE_PLANES] if planes is None else list(planes)
+    bufs = {name: DeviceBuffer2D(ctx, 1, n, dtype, channels) for name, dtype, channels in RESIDUAL_IMAGE_PLANES if name in wanted}
+    shapes = {name: (h, w) if channels == 1 else (h, w, channels) for name, _, channels in RESIDUAL_IMAGE_PLANES}
+    download = lambda: {name: b.download()[0, :w * h].reshape(shapes[name]).copy() for name, b in bufs.items()}   # noqa: E731
+    try:
+        if prefill is not None:
+            for b in bufs.values():
+                b.clear(prefill)
+        F = (C.c_float * 12)(*[float(v) for v in frame_T_global])
+        opt = capi.ResidualImageOptions(select, index_base)
+        out = capi.ResidualImageOut(*[bufs[name].ptr if name in bufs else None for name, _, _ in RESIDUAL_IMAGE_PLANES])
+        try:
+            capi.check(ctx.lib.bahip_frame_residual_image(ctx.handle, C.byref(frame) if frame is not None else None, F, C.byref(surfels),
+                                                          C.byref(opt), C.byref(out)))
+        except capi.BackendError as e:
+            if prefill is not None:
+                ctx.synchronize()
+                e.planes = download()
+            raise
+        return download()
+    finally:
+        for b in bufs.values():
+            b.free()
+
+
 class DeviceBuffer2D:
     """libvis CUDABuffer<T> semantics: (height, width) pitched device allocation."""
 
@@ -785,6 +839,13 @@ class Scene:
         finally:
             for b in bufs.values():
                 b.free()
+
+    def residual_image(self, k, frame_T_global, select=capi.RESIDUAL_BEST, index_base=0, planes=None, prefill=None, size=None):
+        """Keyframe k's images against the surfel buffer at frame_T_global (12 floats), per pixel of the depth image the associated
+        surfel with the smallest (select = capi.RESIDUAL_BEST) or largest (RESIDUAL_WORST) |depth residual| and its residuals:
+        frame_residual_image on this scene's context, cameras and surfels (size: the first `size` surfels only)."""
+        return frame_residual_image(self.ctx, self.frame_struct(k), frame_T_global, self.surfels_struct(size), self.depth_cam.width,
+                                    self.depth_cam.height, select=select, index_base=index_base, planes=planes, prefill=prefill)
 
     def exact_sum(self, values, mode=0):
         """Exactly rounded binary64 sum of binary32 values through the device's exact accumulators (test hook)."""

@@ -77,6 +77,16 @@ int dba_compute_surfel_costs(dba_handle* h, void* hip_stream, uint32_t capacity,
 int dba_render_surfels(dba_handle* h, void* hip_stream, int keyframe_id, const float view_camera[4], int width, int height,
                        const float global_T_frame[7], const bahip_render_options* options, float* depth, uint32_t* index, float* normal,
                        uint8_t* color, float frame_T_global_out[12]);
+/* DirectBA::KeyframeResidualImage / FrameResidualImage (ours): the objective in image space (bahip_frame_residual_image) for the images
+ * of keyframe `keyframe_id`, row-major host planes of the depth image's width * height pixels, any may be NULL: key, pairs, index,
+ * depth_residual, inv_stddev, desc_residual (2 floats per pixel), color_valid.  global_T_frame NULL: the keyframe's own pose
+ * (KeyframeResidualImage); else the pose given, 7 floats (FrameResidualImage on the keyframe's images).  options->select:
+ * BAHIP_RESIDUAL_BEST or BAHIP_RESIDUAL_WORST.  frame_T_global_out: NULL or the 3 x 4 matrix the call used.  Returns non-zero on a bad
+ * argument. */
+int dba_keyframe_residual_image(dba_handle* h, void* hip_stream, int keyframe_id, const float global_T_frame[7],
+                                const bahip_residual_image_options* options, uint64_t* key, uint32_t* pairs, uint32_t* index,
+                                float* depth_residual, float* inv_stddev, float* desc_residual, uint8_t* color_valid,
+                                float frame_T_global_out[12]);
 
 /* accessors */
 uint32_t dba_surfel_count(dba_handle* h);

@@ -698,6 +698,55 @@ int bahip_debug_set_render_stages(int stages);
 int bahip_debug_render_census(bahip_context* ctx, const bahip_surfels* surfels, const bahip_camera* view, const float frame_T_global[12],
                               const bahip_render_options* options, unsigned long long counts_out[3]);
 
+/* ---- residual images (kernels_residual_image.hip; DESIGN.md section 3, "Residual images") ------------------------------------------
+ * The objective in image space: for one frame at frame_T_global, per pixel of the depth image, which surfel the BA associates with it
+ * and with what residuals.  Not a rendered view: the association rule is the sweeps' own (depth gate, normal tests, the
+ * cfactor-calibrated depth), evaluated with the context's intrinsics, depth parameters and cfactor plane (bahip_set_intrinsics).  The
+ * frame is a bahip_frame with or without packed planes, handled as bahip_evaluate_frame_cost handles it.
+ * For every surfel i < surfels_size the pair (i, frame) is evaluated with the production association rule (the device functions of
+ * bahip_debug_evaluate_pairs and of the cost sweep, in their order); activation flags are ignored, a NaN position is never associated.
+ * An associated pair has its pixel (px, py) and raw = inv_std * dot(nl, u - local).  With m = bits(raw) & 0x7fffffff the pair's key is
+ * (m << 32) | (index_base + i) under BAHIP_RESIDUAL_BEST and ((0x7fffffff - m) << 32) | (index_base + i) under BAHIP_RESIDUAL_WORST.
+ * A pixel's value is the MINIMUM key over its pairs, all ones when it has none: the smallest |raw| under BEST, the largest under WORST
+ * (a NaN residual counts as largest), equal magnitudes to the lower index under both.  Nothing depends on the launch shape, the surfel
+ * order or the order in which atomics arrive.
+ * The kernels exist once, in the exact arithmetic flavour: a context set to BAHIP_ARITHMETIC_FAST launches the same code, so the image
+ * is the exact flavour's association and residuals.
+ * Output planes: device memory, dense row-major width x height of the depth camera, borrowed for the call, any may be NULL.
+ *   key            u64   as above                                                             all ones where empty
+ *   pairs          u32   associated pairs at the pixel (all of them, not only the winner)     0
+ *   index          u32   the winner's index_base + i                                          0xFFFFFFFF
+ *   depth_residual f32   the winner's raw, signed, in standard deviations                     +0.0
+ *   inv_stddev     f32   the winner's inv_std (raw / inv_std is metres)                       +0.0
+ *   color_valid    u8    1 when the winner's depth-to-colour transform is valid               0
+ *   desc_residual  2 f32 the winner's r1, r2 where color_valid, else +0.0                     +0.0
+ * The float planes hold, word for word, what bahip_debug_evaluate_pairs reports for (winner, frame) at [5], [7], [3], [14..15]; the
+ * pixel is what it reports at [1], [2].  Every entry of every non-NULL plane is written by every successful call.
+ * The call is refused when the frame, the options or the out struct is NULL, select is neither, index_base + surfels_size would reach
+ * 0xFFFFFFFF, or no intrinsics are set; a refused call writes nothing and launches nothing, and the context stays usable.
+ * Asynchronous on the context's stream.  Either sharding: nothing is exchanged; a surfel shard gives the planes of the shard it holds.
+ * Shards are composited by the caller: the elementwise minimum of key, the sum of pairs, and per pixel the other planes of the shard
+ * whose key won (the key's low word is the index). */
+#define BAHIP_RESIDUAL_BEST 0
+#define BAHIP_RESIDUAL_WORST 1
+typedef struct bahip_residual_image_options {
+  int32_t select;
+  uint32_t index_base;
+} bahip_residual_image_options;
+typedef struct bahip_residual_image_out {   /* device pointers, borrowed; width * height pixels each; any may be NULL */
+  uint64_t* key;
+  uint32_t *pairs, *index;
+  float *depth_residual, *inv_stddev, *desc_residual;
+  uint8_t* color_valid;
+} bahip_residual_image_out;
+int bahip_frame_residual_image(bahip_context* ctx, const bahip_frame* frame, const float frame_T_global[12], const bahip_surfels* surfels,
+                               const bahip_residual_image_options* options, const bahip_residual_image_out* out);
+/* Launch shape of the sweep (test hook; results never depend on it): wavefronts per workgroup 1 .. 8, workgroups >= 1; 0 = the default. */
+int bahip_debug_set_residual_image_shape(int waves, int workgroups);
+/* The kernels bahip_frame_residual_image launches (scripts/residual_image_eval.py takes their times by difference): 1 clear, 2 sweep,
+ * 4 resolve, or-ed; 0 = all.  With a stage missing the planes are not a residual image. */
+int bahip_debug_set_residual_image_stages(int stages);
+
 /* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
  * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
  * e = 1e-8 + prior(u) as before and t = lambda * M[u] (one binary32 product), the preconditioner divides by ((M[u] + 1e-8) + prior(u))
