@@ -124,123 +124,24 @@ pcg_init_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restri
     gr[0] = r_[gi]; gM[0] = M_[gi];
     if (L.geom_stride == 3) { gr[1] = r_[gi + 1]; gM[1] = M_[gi + 1]; gr[2] = r_[gi + 2]; gM[2] = M_[gi + 2]; }
   }
-  constexpr bool kIntr = kDepthIntr || kColorIntr;
-  // The exact atomics of a candidate keyframe are issued one candidate late, behind the next candidate's gathers
-  // (exact_sum.h: exact_atomic_add_part_untracked): the (tile, keyframe) totals wait in pending_a / pending_b -- lanes
-  // 4 j .. 4 j + 3 hold total j of a 16-value halving butterfly: pending_a = 6 pose entries of r, 6 of M, the first 4 global
-  // intrinsics entries of r; pending_b (intrinsics only) = the other 5 of r and the 9 of M -- and the per-cell cfactor terms
-  // of a lane in pending_cf*.
+  // the pending (tile, keyframe) totals: the state of PcgInitPairs (pcg_device.h), which holds the pair body
   float pending_a = 0.f, pending_b = 0.f;
-  bool pending_any = false, pending_pose = false;   // wave-uniform
-  uint32_t pending_base = 0;                          // wave-uniform
-  uint32_t pending_cf = 0xffffffffu;                  // per lane: head index of the cell
+  bool pending_any = false, pending_pose = false;
+  uint32_t pending_base = 0;
+  uint32_t pending_cf = 0xffffffffu;
   float pending_cf_r = 0.f, pending_cf_M = 0.f;
-  auto intr_enabled = [&](int q) { return q < 5 ? kDepthIntr : kColorIntr; };
-  auto flush_pending = [&]() {
-    if (pending_any) {
-      const int j = lane >> 2, part = lane & 3;   // two of the four lanes that hold total j add its two parts
-      if (part < 2) {
-        if (j < 12) {
-          if (pending_pose) exact_atomic_add_part_untracked(j < 6 ? &ex.head_a[pending_base + j] : &ex.head_b[pending_base + j - 6], pending_a, part, ex.invalid);
-        } else if (kIntr && intr_enabled(j - 12)) {
-          exact_atomic_add_part_untracked(hot_cell(ex, kHotA + (j - 12), replica), pending_a, part, ex.invalid);
-        }
-        if (kIntr) {
-          if (j < 5) { if (intr_enabled(4 + j)) exact_atomic_add_part_untracked(hot_cell(ex, kHotA + 4 + j, replica), pending_b, part, ex.invalid); }
-          else if (j < 14 && intr_enabled(j - 5)) exact_atomic_add_part_untracked(hot_cell(ex, kHotB + (j - 5), replica), pending_b, part, ex.invalid);
-        }
-      }
-      pending_any = false;
-    }
-    if (kDepthIntr) {
-      if (pending_cf != 0xffffffffu) {
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-          exact_atomic_add_part_untracked(&ex.head_a[pending_cf], pending_cf_r, part, ex.invalid);
-          exact_atomic_add_part_untracked(&ex.head_b[pending_cf], pending_cf_M, part, ex.invalid);
-        }
-      }
-      pending_cf = 0xffffffffu;
-    }
-  };
+  const PcgInitPairs<kDepthIntr, kColorIntr> pairs{   // by name: a swap of two members of one type must not compile
+      .L = L, .ex = ex, .in = in, .gp = gp, .gn = gn, .tp = tp, .d1 = d1, .d2 = d2, .in_range = in_range, .lane = lane, .replica = replica,
+      .gr = gr, .gM = gM, .pending_a = pending_a, .pending_b = pending_b, .pending_any = pending_any, .pending_pose = pending_pose,
+      .pending_base = pending_base, .pending_cf = pending_cf, .pending_cf_r = pending_cf_r, .pending_cf_M = pending_cf_M};
   const auto may_project = [&](int k) { return sphere_may_project_item(in, kfs[k].pose.F, wb); };
   const auto candidate = [&](int k) {
-        const KfEntry& kf = kfs[k];
-        ++visited;
-        PairGather pg;
-        bool visible = gather_and_associate(L, in, kf, gp, gn, tp, in_range, &pg);
-        flush_pending();
-        if (!__any(visible)) return;
-        const bool pose_kf = kf_pose_is_unknown(L, k);
-        float pr[6] = {0, 0, 0, 0, 0, 0}, pM[6] = {0, 0, 0, 0, 0, 0};
-        float ir[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, iM[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // this keyframe's global intrinsics terms
-        if (visible) {
-          PairTerms t;
-          eval_pair_terms<kDepthIntr, kColorIntr>(L, in, kf, pg.a, pg.pix, pg.dw, gn, d1, d2, &t);
-          if (L.use_depth) {
-            if (L.optimize_geometry) {
-              gr[0] -= t.Jgeom * t.w * t.raw;
-              gM[0] += t.Jgeom * t.w * t.Jgeom;
-            }
-            if (pose_kf) {
-#pragma unroll
-              for (int c = 0; c < 6; ++c) { const float wj = t.w * t.Jpose[c]; pr[c] += -1 * wj * t.raw; pM[c] += t.Jpose[c] * wj; }
-            }
-            if (kDepthIntr) {
-              if (!t.di_valid) visible = false;   // B/kernel_pcg.cu:272-274: also hides the descriptor part
-              if (visible) {
-#pragma unroll
-                for (int c = 0; c < 5; ++c) { const float wj = t.w * t.Jdi[c]; ir[c] += -1 * wj * t.raw; iM[c] += t.Jdi[c] * wj; }
-                const float wj = t.w * t.Jcf;
-                pending_cf = head_index(L, t.cf_index);
-                pending_cf_r = -1 * wj * t.raw;
-                pending_cf_M = t.Jcf * wj;
-              }
-            }
-          }
-          if (L.use_desc && visible && t.color_ok) {
-            if (L.optimize_geometry) {
-              gr[0] -= t.Jg1 * t.w1 * t.raw1 + t.Jg2 * t.w2 * t.raw2;
-              gM[0] += t.Jg1 * t.w1 * t.Jg1 + t.Jg2 * t.w2 * t.Jg2;
-              gr[1] -= -1.f * t.w1 * t.raw1 + 0.f * t.w2 * t.raw2;
-              gM[1] += -1.f * t.w1 * -1.f + 0.f * t.w2 * 0.f;
-              gr[2] -= 0.f * t.w1 * t.raw1 + -1.f * t.w2 * t.raw2;
-              gM[2] += 0.f * t.w1 * 0.f + -1.f * t.w2 * -1.f;
-            }
-            if (pose_kf) {
-#pragma unroll
-              for (int c = 0; c < 6; ++c) {
-                const float wj1 = t.w1 * t.Jp1[c], wj2 = t.w2 * t.Jp2[c];
-                pr[c] += -1 * wj1 * t.raw1 + -1 * wj2 * t.raw2;
-                pM[c] += t.Jp1[c] * wj1 + t.Jp2[c] * wj2;
-              }
-            }
-            if (kColorIntr) {
-#pragma unroll
-              for (int c = 0; c < 4; ++c) {
-                const float wj1 = t.w1 * t.Jci1[c], wj2 = t.w2 * t.Jci2[c];
-                ir[5 + c] += -1 * wj1 * t.raw1 + -1 * wj2 * t.raw2;
-                iM[5 + c] += t.Jci1[c] * wj1 + t.Jci2[c] * wj2;
-              }
-            }
-          }
-        }
-        if (pose_kf || kIntr) {
-          // (tile, keyframe) totals with the halving butterfly of wave_reduce.h: lanes 4 j .. 4 j + 3 hold total j
-          const float va[16] = {pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], pM[0], pM[1], pM[2], pM[3], pM[4], pM[5], ir[0], ir[1], ir[2], ir[3]};
-          pending_a = wave_reduce_small<16>(va, lane);
-          if (kIntr) {
-            const float vb[16] = {ir[4], ir[5], ir[6], ir[7], ir[8], iM[0], iM[1], iM[2], iM[3], iM[4], iM[5], iM[6], iM[7], iM[8], 0.f, 0.f};
-            pending_b = wave_reduce_small<16>(vb, lane);
-          }
-          pending_any = true;
-          pending_pose = pose_kf;
-          pending_base = pose_kf ? kf_pose_index(L, k) : 0u;   // pose unknowns come first: head index == unknown index
-        }
-      };
+    ++visited;
+    pairs.candidate(kfs[k], [&] { return kf_pose_is_unknown(L, k); }, [&] { return kf_pose_index(L, k); });
+  };
   if constexpr (!kClassed) {
     for_each_candidate(num_kfs, may_project, candidate);
-    flush_pending();
+    pairs.flush();
     if (tile_cost && lane == 0 && visited) atomicAdd(&tile_cost[tile], visited);
 
     if (in_range && L.optimize_geometry) {
@@ -267,7 +168,7 @@ pcg_init_kernel(PcgLayout L, PcgExact ex, Intrinsics in, const KfEntry* __restri
 #pragma unroll
     for (int q = 0; q < 3; ++q) { gr[q] = 0.f; gM[q] = 0.f; }
   }
-  flush_pending();
+  pairs.flush();
   if (tile_cost && lane == 0 && visited) atomicAdd(&tile_cost[tile], visited);
 }
 
@@ -471,15 +372,18 @@ __device__ __forceinline__ void pcg_step1_tile(const PcgLayout& L, const PcgExac
     gs[0] = g_[gi];
     if (L.geom_stride == 3) { gs[1] = g_[gi + 1]; gs[2] = g_[gi + 2]; }
   }
-  constexpr bool kIntr = kDepthIntr || kColorIntr;
-  // exact atomics one candidate late, as in pcg_init_kernel.  The (tile, keyframe) totals: 6 pose entries of g, the keyframe's
-  // share of alpha_d and (intrinsics) the 9 global intrinsics entries of g -- 8 or 16 values, one halving butterfly.
+  // the pending (tile, keyframe) totals: the state of PcgStep1Pairs (pcg_device.h), which holds the pair body
   float pending = 0.f;
-  bool pending_any = false, pending_pose = false;   // wave-uniform
-  uint32_t pending_base = 0;                          // wave-uniform
-  uint32_t pending_cf = 0xffffffffu;                  // per lane
+  bool pending_any = false, pending_pose = false;
+  uint32_t pending_base = 0;
+  uint32_t pending_cf = 0xffffffffu;
   float pending_cf_g = 0.f;
-  auto flush_pending = [&]() {
+  const PcgStep1Pairs<kDepthIntr, kColorIntr> pairs{   // by name, as for PcgInitPairs
+      .L = L, .in = in, .p_ = p_, .gp = gp, .gn = gn, .tp = tp, .d1 = d1, .d2 = d2, .in_range = in_range, .lane = lane, .ps = ps, .pdi = pdi,
+      .pci = pci, .gs = gs, .pending = pending, .pending_any = pending_any, .pending_pose = pending_pose, .pending_base = pending_base,
+      .pending_cf = pending_cf, .pending_cf_g = pending_cf_g};
+  constexpr bool kIntr = kDepthIntr || kColorIntr;
+  auto flush_pending = [&]() {   // stays with the caller: pcg_device.h, PcgStep1Pairs
     if (pending_any) {
       const int j = kIntr ? (lane >> 2) : (lane >> 3), part = kIntr ? (lane & 3) : (lane & 7);   // the lanes that hold total j
       if (part < 2) {
@@ -499,97 +403,8 @@ __device__ __forceinline__ void pcg_step1_tile(const PcgLayout& L, const PcgExac
   };
   const auto may_project = [&](int k) { return sphere_may_project_item(in, kfs[k].pose.F, wb); };
   const auto candidate = [&](int k) {
-        const KfEntry& kf = kfs[k];
-        PairGather pg;
-        const bool visible = gather_and_associate(L, in, kf, gp, gn, tp, in_range, &pg);
-        const bool pose_kf = kf_pose_is_unknown(L, k);
-        const uint32_t base = kf_pose_index(L, k);
-        float pp[6] = {0, 0, 0, 0, 0, 0};
-        if (pose_kf) for (int c = 0; c < 6; ++c) pp[c] = p_[base + c];   // (wave-uniform address: scalar loads)
-        flush_pending();
-        if (!__any(visible)) return;
-        float gpose[6] = {0, 0, 0, 0, 0, 0};
-        float gi_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // this keyframe's terms of the global intrinsics entries
-        float ad = 0.f;                                   // ... and of alpha_d
-        if (visible) {
-          PairTerms t;
-          eval_pair_terms<kDepthIntr, kColorIntr>(L, in, kf, pg.a, pg.pix, pg.dw, gn, d1, d2, &t);
-          if (L.use_depth) {
-            float sum = 0;
-            if (L.optimize_geometry) sum += t.Jgeom * ps[0];
-            if (pose_kf) {
-#pragma unroll
-              for (int c = 0; c < 6; ++c) sum += t.Jpose[c] * pp[c];
-            }
-            const bool di = kDepthIntr && t.di_valid;
-            float pcf = 0.f;
-            if (di) {
-              sum += t.Jdi[2] * pdi[2];
-              sum += t.Jdi[3] * pdi[3];
-              sum += t.Jdi[0] * pdi[0];
-              sum += t.Jdi[1] * pdi[1];
-              sum += t.Jdi[4] * pdi[4];
-              pcf = p_[t.cf_index];
-              sum += t.Jcf * pcf;
-            }
-            ad += sum * t.w * sum;
-            sum *= t.w;
-            if (L.optimize_geometry) gs[0] += t.Jgeom * sum;
-            if (pose_kf) {
-#pragma unroll
-              for (int c = 0; c < 6; ++c) gpose[c] += t.Jpose[c] * sum;
-            }
-            if (di) {
-#pragma unroll
-              for (int c = 0; c < 5; ++c) gi_acc[c] += t.Jdi[c] * sum;
-              pending_cf = head_index(L, t.cf_index);
-              pending_cf_g = t.Jcf * sum;
-            }
-          }
-          if (L.use_desc && t.color_ok) {
-            float sum1 = 0, sum2 = 0;
-            if (L.optimize_geometry) {
-              sum1 += t.Jg1 * ps[0]; sum2 += t.Jg2 * ps[0];
-              sum1 += -1.f * ps[1];
-              sum2 += -1.f * ps[2];
-            }
-            if (pose_kf) {
-#pragma unroll
-              for (int c = 0; c < 6; ++c) { sum1 += t.Jp1[c] * pp[c]; sum2 += t.Jp2[c] * pp[c]; }
-            }
-            if (kColorIntr) {
-#pragma unroll
-              for (int c = 0; c < 4; ++c) { sum1 += t.Jci1[c] * pci[c]; sum2 += t.Jci2[c] * pci[c]; }
-            }
-            ad += sum1 * t.w1 * sum1 + sum2 * t.w2 * sum2;
-            sum1 *= t.w1; sum2 *= t.w2;
-            if (L.optimize_geometry) {
-              gs[0] += t.Jg1 * sum1 + t.Jg2 * sum2;
-              gs[1] += -1.f * sum1 + 0.f * sum2;
-              gs[2] += 0.f * sum1 + -1.f * sum2;
-            }
-            if (pose_kf) {
-#pragma unroll
-              for (int c = 0; c < 6; ++c) gpose[c] += t.Jp1[c] * sum1 + t.Jp2[c] * sum2;
-            }
-            if (kColorIntr) {
-#pragma unroll
-              for (int c = 0; c < 4; ++c) gi_acc[5 + c] += t.Jci1[c] * sum1 + t.Jci2[c] * sum2;
-            }
-          }
-        }
-        if (kIntr) {
-          const float v[16] = {gpose[0], gpose[1], gpose[2], gpose[3], gpose[4], gpose[5], ad, gi_acc[0], gi_acc[1], gi_acc[2], gi_acc[3], gi_acc[4],
-                               gi_acc[5], gi_acc[6], gi_acc[7], gi_acc[8]};
-          pending = wave_reduce_small<16>(v, lane);   // lanes 4 j .. 4 j + 3 hold total j
-        } else {
-          const float v[8] = {gpose[0], gpose[1], gpose[2], gpose[3], gpose[4], gpose[5], ad, 0.f};
-          pending = wave_reduce_small<8>(v, lane);    // lanes 8 j .. 8 j + 7 hold total j
-        }
-        pending_any = true;
-        pending_pose = pose_kf;
-        pending_base = pose_kf ? base : 0u;
-      };
+    pairs.candidate(kfs[k], [&] { return kf_pose_is_unknown(L, k); }, [&] { return kf_pose_index(L, k); }, flush_pending);
+  };
   if constexpr (!kClassed) {
     for_each_candidate(num_kfs, may_project, candidate);
     flush_pending();
@@ -760,18 +575,7 @@ __global__ void __launch_bounds__(kPcgBlock)
 pcg_update_surfels_kernel(PcgLayout L, SurfelsView s, const float* __restrict__ delta) {
   const uint32_t i = blockIdx.x * kPcgBlock + threadIdx.x;
   if (i >= s.size) return;
-  const uint32_t gi = L.surfel_start + (uint32_t)L.geom_stride * i;
-  const float t = delta[gi];
-  if (t != 0) {
-    const Vec3 np = surfel_position(s, i) + t * surfel_normal(s, i);
-    s.row(kSurfelX)[i] = np.x; s.row(kSurfelY)[i] = np.y; s.row(kSurfelZ)[i] = np.z;
-  }
-  if (L.geom_stride == 3) {
-    float a = s.row(kSurfelDescriptor1)[i]; a += delta[gi + 1];
-    s.row(kSurfelDescriptor1)[i] = fmaxf(-180.f, fminf(180.f, a));
-    float b = s.row(kSurfelDescriptor2)[i]; b += delta[gi + 2];
-    s.row(kSurfelDescriptor2)[i] = fmaxf(-180.f, fminf(180.f, b));
-  }
+  pcg_update_surfel(L, s, delta, i);
 }
 
 // UpdateCFactorsFromPCGDelta (B/kernel_pcg.cu:1361-1373)

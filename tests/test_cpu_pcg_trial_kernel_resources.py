@@ -1,55 +1,58 @@
 """Build-time guard for the step control of the PCG scheme (no GPU needed: hipcc cross-compiles gfx950).  The new unit
 (kernels_pcg_trial.hip) is compiled once, with the Makefile's flags: its snapshot / restore kernels take no scratch, make no scalar
 memory writes and stay within 32 VGPRs -- the 8 wavefronts per SIMD the unit's comment claims for a copy --, and its damped
-per-unknown kernels keep the shape of the undamped ones (no scratch, at least the 4 wavefronts per SIMD their LDS columns allow).  The
-pair sweeps were not touched: the whole-map sweeps (init, step 1, the LDS form) and the windowed ones compile to the gfx950 code of
-before, in both arithmetic flavours (digests as tests/test_cpu_pcg_window_kernel_resources.py takes them)."""
+per-unknown kernels keep the shape of the undamped ones (no scratch, at least the 4 wavefronts per SIMD their LDS columns allow).  Step
+control adds no pair sweep of its own: the whole-map sweeps (init, step 1, the LDS form) and the windowed ones compile to their recorded
+gfx950 code, in both arithmetic flavours (digests as tests/test_cpu_pcg_window_kernel_resources.py takes them; since the pair bodies
+are shared through pcg_device.h, 54 of the 64 are the digests of that tree, held to the earlier instruction mix by SWEEP_PARENT there)."""
 import re
 
 import pytest
 
 from tests.test_cpu_kernel_resources import HIPCC, _compile, _fast_flags, _kernels
-from tests.test_cpu_pcg_window_kernel_resources import PARENT, _digest, _functions
+from tests.isa_pins import _digest, _functions
+from tests.test_cpu_pcg_window_kernel_resources import PARENT
 
 pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc (the build container has it)")
 
-# sha256 (first 24 hex digits) of the windowed sweeps' normalised gfx950 code before step control, by mangled name
+# sha256 (first 24 hex digits) of the windowed sweeps' normalised gfx950 code, by mangled name (of the tree that shared the pair bodies
+# with the whole-map sweeps: tests/test_cpu_pcg_window_kernel_resources.py, PARENT and SWEEP_PARENT)
 WINDOW_PARENT = {
     "exact": {
         "_ZN5bahip5exact22pcg_window_init_kernelILb0ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
-            "080048e992e87443ee7677a3",
+            "18cdf73667da3e179c123d13",
         "_ZN5bahip5exact22pcg_window_init_kernelILb0ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
-            "d8f1d8ac0f026216f3eb9b0e",
+            "3d08002fc1de9ea05348e0ea",
         "_ZN5bahip5exact22pcg_window_init_kernelILb1ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
-            "bc232bdf07305a1e659d0a29",
+            "c374fd1c2b76bf96851e7530",
         "_ZN5bahip5exact22pcg_window_init_kernelILb1ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
-            "4b718362489b47d10d4a2b25",
+            "81f4bcb0d6d9f5008819f3f8",
         "_ZN5bahip5exact23pcg_window_step1_kernelILb0ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
             "1a679e98c62ed9bea13af0cf",
         "_ZN5bahip5exact23pcg_window_step1_kernelILb0ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
             "23abbebc9caff3a26c44d798",
         "_ZN5bahip5exact23pcg_window_step1_kernelILb1ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
-            "294df01ec9333ceb6a68c029",
+            "00469b4d1ea61d181ffeb655",
         "_ZN5bahip5exact23pcg_window_step1_kernelILb1ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
-            "d6fbe06d9ed4b7bdffbd8cd8",
+            "c6c5a900f10f53d1f7cd1b8e",
     },
     "fast": {
         "_ZN5bahip4fast22pcg_window_init_kernelILb0ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
-            "06eee103807164514103ee85",
+            "1782f9e0949d410810fb38bd",
         "_ZN5bahip4fast22pcg_window_init_kernelILb0ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
-            "469a963fa8e5f72485452ef1",
+            "f8d07d0461ee5b6f57148ce7",
         "_ZN5bahip4fast22pcg_window_init_kernelILb1ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
-            "ea2e2bd40920df832b0f563f",
+            "d8d6d0c82d51f73a60d87f82",
         "_ZN5bahip4fast22pcg_window_init_kernelILb1ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
-            "947eb98aba327df2e2b8aa70",
+            "49518194ef3ff11c17d9ab91",
         "_ZN5bahip4fast23pcg_window_step1_kernelILb0ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
-            "6206c122b24e3e27850c6ecf",
+            "dffe91e5189110d3ad9ea8e6",
         "_ZN5bahip4fast23pcg_window_step1_kernelILb0ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
-            "5d041051ef2abe6cca4e1e91",
+            "54ed21dff5b8fd66e498e74e",
         "_ZN5bahip4fast23pcg_window_step1_kernelILb1ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
-            "21d70ea7268ea99a18db4e47",
+            "cbd3dc75c6012b6ade55e29b",
         "_ZN5bahip4fast23pcg_window_step1_kernelILb1ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
-            "74aa12cf26d881180e97366c",
+            "326877cd373a59d208e397ab",
     },
 }
 SCALAR_WRITES = re.compile(r"\b(" + "|".join(["s_" + "store", "s_buffer_" + "store", "s_scratch_" + "store", "s_" + "atomic", "s_buffer_" + "atomic",

@@ -1,31 +1,29 @@
-"""Build-time guard for the windowed PCG scheme (no GPU needed: hipcc cross-compiles gfx950).  The windowed sweeps live in a unit of
-their own (kernels_pcg_window.hip) and share device helpers with kernels_pcg.hip through pcg_device.h; moving those helpers must not
-change the whole-map unit: every function of kernels_pcg.hip, in both arithmetic flavours, compiles with the Makefile's flags to the
-parent's gfx950 code -- the whole function up to its end label, every exit included (label numbers and comments aside).  The
-new unit's sweeps keep the PCG sweeps' budget -- 4 wavefronts per SIMD (<= 128 VGPRs), at most 64 bytes of scratch -- each in its
-flavour's namespace."""
-import hashlib
+"""Build-time guard for the PCG sweeps (no GPU needed: hipcc cross-compiles gfx950).  The whole-map sweeps (kernels_pcg.hip) and the
+windowed ones (kernels_pcg_window.hip, a unit of its own) are built from one definition of each pair body, in pcg_device.h.  What is
+held, with the Makefile's flags and in both arithmetic flavours:
+  - every function of kernels_pcg.hip that is no sweep (the per-unknown, control, resolve and debug kernels, exact_value) compiles to
+    the gfx950 code of before the windowed scheme -- the whole function up to its end label, every exit included (label numbers and
+    comments aside);
+  - every sweep kernel compiles to its recorded code (PARENT here, WINDOW_PARENT in tests/test_cpu_pcg_trial_kernel_resources.py:
+    the digests of this tree where sharing the pair bodies changed register numbering or instruction order);
+  - every sweep kernel has the instruction mix and the resources of the commit before the pair bodies were shared (SWEEP_PARENT): the
+    same number of instructions per mnemonic, the same NumVgprs, ScratchSize and Occupancy;
+  - the two plain kernels of the windowed unit (tile list, masked surfel update) compile to the code they had before (WINDOW_PLAIN);
+  - the windowed sweeps keep the PCG sweeps' budget -- 4 wavefronts per SIMD (<= 128 VGPRs), at most 64 bytes of scratch -- each in
+    its flavour's namespace."""
 import re
 
 import pytest
 
+from tests.isa_pins import _digest, _functions, _histogram   # noqa: F401  (re-exported: other resource tests import them from here)
 from tests.test_cpu_kernel_resources import HIPCC, _compile, _fast_flags, _kernels
 
 pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc (the build container has it)")
 
 
-def _functions(listing):
-    """mangled name -> the function's whole code, from its label to its .Lfunc_end label (every exit included)"""
-    return {m.group(1): m.group(2) for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", listing, re.S | re.M)}
-
-
-def _digest(body):
-    body = re.sub(r";.*", "", body)                          # comments
-    body = re.sub(r"\.L(BB|tmp)\d+_", r".L\1_", body)        # label numbers follow the function's place in the unit
-    return hashlib.sha256("\n".join(line.rstrip() for line in body.splitlines() if line.strip()).encode()).hexdigest()[:24]
-
-
-# sha256 (first 24 hex digits) of each function's normalised gfx950 code before the windowed scheme, by mangled name
+# sha256 (first 24 hex digits) of each function's normalised gfx950 code by mangled name: before the windowed scheme for the functions
+# that are no sweep, of the tree that shared the pair bodies for the sweep kernels whose register numbering or instruction order that
+# moved (10 of the 64 sweep kernels of both tables kept the digest they had; the others hold SWEEP_PARENT's instruction mix)
 PARENT = {
     "exact": {
         "_ZN5bahip11exact_valueERA9_Kx":
@@ -57,21 +55,21 @@ PARENT = {
         "_ZN5bahip30exact_sum_debug_resolve_kernelENS_8PcgExactEPd":
             "505daa3a8e3f73c0f47f81c1",
         "_ZN5bahip5exact15pcg_init_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
-            "6ec0526de443bd6825d0f830",
+            "0cf9b2aaedbd85ddf280e649",
         "_ZN5bahip5exact15pcg_init_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
             "7d6eee6d876489b83a410d77",
         "_ZN5bahip5exact15pcg_init_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
-            "4f8aed25e5eb9cb9cfa4f735",
+            "b2db1411ee6f9c0212424578",
         "_ZN5bahip5exact15pcg_init_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
-            "f263292b152a48eafbf180ea",
+            "83e741cbe2b11cab6e7af530",
         "_ZN5bahip5exact15pcg_init_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
-            "643d00ee2ef0dbcfed0379d4",
+            "21fea1ad91107b7df1b6b1fc",
         "_ZN5bahip5exact15pcg_init_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
-            "63c25efd9eb7a380e75dbcb7",
+            "76ade6e9b9169995fd33e658",
         "_ZN5bahip5exact15pcg_init_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
-            "a5e82ea1bd695f05172ab9ab",
+            "87be7ec57df02d5332bae6a8",
         "_ZN5bahip5exact15pcg_init_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
-            "0d4b66b7259ba672e24361b1",
+            "e13f00f6086041a2b783a678",
         "_ZN5bahip5exact16pcg_step1_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
             "0c7942f450024255e8e4cf40",
         "_ZN5bahip5exact16pcg_step1_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
@@ -81,81 +79,230 @@ PARENT = {
         "_ZN5bahip5exact16pcg_step1_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
             "08704f6b9bd5a0bbd3fb0d53",
         "_ZN5bahip5exact16pcg_step1_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "382f84346eb2eabecaafc267",
+            "7f597db9a6d01d26b240b94c",
         "_ZN5bahip5exact16pcg_step1_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "e810c07ba89cd2a4ea850f31",
+            "d8ed085df221b426332935d2",
         "_ZN5bahip5exact16pcg_step1_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "6ef0eb1fd569539b3101f418",
+            "31ec99bf05c3ac6da4cfa8b4",
         "_ZN5bahip5exact16pcg_step1_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "971812d7dece1f32b5419d2b",
+            "9f2d59af83e1006201b68cb8",
         "_ZN5bahip5exact20pcg_step1_lds_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "232fbda68079df5640768e66",
+            "2cfa7b2f69d14639d2af9af7",
         "_ZN5bahip5exact20pcg_step1_lds_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
             "0ef9105f9b1afc5072d26d4e",
         "_ZN5bahip5exact20pcg_step1_lds_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "6ff51c056a39b9382277fdb8",
+            "c03b7a618ed850c17dcf5dde",
         "_ZN5bahip5exact20pcg_step1_lds_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
             "7826763bb0c02350ff561901",
         "_ZN5bahip5exact20pcg_step1_lds_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "e054af80b92357b0a094c991",
+            "4db471f97f4a490996c1c337",
         "_ZN5bahip5exact20pcg_step1_lds_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "fcd020c613e25585cfcdbeb0",
+            "a9b8d661a14ce64803bbd503",
         "_ZN5bahip5exact20pcg_step1_lds_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "ce9c10d7c01b71b05cb34eec",
+            "f7c112a20d478bf0f955243d",
         "_ZN5bahip5exact20pcg_step1_lds_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "e537e81ee3b28892a0d36027",
+            "5de6666d209fd04a812d497a",
     },
     "fast": {
         "_ZN5bahip4fast15pcg_init_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
-            "d8ad6adb0667dfe8d30adf11",
+            "6577745445f8734f0424e27e",
         "_ZN5bahip4fast15pcg_init_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
             "d7eeb4ffa18121ad85eabedc",
         "_ZN5bahip4fast15pcg_init_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
-            "c8e29a2783ff87087d5cc88d",
+            "76cdc95bc08b1ba98fbe8f2d",
         "_ZN5bahip4fast15pcg_init_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
-            "caf92028a308cd3c4ee8a502",
+            "7ec062245042b5bc35b78ce0",
         "_ZN5bahip4fast15pcg_init_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
-            "6766e8824a5bfaf6c4945c4b",
+            "2e27effcd7a31cfce38e42b1",
         "_ZN5bahip4fast15pcg_init_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
-            "c5c1fab61c51373c90fbd4c8",
+            "5d4ea46d18054523047c59aa",
         "_ZN5bahip4fast15pcg_init_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
-            "f4286f548dbf91c55fb169e5",
+            "170eeb64e56648ff6442b1d5",
         "_ZN5bahip4fast15pcg_init_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
-            "61e5624fb75cc0e4f2afefba",
+            "9e992d5f1f7db6229cdc5e22",
         "_ZN5bahip4fast16pcg_step1_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "cc28588e885b08018e691748",
+            "63db06c4f1bb32019ae889e3",
         "_ZN5bahip4fast16pcg_step1_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "b7dc8791e1a84459f9e36ae3",
+            "ff8f8cf85826936054403660",
         "_ZN5bahip4fast16pcg_step1_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "eed9ce9e142e64f348458988",
+            "9c03879c99ba62334bc01e1f",
         "_ZN5bahip4fast16pcg_step1_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "b67ee2d66e2a6d0b387cf244",
+            "870ee5af7dff86b8ae14310c",
         "_ZN5bahip4fast16pcg_step1_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "0bc48ed9c9d37b4679a0d7c9",
+            "4fee7051be55f7206af2a8ae",
         "_ZN5bahip4fast16pcg_step1_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "c186eeb785a17e78426a6710",
+            "221fab9f9bd1a36ed571b526",
         "_ZN5bahip4fast16pcg_step1_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "b195244f349f1513c1e201e8",
+            "d020f06d15da72753dc7bef7",
         "_ZN5bahip4fast16pcg_step1_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
-            "888e3900c0f8d4194bab9b3b",
+            "fe0242b0eade9847aaf77812",
         "_ZN5bahip4fast20pcg_step1_lds_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "83546f06097590f2e4c43c2e",
+            "041ffe076bce6c126bc4a040",
         "_ZN5bahip4fast20pcg_step1_lds_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "9df2266928045bd89ed0e0b7",
+            "c0118f165c7bc9ffe8c1f592",
         "_ZN5bahip4fast20pcg_step1_lds_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "b05ecd1356d87df6959a11ec",
+            "6c3aeca3ddd0d5f5417a2196",
         "_ZN5bahip4fast20pcg_step1_lds_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "f707723aaabdf2f64dbe97fd",
+            "578168d418669bdf0d2cc16b",
         "_ZN5bahip4fast20pcg_step1_lds_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "eafd5a6e7b8d436847e743ef",
+            "c4c5b9de33f2e1cfa6703c1e",
         "_ZN5bahip4fast20pcg_step1_lds_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "11fbfc70400568b094d3ed28",
+            "b96633fb117dc0896e9499ec",
         "_ZN5bahip4fast20pcg_step1_lds_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "f2e719998f2f37c517f31300",
+            "18d43293b83db6642faaff19",
         "_ZN5bahip4fast20pcg_step1_lds_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
-            "177e3183a16d945bfa5122d0",
+            "7dc29a196b5a08d52ff64fd6",
     },
 }
+
+# The sweep kernels (24 whole-map + 8 windowed per flavour) at commit 7a6ae13, the parent of the commit that shared the pair bodies: per
+# mangled name (digest of the sorted (mnemonic, count) list of the function's instructions, their number, NumVgprs, ScratchSize,
+# Occupancy).  Regenerate: `git worktree add --detach <dir> 7a6ae13 && python scripts/pcg_sweep_mix.py <dir>` prints this table.
+SWEEP_PARENT = {
+    "exact": {
+        "_ZN5bahip5exact15pcg_init_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
+            ("4b1292ac09702c01", 2180, 119, 0, 4),
+        "_ZN5bahip5exact15pcg_init_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
+            ("21b4e5d3b7767f45", 2205, 121, 0, 4),
+        "_ZN5bahip5exact15pcg_init_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
+            ("1927857da5b8c510", 2868, 124, 0, 4),
+        "_ZN5bahip5exact15pcg_init_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
+            ("3e70f0e7aadd3c08", 2872, 126, 0, 4),
+        "_ZN5bahip5exact15pcg_init_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
+            ("a39c3bd2fe3e6724", 3457, 128, 12, 4),
+        "_ZN5bahip5exact15pcg_init_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
+            ("9efe9382967586d7", 3498, 128, 16, 4),
+        "_ZN5bahip5exact15pcg_init_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
+            ("e292af0820c45bd1", 3481, 128, 20, 4),
+        "_ZN5bahip5exact15pcg_init_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
+            ("ac14c731a1fddc02", 3618, 128, 24, 4),
+        "_ZN5bahip5exact16pcg_step1_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("dbe5838e78068667", 2344, 115, 0, 4),
+        "_ZN5bahip5exact16pcg_step1_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("90a5957737ac2eb0", 2355, 116, 0, 4),
+        "_ZN5bahip5exact16pcg_step1_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("fdaa2a4379a6d57d", 2647, 119, 0, 4),
+        "_ZN5bahip5exact16pcg_step1_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("6e70617bdc546db3", 2653, 120, 0, 4),
+        "_ZN5bahip5exact16pcg_step1_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("58d08cc9063908fb", 3068, 125, 0, 4),
+        "_ZN5bahip5exact16pcg_step1_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("3cfcd60537523cca", 3124, 127, 0, 4),
+        "_ZN5bahip5exact16pcg_step1_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("679d950f3bf07dcc", 3093, 127, 0, 4),
+        "_ZN5bahip5exact16pcg_step1_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("84aafb7737cf3394", 3131, 128, 0, 4),
+        "_ZN5bahip5exact20pcg_step1_lds_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("1d001d6eb8ff7505", 2773, 125, 0, 4),
+        "_ZN5bahip5exact20pcg_step1_lds_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("338fc53ff0657d15", 2815, 126, 0, 4),
+        "_ZN5bahip5exact20pcg_step1_lds_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("d66d72be7712a036", 3121, 128, 0, 4),
+        "_ZN5bahip5exact20pcg_step1_lds_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("d4c05f9820ab204d", 3130, 128, 8, 4),
+        "_ZN5bahip5exact20pcg_step1_lds_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("113f660f8bf26c6a", 3541, 128, 8, 4),
+        "_ZN5bahip5exact20pcg_step1_lds_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("1d058edcaa9fd812", 3552, 128, 0, 4),
+        "_ZN5bahip5exact20pcg_step1_lds_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("960e7f5a2e7ecf22", 3570, 128, 16, 4),
+        "_ZN5bahip5exact20pcg_step1_lds_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("6b19de83648b15f6", 3635, 128, 0, 4),
+        "_ZN5bahip5exact22pcg_window_init_kernelILb0ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
+            ("290c339e413a0861", 2063, 121, 0, 4),
+        "_ZN5bahip5exact22pcg_window_init_kernelILb0ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
+            ("a62d8fdbbff03bcb", 2716, 125, 0, 4),
+        "_ZN5bahip5exact22pcg_window_init_kernelILb1ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
+            ("7bbb1909f62b6c1c", 3343, 128, 16, 4),
+        "_ZN5bahip5exact22pcg_window_init_kernelILb1ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
+            ("50171b19936b33e4", 3406, 128, 36, 4),
+        "_ZN5bahip5exact23pcg_window_step1_kernelILb0ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
+            ("0591f169b0b08e51", 2278, 115, 0, 4),
+        "_ZN5bahip5exact23pcg_window_step1_kernelILb0ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
+            ("7b5a2d56c9ec9530", 2565, 119, 0, 4),
+        "_ZN5bahip5exact23pcg_window_step1_kernelILb1ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
+            ("bb7243e0aaef30e5", 2960, 125, 0, 4),
+        "_ZN5bahip5exact23pcg_window_step1_kernelILb1ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
+            ("59636cbc9079349c", 3003, 127, 0, 4),
+    },
+    "fast": {
+        "_ZN5bahip4fast15pcg_init_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
+            ("5e1f25ef590fc4ff", 1957, 119, 0, 4),
+        "_ZN5bahip4fast15pcg_init_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
+            ("549ee21ed9fd8220", 1989, 121, 0, 4),
+        "_ZN5bahip4fast15pcg_init_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
+            ("9a0b21ade4c37fde", 2635, 124, 0, 4),
+        "_ZN5bahip4fast15pcg_init_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
+            ("60aff522f6ad10b2", 2652, 126, 0, 4),
+        "_ZN5bahip4fast15pcg_init_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
+            ("182d1650710aad5c", 3174, 128, 16, 4),
+        "_ZN5bahip4fast15pcg_init_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
+            ("9868863f12c2a337", 3226, 128, 20, 4),
+        "_ZN5bahip4fast15pcg_init_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfS9_PjPKjDpT2_":
+            ("43b89ac2ec8b3d2d", 3196, 128, 24, 4),
+        "_ZN5bahip4fast15pcg_init_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPfSA_PjPKjDpT2_":
+            ("ba57d21a50e69191", 3238, 128, 28, 4),
+        "_ZN5bahip4fast16pcg_step1_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("d4328393e49030ba", 2116, 115, 0, 4),
+        "_ZN5bahip4fast16pcg_step1_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("166bebe160667538", 2128, 116, 0, 4),
+        "_ZN5bahip4fast16pcg_step1_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("b46e99ddf7b2f7dd", 2411, 119, 0, 4),
+        "_ZN5bahip4fast16pcg_step1_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("aa97fb8285d26b09", 2418, 120, 0, 4),
+        "_ZN5bahip4fast16pcg_step1_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("d28216c175936553", 2764, 125, 0, 4),
+        "_ZN5bahip4fast16pcg_step1_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("5c13bc2ee99d2265", 2789, 127, 0, 4),
+        "_ZN5bahip4fast16pcg_step1_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("73899e0c72f41fe6", 2801, 127, 0, 4),
+        "_ZN5bahip4fast16pcg_step1_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjDpT2_":
+            ("3fc9d272a7b8ffca", 2836, 128, 0, 4),
+        "_ZN5bahip4fast20pcg_step1_lds_kernelILb0ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("e76a5ecde7a6256b", 2555, 124, 0, 4),
+        "_ZN5bahip4fast20pcg_step1_lds_kernelILb0ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("561e05cb01db5de6", 2584, 125, 0, 4),
+        "_ZN5bahip4fast20pcg_step1_lds_kernelILb0ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("c661fb906adf7018", 2843, 127, 0, 4),
+        "_ZN5bahip4fast20pcg_step1_lds_kernelILb0ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("f96d8c0d78a4bae6", 2877, 128, 0, 4),
+        "_ZN5bahip4fast20pcg_step1_lds_kernelILb1ELb0ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("25b10243ab7c7be4", 3197, 128, 28, 4),
+        "_ZN5bahip4fast20pcg_step1_lds_kernelILb1ELb0ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("f828260a4b465e5d", 3270, 128, 20, 4),
+        "_ZN5bahip4fast20pcg_step1_lds_kernelILb1ELb1ELb0EJEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("f7bb4acfb4f2df92", 3254, 128, 28, 4),
+        "_ZN5bahip4fast20pcg_step1_lds_kernelILb1ELb1ELb1EJNS_10PcgClassesEEEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryEiNS_11SurfelsViewEPKfPfPKNS_10PcgControlEPKjjPjijDpT2_":
+            ("eec70bf69c5f0249", 3329, 128, 24, 4),
+        "_ZN5bahip4fast22pcg_window_init_kernelILb0ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
+            ("8d353c988acab57e", 1839, 121, 0, 4),
+        "_ZN5bahip4fast22pcg_window_init_kernelILb0ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
+            ("4e463e07af8d8d0d", 2494, 125, 0, 4),
+        "_ZN5bahip4fast22pcg_window_init_kernelILb1ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
+            ("7bbf2aefefed5efb", 3081, 128, 20, 4),
+        "_ZN5bahip4fast22pcg_window_init_kernelILb1ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPfSA_":
+            ("8e60222634918a66", 3117, 128, 28, 4),
+        "_ZN5bahip4fast23pcg_window_step1_kernelILb0ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
+            ("faf7f4bee5b64221", 2047, 115, 0, 4),
+        "_ZN5bahip4fast23pcg_window_step1_kernelILb0ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
+            ("00e8e25dd2c407ed", 2337, 119, 0, 4),
+        "_ZN5bahip4fast23pcg_window_step1_kernelILb1ELb0EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
+            ("6e5920a299286ac5", 2678, 125, 0, 4),
+        "_ZN5bahip4fast23pcg_window_step1_kernelILb1ELb1EEEvNS_9PcgLayoutENS_8PcgExactENS_10IntrinsicsEPKNS_7KfEntryENS_9PcgWindowENS_11SurfelsViewEPKfPfPKNS_10PcgControlE":
+            ("0fc762ce99936c55", 2745, 127, 0, 4),
+    },
+}
+
+
+# The two plain kernels of the windowed unit (tile list, masked surfel update: compiled once, in the exact unit), digests as PARENT's; they
+# are the bytes of commit 7a6ae13 -- pcg_update_surfel (pcg_device.h) became the body of both update kernels without moving either
+WINDOW_PLAIN = {
+    "_ZN5bahip23pcg_window_tiles_kernelENS_11SurfelsViewEPjS1_":
+        "9b6044f692fa129dab906436",
+    "_ZN5bahip32pcg_window_update_surfels_kernelENS_9PcgLayoutENS_11SurfelsViewEPKf":
+        "44738f8d95ca67a13eb935ce",
+}
+
 
 def _listings(tmp_path_factory, unit):
     d = tmp_path_factory.mktemp("isa_" + unit)
@@ -164,13 +311,23 @@ def _listings(tmp_path_factory, unit):
 
 
 @pytest.fixture(scope="module")
-def pcg(tmp_path_factory):
-    return {flavour: _functions(listing) for flavour, listing in _listings(tmp_path_factory, "kernels_pcg").items()}
+def pcg_listings(tmp_path_factory):
+    return _listings(tmp_path_factory, "kernels_pcg")
 
 
 @pytest.fixture(scope="module")
-def window(tmp_path_factory):
-    return {flavour: _kernels(listing) for flavour, listing in _listings(tmp_path_factory, "kernels_pcg_window").items()}
+def window_listings(tmp_path_factory):
+    return _listings(tmp_path_factory, "kernels_pcg_window")
+
+
+@pytest.fixture(scope="module")
+def pcg(pcg_listings):
+    return {flavour: _functions(listing) for flavour, listing in pcg_listings.items()}
+
+
+@pytest.fixture(scope="module")
+def window(window_listings):
+    return {flavour: _kernels(listing) for flavour, listing in window_listings.items()}
 
 
 @pytest.mark.parametrize("flavour", ["exact", "fast"])
@@ -196,3 +353,25 @@ def test_the_windowed_sweeps_keep_the_pcg_sweep_budget(window, flavour):
     assert len(helpers) == (2 if flavour == "exact" else 0), helpers
     for name in helpers:
         assert kernels[name][2] == 0, name
+
+
+@pytest.mark.parametrize("flavour", ["exact", "fast"])
+def test_every_sweep_kernel_has_the_parents_instruction_mix_and_resources(pcg_listings, window_listings, flavour):
+    """One definition of a pair body serves kernels that used to have a copy each; register numbering and instruction order may move
+    with that, what a sweep costs may not: per kernel the instructions per mnemonic, the registers, the scratch and the occupancy of
+    the parent commit.  No kernel is excepted."""
+    functions, kernels = {}, {}
+    for listing in (pcg_listings[flavour], window_listings[flavour]):
+        functions.update(_functions(listing))
+        kernels.update(_kernels(listing))
+    parent = SWEEP_PARENT[flavour]
+    assert len(parent) == 32 and set(parent) == {name for name in functions if re.search(r"\d+pcg_(window_)?(init|step1|step1_lds)_kernelI", name)}
+    moved = {name: (_histogram(functions[name]) + kernels[name][1:], expected) for name, expected in parent.items()
+             if _histogram(functions[name]) + kernels[name][1:] != expected}
+    assert not moved, moved
+
+
+def test_the_plain_kernels_of_the_windowed_unit_are_the_code_of_before(window_listings):
+    functions = _functions(window_listings["exact"])
+    changed = sorted(name for name, digest in WINDOW_PLAIN.items() if name not in functions or _digest(functions[name]) != digest)
+    assert len(WINDOW_PLAIN) == 2 and not changed, changed

@@ -9,7 +9,7 @@ import re
 import pytest
 
 from tests.test_cpu_kernel_resources import HIPCC, _compile, _fast_flags, _kernels
-from tests.test_cpu_pcg_window_kernel_resources import _digest, _functions
+from tests.isa_pins import _digest, _functions
 
 pytestmark = pytest.mark.skipif(HIPCC is None, reason="needs hipcc (the build container has it)")
 
