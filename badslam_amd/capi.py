@@ -305,6 +305,7 @@ SIGNATURES = {
     "bahip_debug_lifecycle_deal_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.c_int]),
     "bahip_debug_exact_sum": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "bahip_debug_count_pairs": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.POINTER(C.c_uint64)]),
+    "bahip_debug_tile_cull": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
     "bahip_debug_set_launch_shapes": (C.c_int, [C.c_int, C.c_int]),
     "bahip_debug_set_pose_form": (C.c_int, [C.c_int]),
     "bahip_debug_set_append_groups": (C.c_int, [C.c_int]),

@@ -84,6 +84,11 @@ void launch_activation_from_hits(hipStream_t stream, const SurfelsView& s, uint3
 
 void launch_count_pairs(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,
                         unsigned long long* counts);
+// kernels_cull_probe.hip: per 64-entry tile in buffer order the bounding sphere of wave_cull.h (bounds: 4 floats per tile, may be NULL)
+// and, per keyframe of the table, its frustum test against that sphere (masks: ceil(num_kfs / 64) words per tile, bit k % 64 of word
+// k / 64), in the flavour of in.fast_math
+void launch_tile_cull_probe(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, float* bounds,
+                            unsigned long long* masks);
 
 // kernels_pose.hip
 size_t pose_tile_bounds_bytes(uint32_t surfels);   // size of the per-tile bounding-sphere buffer launch_pose_accumulate needs
@@ -419,7 +424,10 @@ hipError_t launch_compact(hipStream_t st, const SurfelsView& s, uint32_t* invali
   void launch_pcg_window_init(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs,              \
                               const PcgWindow& w, const SurfelsView& s, float* r, float* M);                                                  \
   void launch_pcg_window_step1(hipStream_t st, const PcgLayout& L, const PcgExact& ex, const Intrinsics& in, const KfEntry* kfs,             \
-                               const PcgWindow& w, const SurfelsView& s, const float* p, float* g, const void* ctl);
+                               const PcgWindow& w, const SurfelsView& s, const float* p, float* g, const void* ctl);                    \
+  /* kernels_cull_probe.hip */                                                                                                                \
+  void launch_tile_cull_probe(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, float* bounds, \
+                              unsigned long long* masks);
 namespace exact { BAHIP_FLAVOURED_DECLARATIONS }
 namespace fast { BAHIP_FLAVOURED_DECLARATIONS }
 #define BAHIP_PICK(in, call) do { if ((in).fast_math) fast::call; else exact::call; } while (0)

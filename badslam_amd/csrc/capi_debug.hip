@@ -250,6 +250,25 @@ int bahip_debug_count_pairs(bahip_context* ctx, const bahip_surfels* surfels, ui
   return 0;
 }
 
+int bahip_debug_tile_cull(bahip_context* ctx, const bahip_surfels* surfels, float* bounds_out, uint64_t* masks_out) {
+  if (ctx == nullptr || surfels == nullptr || masks_out == nullptr) return fail("bahip_debug_tile_cull: NULL argument", __FILE__, __LINE__, hipSuccess);
+  REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
+  REQUIRE(ctx->num_kfs > 0 && ctx->dev_kfs != nullptr, "bahip_debug_tile_cull: no keyframes bound (bahip_set_keyframes)");
+  const SurfelsView view = make_view(surfels);
+  const size_t tiles = ((size_t)view.size + 63u) / 64u;
+  if (tiles == 0) return 0;
+  REQUIRE(view.data != nullptr, "bahip_debug_tile_cull: surfels without a buffer");
+  const size_t words = ((size_t)ctx->num_kfs + 63u) / 64u;
+  DeviceBuffer<float> d_bounds; DeviceBuffer<unsigned long long> d_masks;
+  if (d_bounds.reserve(4 * tiles, 0, kHookScratch) || d_masks.reserve(tiles * words, 0, kHookScratch)) return 1;
+  launch_tile_cull_probe(ctx->stream, ctx->in, ctx->dev_kfs, ctx->num_kfs, view, d_bounds, d_masks);
+  CHECK_LAUNCH();
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (bounds_out) HIP_TRY(hipMemcpy(bounds_out, d_bounds, sizeof(float) * 4 * tiles, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(masks_out, d_masks, sizeof(unsigned long long) * tiles * words, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int bahip_debug_set_intrinsics_bin_capacity(bahip_context* ctx, int records_per_block) {
   ctx->intr_bin_forced = records_per_block;
   return 0;

@@ -861,6 +861,29 @@ class Scene:
         capi.check(self.lib.bahip_debug_count_pairs(self.ctx.handle, C.byref(s), out))
         return [int(v) for v in out]
 
+    def tile_cull(self, size=None, want_bounds=True, prefill=None):
+        """The tile cull of the sweeps as the device compiles it in the context's flavour (bahip_debug_tile_cull) over the first `size`
+        surfels (default: all) and the bound keyframes: (bounds, masks) -- bounds (tiles, 4) float32 (centre, inflated radius; None
+        without want_bounds), masks (tiles, ceil(K / 64)) uint64, bit k % 64 of word k / 64 = the tile's sphere may project into
+        keyframe k.  prefill: a byte value both host arrays are filled with before the call (tests: a word the call did not write
+        shows; after a refused call they are the exception's `arrays` attribute)."""
+        n = self.surfels_size if size is None else int(size)
+        tiles, words = (n + 63) // 64, (len(self.keyframes) + 63) // 64
+        bounds = np.zeros((max(1, tiles), 4), np.float32) if want_bounds else None
+        masks = np.zeros((max(1, tiles), max(1, words)), np.uint64)
+        if prefill is not None:
+            for a in (bounds, masks):
+                if a is not None:
+                    a.view(np.uint8)[...] = prefill
+        s = self.surfels_struct(n)
+        try:
+            capi.check(self.lib.bahip_debug_tile_cull(self.ctx.handle, C.byref(s), bounds.ctypes.data_as(C.POINTER(C.c_float)) if want_bounds else None,
+                                                      masks.ctypes.data_as(C.POINTER(C.c_uint64))))
+        except capi.BackendError as e:
+            e.arrays = (bounds, masks)
+            raise
+        return (bounds[:tiles] if want_bounds else None), masks[:tiles, :words]
+
     def evaluate_pairs(self, i, surfel_indices, frame_T_global):
         idx = np.ascontiguousarray(surfel_indices, dtype=np.uint32)
         out = np.zeros((len(idx), 40), np.float32)

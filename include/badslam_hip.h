@@ -1091,6 +1091,14 @@ int bahip_debug_read_pattern(bahip_context* ctx, size_t bytes, int pattern, int 
 int bahip_debug_exact_math(bahip_context* ctx, int kind, const float* in, float* out, size_t n);
 int bahip_debug_pose_step(bahip_context* ctx, const float* H21_b6, const float* global_T_frame, float* out_25);
 int bahip_debug_count_pairs(bahip_context* ctx, const bahip_surfels* surfels, uint64_t* counts_out);
+/* The tile cull every surfel sweep begins with (badslam_amd/csrc/wave_cull.h), as the device compiles it in the context's arithmetic
+ * flavour.  Per 64-entry tile of the buffer, in buffer order (ceil(surfels_size / 64) tiles, the last one ragged): bounds_out[4 t ..
+ * 4 t + 3] = the bounding sphere (centre x, y, z, inflated radius; 0, 0, 0, -1 for a tile without a live entry) of the entries whose
+ * x is not NaN, and bit k % 64 of masks_out[t * ceil(K / 64) + k / 64] = may the sphere project into the depth image of bound keyframe
+ * k of K, at its bound pose (the bits beyond K are zero).  Activation flags of surfels and keyframes are ignored.  Host pointers;
+ * bounds_out may be NULL.  Refused, with nothing written: a NULL context, surfel struct or masks_out, intrinsics not set, no keyframe
+ * bound. */
+int bahip_debug_tile_cull(bahip_context* ctx, const bahip_surfels* surfels, float* bounds_out, uint64_t* masks_out);
 
 /* ---- instrumentation ---------------------------------------------------------------------------- */
 /* Time (ms, hipEvent on the context stream) and launch count of the kernels issued by the last
