@@ -290,6 +290,10 @@ SIGNATURES = {
                                              C.POINTER(ResidualImageOptions), C.POINTER(ResidualImageOut)]),
     "bahip_debug_set_residual_image_shape": (C.c_int, [C.c_int, C.c_int]),
     "bahip_debug_set_residual_image_stages": (C.c_int, [C.c_int]),
+    "bahip_observed_covisibility": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.c_void_p, C.c_int]),
+    "bahip_debug_set_covisibility_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bahip_debug_set_covisibility_stages": (C.c_int, [C.c_int]),
+    "bahip_debug_covisibility_census": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

@@ -624,6 +624,28 @@ void launch_residual_image_sweep(hipStream_t stream, const Intrinsics& in, const
 void launch_residual_image_resolve(hipStream_t stream, const Intrinsics& in, const ResidualFrame& frame, const SurfelsView& s, uint32_t index_base,
                                    const unsigned long long* keys, uint32_t pixels, const ResidualImagePlanes& out);
 
+// kernels_covisibility.hip: observed co-visibility, the surfels every pair of keyframes shares (exists once: the exact flavour's
+// association under either flavour).  counts: device, num_kfs rows of `pitch` words; launch shape: `waves` wavefronts per workgroup, at
+// most `workgroups` of them, `list_capacity` (keyframe, mask) entries per wavefront in LDS (12 bytes each) before a tile takes passes.
+constexpr int kCovisMaxWaves = 8, kCovisMaxListCapacity = 512, kCovisEntryBytes = 12;   // 8 x 512 x 12 bytes = 48 KB of LDS at most
+// default shape: 8 wavefronts per workgroup (12 KB), 4 workgroups per compute unit -- the fastest of the shapes
+// scripts/covisibility_eval.py times ("Observed co-visibility")
+constexpr int kCovisDefaultWaves = 8, kCovisWorkgroupsPerUnit = 4, kCovisDefaultListCapacity = 128;
+struct CovisShape {
+  int waves, workgroups, list_capacity;
+};
+void launch_covisibility_clear(hipStream_t stream, uint32_t* counts, int num_kfs, uint32_t pitch);
+// counts[i][j] += surfels of s associated with both keyframes, for i >= j (the lower triangle: launch_covisibility_mirror completes the
+// matrix); pair_stage false: the traversal and the lists only, no atomic (timing);
+// census: NULL or three zeroed words (entries with a non-zero mask, atomic adds issued, tiles with more entries than the list holds)
+void launch_covisibility_sweep(hipStream_t stream, const Intrinsics& in, const KfEntry* frames, int num_kfs, const SurfelsView& s,
+                               const uint32_t* sched, const CovisShape& shape, bool pair_stage, uint32_t* counts, uint32_t pitch,
+                               unsigned long long* census);
+void launch_covisibility_mirror(hipStream_t stream, uint32_t* counts, int num_kfs, uint32_t pitch);
+// the compact num_kfs x num_kfs words as int64 (what the ranks of a surfel partition sum), and the summed words into pitched rows
+void launch_covisibility_widen(hipStream_t stream, const uint32_t* compact, int num_kfs, long long* wide);
+void launch_covisibility_narrow(hipStream_t stream, const long long* wide, int num_kfs, uint32_t* counts, uint32_t pitch);
+
 // kernels_ingest.hip: a frame brought to the BA's pyramid level (exists once: integer rules and one correctly rounded division, the same
 // under either flavour).  The callers have checked sizes and pitches; the downscale's blocks are at most kIngestMaxBlock on a side.
 constexpr int kIngestMaxBlock = 9, kIngestMaxLevels = 3;

@@ -10,6 +10,7 @@
 //   capi_surfel_cost.hip the value of the BA objective per surfel (bahip_evaluate_surfel_costs)
 //   capi_render.hip     the surfel map rendered into a camera view (bahip_render_surfels)
 //   capi_residual_image.hip a frame's residuals per pixel (bahip_frame_residual_image)
+//   capi_covisibility.hip the surfels every pair of keyframes shares (bahip_observed_covisibility)
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
 //   capi_geometry_trial.hip step control of the geometry phase of the alternating scheme
@@ -220,6 +221,10 @@ struct bahip_context {
   // bahip_frame_residual_image: the dense key and pair-count planes of the sweep, when the caller passes NULL for them (kernels_residual_image.hip)
   DeviceBuffer<unsigned long long> residual_keys;
   DeviceBuffer<uint32_t> residual_counts;
+  // bahip_observed_covisibility: the three census words of the last call, and, with a transport installed, the words of a shard
+  // ([K x K int64 | K x K uint32]) that are summed over the ranks (kernels_covisibility.hip)
+  DeviceBuffer<unsigned long long> covis_census;
+  DeviceBuffer<long long> covis_stage;
   // dealing the lifecycle under surfel sharding (bahip_context_set_lifecycle_dealing): the switch, and the surfel partition of the
   // whole-cloud phase in progress -- set by bahip_gather_surfel_shards, cleared by bahip_extract_surfel_shard (deal_world 1: none) --
   // with the gathered cloud it belongs to: lifecycle calls on any other buffer are not dealt

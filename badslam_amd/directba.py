@@ -52,6 +52,8 @@ def _load():
         if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_keyframe_residual_image"):
             L.dba_keyframe_residual_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float),
                                                       C.POINTER(capi.ResidualImageOptions)] + [C.c_void_p] * 7 + [C.POINTER(C.c_float)]
+        if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_observed_covisibility"):
+            L.dba_observed_covisibility.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dba_surfel_count.restype = C.c_uint32
         L.dba_surfel_count.argtypes = [C.c_void_p]
         L.dba_surfels_size.restype = C.c_uint32
@@ -265,6 +267,18 @@ class DirectBA:
         out.update({name: np.zeros(n, np.uint32) for name in ("depth_residuals", "descriptor_pairs")})
         assert self.L.dba_compute_surfel_costs(self.h, self.stream, n, *[a.ctypes.data for a in out.values()]) == 0
         return out
+
+    def observed_covisibility(self):
+        """DirectBA::ComputeObservedCovisibility: (ids, counts) -- the ids of the existing keyframes in order and the (K, K) uint32
+        matrix of the surfels the association rule pairs with both keyframes of a pair (both triangles; the diagonal a keyframe's own
+        pair count).  Under surfel sharding with an all-reduce installed every rank gets the unsharded matrix."""
+        cap = max(1, self.keyframe_count())
+        counts = np.zeros(cap * cap, np.uint32)
+        ids = (C.c_int * cap)()
+        rows = C.c_int()
+        assert self.L.dba_observed_covisibility(self.h, self.stream, cap, counts.ctypes.data, ids, C.byref(rows)) == 0
+        K = rows.value
+        return [int(v) for v in ids[:K]], counts[:K * K].reshape(K, K).copy()
 
     def render_surfels(self, keyframe=None, view_camera=None, width=None, height=None, global_T_frame=None, options=None):
         """DirectBA::RenderKeyframeView (keyframe: an id -- the depth camera at that keyframe's pose) or DirectBA::RenderSurfels (the

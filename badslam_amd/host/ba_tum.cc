@@ -14,7 +14,7 @@
 //          [--bilateral_sigma_xy S] [--bilateral_sigma_inv_depth S] [--bilateral_radius_factor R] [--report_cost]
 //          [--pcg_step_control] [--pose_step_control] [--geometry_step_control] [--intrinsics_step_control]
 //          [--render_dir DIR [--render_mode point|disc] [--render_max_radius N] [--render_radius_factor F]]
-//          [--residual_dir DIR [--residual_select best|worst]]
+//          [--residual_dir DIR [--residual_select best|worst]] [--covisibility_file F]
 //          [--pyramid_level_for_depth N] [--pyramid_level_for_color N] [--median_filter_and_densify_iterations N]
 //
 // --pyramid_level_for_depth N / --pyramid_level_for_color N (0 .. 3): the BA runs on depth / colour images of 2^-N the dataset's size, with
@@ -33,6 +33,11 @@
 // clamp(32768 + (int)floorf(raw * 1024 + 0.5f), 1, 65535), raw in standard deviations), residual_%06d_pairs.pgm (binary P5, 8 bit:
 // min(pairs, 255)) and residuals.txt, one line per keyframe: id, explained pixels, pairs, pixels with two or more pairs, mean and RMS of
 // the winners' raw (accumulated in binary64 in row-major order, printed with 17 digits).
+// --covisibility_file F: after the last BA call (and after the saved state, the output files, the rendered views and the residual images)
+// the observed co-visibility of the final state (DirectBA::ComputeObservedCovisibility: the surfels the association rule pairs with both
+// keyframes) as a text file, one line per pair of keyframes i <= j in id order: id_i id_j shared frustum -- frustum = 1 if j is in i's
+// co-visibility list (the frustum test's), else 0 -- and one summary line on the output: the pairs i < j with shared > 0, the pairs of
+// the lists with shared == 0, and the pairs with shared > 0 that are in no list.  Nothing acts on the values.
 // --report_cost: prints the value of the BA objective (DirectBA::ComputeCost: total and the depth / descriptor sums and counts) before
 // the first and after the last BA call.
 // --pose_step_control: without --pcg, damped pose steps kept per keyframe only if its cost falls (DirectBA::SetPoseStepControl, its defaults)
@@ -191,7 +196,7 @@ int main(int argc, char** argv) {
   bool row_major_creation = false, report_cost = false, pcg_step_control = false, pose_step_control = false, geometry_step_control = false;
   bool intrinsics_step_control = false;
   bool use_pcg = false, intrinsics = false, incremental = false, parallel_ba = false;
-  std::string save_state, load_state, render_dir, residual_dir;
+  std::string save_state, load_state, render_dir, residual_dir, covisibility_file;
   DirectBA::RenderOptions render_options;
   DirectBA::ResidualImageOptions residual_options;
   PreprocessConfig config;
@@ -226,6 +231,7 @@ int main(int argc, char** argv) {
     else if (a == "--render_radius_factor" && i + 1 < argc) render_options.radius_factor = (float)atof(argv[++i]);
     else if (a == "--residual_dir" && i + 1 < argc) residual_dir = argv[++i];
     else if (a == "--residual_select" && i + 1 < argc && (!strcmp(argv[i + 1], "best") || !strcmp(argv[i + 1], "worst"))) residual_options.worst = !strcmp(argv[++i], "worst");
+    else if (a == "--covisibility_file" && i + 1 < argc) covisibility_file = argv[++i];
     else if (a == "--pyramid_level_for_depth" && i + 1 < argc) config.pyramid_level_for_depth = atoi(argv[++i]);
     else if (a == "--pyramid_level_for_color" && i + 1 < argc) config.pyramid_level_for_color = atoi(argv[++i]);
     else if (a == "--median_filter_and_densify_iterations" && i + 1 < argc) config.median_filter_and_densify_iterations = atoi(argv[++i]);
@@ -396,6 +402,30 @@ int main(int argc, char** argv) {
       ok = (fclose(summary) == 0) && ok;
       if (!ok) { fprintf(stderr, "cannot write the residual images to %s\n", residual_dir.c_str()); return 1; }
       printf("wrote %d residual image(s) (%s pair per pixel) to %s\n", images, residual_options.worst ? "worst" : "best", residual_dir.c_str());
+    }
+    if (!covisibility_file.empty()) {
+      vector<uint32_t> counts;
+      vector<int> ids;
+      ba.ComputeObservedCovisibility(stream, &counts, &ids);
+      const size_t K = ids.size();
+      FILE* file = fopen(covisibility_file.c_str(), "w");
+      if (!file) { fprintf(stderr, "cannot write the observed co-visibility to %s\n", covisibility_file.c_str()); return 1; }
+      size_t shared_pairs = 0, list_pairs_without = 0, shared_pairs_unlisted = 0;
+      for (size_t i = 0; i < K; ++i) {
+        const vector<int>& list = ba.keyframes()[ids[i]]->co_visibility_list();
+        for (size_t j = i; j < K; ++j) {
+          const uint32_t shared = counts[i * K + j];
+          const bool listed = std::find(list.begin(), list.end(), ids[j]) != list.end();
+          fprintf(file, "%d %d %u %d\n", ids[i], ids[j], shared, listed ? 1 : 0);
+          if (i == j) continue;
+          if (shared > 0) ++shared_pairs;
+          if (listed && shared == 0) ++list_pairs_without;
+          if (!listed && shared > 0) ++shared_pairs_unlisted;
+        }
+      }
+      if (fclose(file) != 0) { fprintf(stderr, "cannot write the observed co-visibility to %s\n", covisibility_file.c_str()); return 1; }
+      printf("wrote the observed co-visibility of %zu keyframe(s) to %s: %zu pair(s) share surfels, %zu pair(s) of the lists share none, %zu sharing pair(s) "
+             "are in no list\n", K, covisibility_file.c_str(), shared_pairs, list_pairs_without, shared_pairs_unlisted);
     }
   }
   bahip_stream_destroy(stream);

@@ -171,6 +171,20 @@ int dba_compute_surfel_costs(dba_handle* h, void* stream, uint32_t capacity, dou
   return 0;
 }
 
+int dba_observed_covisibility(dba_handle* h, void* stream, int capacity_rows, uint32_t* counts, int* keyframe_ids, int* num_rows_out) {
+  int rows = 0;
+  for (int id = 0; id < (int)h->ba->keyframes().size(); ++id)
+    if (h->ba->keyframes()[id]) ++rows;
+  if (num_rows_out) *num_rows_out = rows;
+  if (capacity_rows < rows || !counts) return 1;
+  std::vector<uint32_t> words;
+  std::vector<int> ids;
+  h->ba->ComputeObservedCovisibility(static_cast<hipStream_t>(stream), &words, &ids);
+  std::copy(words.begin(), words.end(), counts);
+  if (keyframe_ids) std::copy(ids.begin(), ids.end(), keyframe_ids);
+  return 0;
+}
+
 int dba_render_surfels(dba_handle* h, void* stream, int keyframe_id, const float view_camera[4], int width, int height,
                        const float global_T_frame[7], const bahip_render_options* options, float* depth, uint32_t* index, float* normal,
                        uint8_t* color, float frame_T_global_out[12]) {

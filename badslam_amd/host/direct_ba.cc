@@ -569,6 +569,20 @@ void DirectBA::ComputeSurfelCosts(hipStream_t stream, SurfelCosts* out) {
   BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
 }
 
+void DirectBA::ComputeObservedCovisibility(hipStream_t stream, vector<uint32_t>* counts, vector<int>* keyframe_ids) {
+  BindScene(stream);
+  const bahip_surfels s = SurfelsStruct(/*with_active*/ false);
+  const size_t K = bound_ids_.size();
+  counts->assign(K * K, 0u);
+  if (keyframe_ids) keyframe_ids->assign(bound_ids_.begin(), bound_ids_.end());
+  if (K == 0) return;
+  CUDABuffer<uint32_t> words(1, (int)(K * K));
+  uint32_t* dev = words.ToCUDA().address();
+  BAHIP_CHECKED_CALL(bahip_observed_covisibility(ctx_, &s, dev, (int)K));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, counts->data(), dev, sizeof(uint32_t) * K * K, 2));
+  BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
+}
+
 void DirectBA::RenderSurfels(hipStream_t stream, const PinholeCamera4f& view, const SE3f& global_T_frame, const RenderOptions& options,
                              RenderedView* out) {
   BAHIP_CHECKED_CALL(bahip_context_set_stream(ctx_, stream));

@@ -65,6 +65,12 @@ class DirectBA {
     vector<uint32_t> depth_residuals, descriptor_pairs;
   };
   void ComputeSurfelCosts(hipStream_t stream, SurfelCosts* out);
+  // Observed co-visibility (bahip_observed_covisibility; DESIGN.md section 3, "Observed co-visibility"): counts[i * K + j] = the surfels
+  // the association rule pairs with both the i-th and the j-th existing keyframe, K x K row-major, both triangles, the diagonal a
+  // keyframe's own pair count; keyframe_ids[i] = the id of row i (deleted keyframes are not rows, as with ComputeCost).  Nothing acts on
+  // the values: the co-visibility lists of the keyframes stay the frustum test's.  Surfel sharding with an all-reduce installed: every
+  // rank gets the unsharded matrix; keyframe sharding: refused.  Waits for the stream.
+  void ComputeObservedCovisibility(hipStream_t stream, vector<uint32_t>* counts, vector<int>* keyframe_ids);
   // The surfel map seen from a camera (bahip_render_surfels; DESIGN.md section 3, "Rendered views of the map"): per pixel of `view` at
   // pose global_T_frame the nearest surfel's depth, buffer index, normal in the view's frame and colour, row-major.  Empty pixels hold
   // depth 0, index 0xFFFFFFFF, normal (0, 0, 0), colour 0.  Binds nothing; under surfel sharding the view of this rank's shard.  Waits

@@ -847,6 +847,36 @@ class Scene:
         return frame_residual_image(self.ctx, self.frame_struct(k), frame_T_global, self.surfels_struct(size), self.depth_cam.width,
                                     self.depth_cam.height, select=select, index_base=index_base, planes=planes, prefill=prefill)
 
+    def observed_covisibility(self, size=None, pitch=None, prefill=None):
+        """The surfels every pair of bound keyframes shares (bahip_observed_covisibility) over the first `size` surfels (default: all):
+        a (K, K) uint32 array in bound order, both triangles, the diagonal a keyframe's own pair count.  pitch: words per row of the
+        device buffer (default K; the call refuses less) -- the result is then the whole (K, pitch) buffer; prefill: a byte value the
+        buffer is filled with before the call (tests: a word the call did not write shows; after a refused call the buffer is the
+        exception's `arrays` attribute).  Call bind_keyframes first."""
+        K = len(self.keyframes)
+        p = K if pitch is None else int(pitch)
+        buf = DeviceBuffer2D(self.ctx, 1, max(1, K * max(p, 1)), np.uint32)
+        try:
+            buf.clear(0 if prefill is None else prefill)
+            s = self.surfels_struct(size)
+            try:
+                capi.check(self.lib.bahip_observed_covisibility(self.ctx.handle, C.byref(s), buf.ptr, p))
+            except capi.BackendError as e:
+                self.ctx.synchronize()
+                e.arrays = buf.download()[0].copy()
+                raise
+            self.ctx.synchronize()
+            return buf.download()[0, :K * p].reshape(K, p).copy()
+        finally:
+            buf.free()
+
+    def covisibility_census(self):
+        """Of the last observed_covisibility: [(tile, keyframe) entries with a non-zero mask, atomic adds issued, tiles that took the
+        overflow path] (bahip_debug_covisibility_census)."""
+        out = (C.c_uint64 * 3)()
+        capi.check(self.lib.bahip_debug_covisibility_census(self.ctx.handle, out))
+        return [int(v) for v in out]
+
     def exact_sum(self, values, mode=0):
         """Exactly rounded binary64 sum of binary32 values through the device's exact accumulators (test hook)."""
         v = np.ascontiguousarray(values, np.float32)

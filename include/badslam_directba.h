@@ -69,6 +69,12 @@ int dba_compute_cost(dba_handle* h, void* hip_stream, bahip_cost* total, bahip_c
  * unsharded values on every rank; surfel sharding: this rank's shard.  Returns non-zero when capacity is too small. */
 int dba_compute_surfel_costs(dba_handle* h, void* hip_stream, uint32_t capacity, double* depth, double* descriptor_1, double* descriptor_2,
                              uint32_t* depth_residuals, uint32_t* descriptor_pairs);
+/* DirectBA::ComputeObservedCovisibility (ours): the surfels the association rule pairs with both of two keyframes
+ * (bahip_observed_covisibility), over the existing keyframes in id order (deleted ids are not rows).  *num_rows_out = K, the number of
+ * rows; when capacity_rows >= K: keyframe_ids[0 .. K) = the id of each row (may be NULL) and counts[i * K + j], K x K row-major, both
+ * triangles, the diagonal a keyframe's own pair count.  Returns non-zero, with *num_rows_out set and nothing else written, when
+ * capacity_rows < K.  Surfel sharding with an all-reduce installed: the unsharded matrix on every rank; keyframe sharding: refused. */
+int dba_observed_covisibility(dba_handle* h, void* hip_stream, int capacity_rows, uint32_t* counts, int* keyframe_ids, int* num_rows_out);
 /* DirectBA::RenderSurfels / RenderKeyframeView (ours): the surfel map seen from a camera (bahip_render_surfels), row-major host planes
  * of width * height pixels, any may be NULL: depth, index, normal (3 floats per pixel), color (4 bytes per pixel).  keyframe_id >= 0:
  * the depth camera at that keyframe's pose (view_camera, width, height and global_T_frame are ignored; the planes have the depth

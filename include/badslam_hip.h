@@ -747,6 +747,36 @@ int bahip_debug_set_residual_image_shape(int waves, int workgroups);
  * 4 resolve, or-ed; 0 = all.  With a stage missing the planes are not a residual image. */
 int bahip_debug_set_residual_image_stages(int stages);
 
+/* ---- observed co-visibility (kernels_covisibility.hip; DESIGN.md section 3, "Observed co-visibility") ------------------------------
+ * The objective as a graph over the keyframes: how many surfels the BA's own association rule pairs with both keyframe i and keyframe
+ * j.  counts: device memory, borrowed for the call, K rows of pitch_words >= K words, K the number of bound keyframes
+ * (bahip_set_keyframes); rows and columns in bound order, as per_keyframe of bahip_evaluate_cost.  After a successful call, for all
+ * i, j < K, counts[i * pitch_words + j] is the number of surfels s < surfels_size associated with both keyframe i and keyframe j, where
+ * "associated" is the pair population of bahip_evaluate_cost with the depth term on: the production association rule, a finite
+ * position, activation flags of surfels and keyframes ignored.  Both triangles are written; the diagonal is the keyframe's own pair
+ * count (per_keyframe[i].depth_residuals of bahip_evaluate_cost(use_depth = 1)).  The words [K, pitch_words) of a row are never
+ * touched.  K = 0 succeeds and writes nothing; surfels_size = 0 writes zeros.  Sums of integers: nothing depends on the launch shape,
+ * the tile order, the surfel order or the order in which atomics arrive.  The kernels exist once, in the exact arithmetic flavour: a
+ * context set to BAHIP_ARITHMETIC_FAST launches the same code, so the matrix is the exact flavour's association.
+ * The call is refused -- error text, nothing written, nothing launched, the context still usable -- when ctx, surfels or counts is NULL,
+ * pitch_words < K, no intrinsics are set, or the context is keyframe-sharded: a rank then holds the masks of its own keyframes only, and
+ * a pair of keyframes on two ranks would need their mask tables exchanged, which is left for later (use surfel sharding).
+ * Asynchronous on the context's stream.  Surfel sharding: the call covers the shard it is given; with an all-reduce hook or an RCCL
+ * communicator installed the K x K words are summed over the ranks as int64 (one exchange of K x K words; a rank with an empty shard
+ * takes part too; the hook's waits apply) and every rank ends with the unsharded matrix; without one the shards' matrices are summed by
+ * the caller.  A failing exchange fails the call, writes nothing into counts and leaves the context usable. */
+int bahip_observed_covisibility(bahip_context* ctx, const bahip_surfels* surfels, uint32_t* counts, int pitch_words);
+/* Launch shape of the sweep (test hook; results never depend on it): wavefronts per workgroup 1 .. 8, workgroups >= 1, list_capacity
+ * 1 .. 512 = the (keyframe, mask) entries a wavefront keeps in LDS before a tile is walked in passes (the overflow path), tile_order
+ * 0 = buffer order, 1 = the sweeps' heavy-first order when there is one; 0 / -1 = the default. */
+int bahip_debug_set_covisibility_shape(int waves, int workgroups, int list_capacity, int tile_order);
+/* What bahip_observed_covisibility launches (scripts/covisibility_eval.py takes the stages' times by difference): 1 clear, 2 traversal
+ * (the lists are built), 4 pair stage (the atomics and the copy of the lower triangle into the upper one; needs 2), or-ed; 0 = all.  With a stage missing the words are not the matrix. */
+int bahip_debug_set_covisibility_stages(int stages);
+/* Of the last bahip_observed_covisibility of this context (this rank's shard), after a wait: out[0] = (tile, keyframe) entries with a
+ * non-zero mask, out[1] = atomic adds issued into counts, out[2] = tiles that took the overflow path. */
+int bahip_debug_covisibility_census(bahip_context* ctx, uint64_t out[3]);
+
 /* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
  * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
  * e = 1e-8 + prior(u) as before and t = lambda * M[u] (one binary32 product), the preconditioner divides by ((M[u] + 1e-8) + prior(u))
