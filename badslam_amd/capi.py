@@ -115,7 +115,12 @@ class ResidualImageOut(C.Structure):      # bahip_residual_image_out: device pla
                 ("inv_stddev", C.c_void_p), ("desc_residual", C.c_void_p), ("color_valid", C.c_void_p)]
 
 
-class PoseStepControl(C.Structure):   # bahip_pose_step_control: step control of the pose phase (bahip_estimate_keyframe_poses_controlled)
+class Observations(C.Structure):          # bahip_observations: device planes of the observation lists (bahip_surfel_observations)
+    _fields_ = [("surfel_first", C.c_void_p), ("keyframes", C.c_void_p), ("depth_raw", C.c_void_p), ("descriptor_raw", C.c_void_p),
+                ("capacity", C.c_uint64)]
+
+
+class PoseStepControl(C.Structure):  # bahip_pose_step_control: step control of the pose phase (bahip_estimate_keyframe_poses_controlled)
     _fields_ = [("lambda_up", C.c_float), ("lambda_down", C.c_float), ("lambda_min", C.c_float), ("lambda_max", C.c_float),
                 ("max_trials", C.c_int)]
 
@@ -294,6 +299,9 @@ SIGNATURES = {
     "bahip_debug_set_covisibility_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bahip_debug_set_covisibility_stages": (C.c_int, [C.c_int]),
     "bahip_debug_covisibility_census": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bahip_surfel_observations": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.POINTER(Observations), C.POINTER(C.c_uint64)]),
+    "bahip_debug_set_observations_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64]),
+    "bahip_debug_set_observations_stages": (C.c_int, [C.c_int]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

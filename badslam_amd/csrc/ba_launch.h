@@ -646,6 +646,33 @@ void launch_covisibility_mirror(hipStream_t stream, uint32_t* counts, int num_kf
 void launch_covisibility_widen(hipStream_t stream, const uint32_t* compact, int num_kfs, long long* wide);
 void launch_covisibility_narrow(hipStream_t stream, const long long* wide, int num_kfs, uint32_t* counts, uint32_t pitch);
 
+// kernels_observations.hip: observation lists, the keyframes paired with each surfel in compressed rows (exists once: the exact
+// flavour's association and residual bits under either flavour).  Launch shape: `waves` wavefronts per workgroup, at most `workgroups`
+// of them; stage_entries 0: the direct fill (each lane stores into its own list), > 0: the staged fill, the first stage_entries entries
+// of a tile assembled in LDS per wavefront and written with coalesced stores, the entries beyond stored at once.
+constexpr int kObsMaxWaves = 8, kObsMaxStageEntries = 4096;
+constexpr int kObsKeyframeBytes = 2, kObsDepthBytes = 4, kObsDescriptorBytes = 8;   // of a staged entry, per plane asked for
+constexpr int kObsMaxLdsBytes = 65536;                                              // waves x stage_entries x entry bytes at most
+// default shape and window: the fastest of those scripts/surfel_observations_eval.py times ("Observation lists")
+constexpr int kObsDefaultWaves = 4, kObsWorkgroupsPerUnit = 4, kObsDefaultStageEntries = 1024;
+struct ObsShape {
+  int waves, workgroups, stage_entries;
+};
+struct ObsPlanes {   // device; keyframes required for a fill, the payload planes may be NULL
+  uint16_t* keyframes;
+  float* depth_raw;
+  float* descriptor_raw;
+};
+inline size_t obs_entry_bytes(const ObsPlanes& p) {
+  return (size_t)kObsKeyframeBytes + (p.depth_raw ? kObsDepthBytes : 0) + (p.descriptor_raw ? kObsDescriptorBytes : 0);
+}
+// counts[s] = the keyframes paired with surfel s, for s < s.size (counts[s.size] is not written); *total (zeroed) += their sum
+void launch_observations_count(hipStream_t stream, const Intrinsics& in, const KfEntry* frames, int num_kfs, const SurfelsView& s,
+                               const uint32_t* sched, const ObsShape& shape, uint32_t* counts, unsigned long long* total);
+// the entries [first[s], first[s + 1]) of every plane given, for s < s.size: first is the exclusive scan of the counts (s.size + 1 words)
+void launch_observations_fill(hipStream_t stream, const Intrinsics& in, const KfEntry* frames, int num_kfs, const SurfelsView& s,
+                              const uint32_t* sched, const ObsShape& shape, const uint32_t* first, const ObsPlanes& planes);
+
 // kernels_ingest.hip: a frame brought to the BA's pyramid level (exists once: integer rules and one correctly rounded division, the same
 // under either flavour).  The callers have checked sizes and pitches; the downscale's blocks are at most kIngestMaxBlock on a side.
 constexpr int kIngestMaxBlock = 9, kIngestMaxLevels = 3;

@@ -11,6 +11,7 @@
 //   capi_render.hip     the surfel map rendered into a camera view (bahip_render_surfels)
 //   capi_residual_image.hip a frame's residuals per pixel (bahip_frame_residual_image)
 //   capi_covisibility.hip the surfels every pair of keyframes shares (bahip_observed_covisibility)
+//   capi_observations.hip the keyframes paired with each surfel, in compressed rows (bahip_surfel_observations)
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
 //   capi_geometry_trial.hip step control of the geometry phase of the alternating scheme
@@ -225,6 +226,11 @@ struct bahip_context {
   // ([K x K int64 | K x K uint32]) that are summed over the ranks (kernels_covisibility.hip)
   DeviceBuffer<unsigned long long> covis_census;
   DeviceBuffer<long long> covis_stage;
+  // bahip_surfel_observations: the per-surfel counts (surfels_size + 1 words, the last zero), their 64-bit total and the scan's
+  // storage (kernels_observations.hip)
+  DeviceBuffer<uint32_t> obs_counts;
+  DeviceBuffer<unsigned long long> obs_total;
+  DeviceBuffer<void> obs_scan_temp;
   // dealing the lifecycle under surfel sharding (bahip_context_set_lifecycle_dealing): the switch, and the surfel partition of the
   // whole-cloud phase in progress -- set by bahip_gather_surfel_shards, cleared by bahip_extract_surfel_shard (deal_world 1: none) --
   // with the gathered cloud it belongs to: lifecycle calls on any other buffer are not dealt

@@ -54,6 +54,9 @@ def _load():
                                                       C.POINTER(capi.ResidualImageOptions)] + [C.c_void_p] * 7 + [C.POINTER(C.c_float)]
         if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_observed_covisibility"):
             L.dba_observed_covisibility.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_surfel_observations"):
+            L.dba_surfel_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int] + [C.c_void_p] * 4 + \
+                [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.dba_surfel_count.restype = C.c_uint32
         L.dba_surfel_count.argtypes = [C.c_void_p]
         L.dba_surfels_size.restype = C.c_uint32
@@ -279,6 +282,27 @@ class DirectBA:
         assert self.L.dba_observed_covisibility(self.h, self.stream, cap, counts.ctypes.data, ids, C.byref(rows)) == 0
         K = rows.value
         return [int(v) for v in ids[:K]], counts[:K * K].reshape(K, K).copy()
+
+    def surfel_observations(self, residuals=False):
+        """DirectBA::ComputeSurfelObservations: a dict -- keyframe_ids (the id of each bound index), first (surfels_size + 1 uint32
+        offsets, the last one the number of pairs P), keyframes (P uint16 indices into keyframe_ids, ascending within a surfel's list)
+        and, with residuals, depth_raw (P float32) and descriptor_raw ((P, 2) float32, NaN where the pair's colour pixel is not
+        valid).  Under surfel sharding this rank's shard."""
+        n, cap = self.surfels_size(), max(1, self.keyframe_count())
+        pairs, K = C.c_uint64(), C.c_int()
+        self.L.dba_surfel_observations(self.h, self.stream, 0, 0, 0, None, None, None, None, None, C.byref(pairs), C.byref(K))   # sizes the arrays
+        P = int(pairs.value)
+        first, ks = np.zeros(n + 1, np.uint32), np.zeros(P, np.uint16)
+        depth, desc = (np.zeros(P, np.float32), np.zeros((P, 2), np.float32)) if residuals else (None, None)
+        ids = (C.c_int * cap)()
+        assert self.L.dba_surfel_observations(self.h, self.stream, n, P, cap, first.ctypes.data, ks.ctypes.data,
+                                              depth.ctypes.data if residuals else None, desc.ctypes.data if residuals else None, ids,
+                                              C.byref(pairs), C.byref(K)) == 0
+        assert pairs.value == P
+        out = dict(keyframe_ids=[int(v) for v in ids[:K.value]], first=first, keyframes=ks)
+        if residuals:
+            out.update(depth_raw=depth, descriptor_raw=desc)
+        return out
 
     def render_surfels(self, keyframe=None, view_camera=None, width=None, height=None, global_T_frame=None, options=None):
         """DirectBA::RenderKeyframeView (keyframe: an id -- the depth camera at that keyframe's pose) or DirectBA::RenderSurfels (the

@@ -14,7 +14,7 @@
 //          [--bilateral_sigma_xy S] [--bilateral_sigma_inv_depth S] [--bilateral_radius_factor R] [--report_cost]
 //          [--pcg_step_control] [--pose_step_control] [--geometry_step_control] [--intrinsics_step_control]
 //          [--render_dir DIR [--render_mode point|disc] [--render_max_radius N] [--render_radius_factor F]]
-//          [--residual_dir DIR [--residual_select best|worst]] [--covisibility_file F]
+//          [--residual_dir DIR [--residual_select best|worst]] [--covisibility_file F] [--observations_file F]
 //          [--pyramid_level_for_depth N] [--pyramid_level_for_color N] [--median_filter_and_densify_iterations N]
 //
 // --pyramid_level_for_depth N / --pyramid_level_for_color N (0 .. 3): the BA runs on depth / colour images of 2^-N the dataset's size, with
@@ -38,6 +38,10 @@
 // keyframes) as a text file, one line per pair of keyframes i <= j in id order: id_i id_j shared frustum -- frustum = 1 if j is in i's
 // co-visibility list (the frustum test's), else 0 -- and one summary line on the output: the pairs i < j with shared > 0, the pairs of
 // the lists with shared == 0, and the pairs with shared > 0 that are in no list.  Nothing acts on the values.
+// --observations_file F: after the co-visibility file, the observation lists of the final state (DirectBA::ComputeSurfelObservations: per
+// surfel the keyframes the association rule pairs it with) as a text file, one line per surfel with at least one pair: surfel_index count
+// id ... (the keyframe ids ascending), and one summary line on the output: the number of pairs, the histogram of the list lengths and
+// the surfels whose list is shorter than min_observation_count (what the next deletion pass would remove).  Nothing acts on the lists.
 // --report_cost: prints the value of the BA objective (DirectBA::ComputeCost: total and the depth / descriptor sums and counts) before
 // the first and after the last BA call.
 // --pose_step_control: without --pcg, damped pose steps kept per keyframe only if its cost falls (DirectBA::SetPoseStepControl, its defaults)
@@ -196,7 +200,7 @@ int main(int argc, char** argv) {
   bool row_major_creation = false, report_cost = false, pcg_step_control = false, pose_step_control = false, geometry_step_control = false;
   bool intrinsics_step_control = false;
   bool use_pcg = false, intrinsics = false, incremental = false, parallel_ba = false;
-  std::string save_state, load_state, render_dir, residual_dir, covisibility_file;
+  std::string save_state, load_state, render_dir, residual_dir, covisibility_file, observations_file;
   DirectBA::RenderOptions render_options;
   DirectBA::ResidualImageOptions residual_options;
   PreprocessConfig config;
@@ -232,6 +236,7 @@ int main(int argc, char** argv) {
     else if (a == "--residual_dir" && i + 1 < argc) residual_dir = argv[++i];
     else if (a == "--residual_select" && i + 1 < argc && (!strcmp(argv[i + 1], "best") || !strcmp(argv[i + 1], "worst"))) residual_options.worst = !strcmp(argv[++i], "worst");
     else if (a == "--covisibility_file" && i + 1 < argc) covisibility_file = argv[++i];
+    else if (a == "--observations_file" && i + 1 < argc) observations_file = argv[++i];
     else if (a == "--pyramid_level_for_depth" && i + 1 < argc) config.pyramid_level_for_depth = atoi(argv[++i]);
     else if (a == "--pyramid_level_for_color" && i + 1 < argc) config.pyramid_level_for_color = atoi(argv[++i]);
     else if (a == "--median_filter_and_densify_iterations" && i + 1 < argc) config.median_filter_and_densify_iterations = atoi(argv[++i]);
@@ -264,10 +269,11 @@ int main(int argc, char** argv) {
 
   hipStream_t stream = nullptr;
   BAHIP_CHECKED_CALL(bahip_stream_create(&stream));
+  const int kMinObservationCount = 2;
   {
     // B/bad_slam.cc:125-142 with the defaults of B/bad_slam_config.h
     DirectBA ba(/*max_surfel_count*/ 25 * 1000 * 1000, raw_to_float_depth, baseline_fx, cell, /*surfel_merge_dist_factor*/ 0.8f,
-                /*min_observation_count_while_bootstrapping_1*/ 1, /*min_observation_count_while_bootstrapping_2*/ 2, /*min_observation_count*/ 2,
+                /*min_observation_count_while_bootstrapping_1*/ 1, /*min_observation_count_while_bootstrapping_2*/ 2, kMinObservationCount,
                 ba_color_camera, ba_depth_camera, config.pyramid_level_for_color, /*use_depth_residuals*/ true,
                 /*use_descriptor_residuals*/ true, nullptr, SE3f());
     if (spatial_sort_cell >= 0.f) ba.SetSpatialSortCellSize(spatial_sort_cell);
@@ -426,6 +432,29 @@ int main(int argc, char** argv) {
       if (fclose(file) != 0) { fprintf(stderr, "cannot write the observed co-visibility to %s\n", covisibility_file.c_str()); return 1; }
       printf("wrote the observed co-visibility of %zu keyframe(s) to %s: %zu pair(s) share surfels, %zu pair(s) of the lists share none, %zu sharing pair(s) "
              "are in no list\n", K, covisibility_file.c_str(), shared_pairs, list_pairs_without, shared_pairs_unlisted);
+    }
+    if (!observations_file.empty()) {
+      DirectBA::SurfelObservations table;
+      ba.ComputeSurfelObservations(stream, &table);
+      FILE* file = fopen(observations_file.c_str(), "w");
+      if (!file) { fprintf(stderr, "cannot write the observation lists to %s\n", observations_file.c_str()); return 1; }
+      vector<size_t> histogram;
+      size_t below = 0;
+      for (size_t s = 0; s + 1 < table.first.size(); ++s) {
+        const uint32_t begin = table.first[s], count = table.first[s + 1] - begin;
+        if (count >= histogram.size()) histogram.resize(count + 1, 0);
+        ++histogram[count];
+        if (count == 0) continue;
+        if ((int)count < kMinObservationCount) ++below;
+        fprintf(file, "%zu %u", s, count);
+        for (uint32_t e = begin; e < begin + count; ++e) fprintf(file, " %d", table.keyframe_ids[table.keyframes[e]]);
+        fprintf(file, "\n");
+      }
+      if (fclose(file) != 0) { fprintf(stderr, "cannot write the observation lists to %s\n", observations_file.c_str()); return 1; }
+      printf("wrote the observation lists of %zu surfel(s) to %s: %zu pair(s), list lengths", table.first.size() - 1, observations_file.c_str(),
+             table.keyframes.size());
+      for (size_t c = 0; c < histogram.size(); ++c) printf(" %zu:%zu", c, histogram[c]);
+      printf(", %zu observed surfel(s) below min_observation_count %d\n", below, kMinObservationCount);
     }
   }
   bahip_stream_destroy(stream);

@@ -185,6 +185,23 @@ int dba_observed_covisibility(dba_handle* h, void* stream, int capacity_rows, ui
   return 0;
 }
 
+int dba_surfel_observations(dba_handle* h, void* stream, uint32_t capacity_surfels, uint64_t capacity_pairs, int capacity_keyframes, uint32_t* first,
+                            uint16_t* keyframes, float* depth_raw, float* descriptor_raw, int* keyframe_ids, uint64_t* pairs_out, int* num_keyframes_out) {
+  DirectBA::SurfelObservations t;
+  h->ba->ComputeSurfelObservations(static_cast<hipStream_t>(stream), &t, depth_raw != nullptr || descriptor_raw != nullptr);
+  if (pairs_out) *pairs_out = t.keyframes.size();
+  if (num_keyframes_out) *num_keyframes_out = (int)t.keyframe_ids.size();
+  if (capacity_surfels < t.first.size() - 1 || capacity_pairs < t.keyframes.size() || capacity_keyframes < (int)t.keyframe_ids.size() || !first ||
+      !keyframes)
+    return 1;
+  std::copy(t.first.begin(), t.first.end(), first);
+  std::copy(t.keyframes.begin(), t.keyframes.end(), keyframes);
+  if (depth_raw) std::copy(t.depth_raw.begin(), t.depth_raw.end(), depth_raw);
+  if (descriptor_raw) std::copy(t.descriptor_raw.begin(), t.descriptor_raw.end(), descriptor_raw);
+  if (keyframe_ids) std::copy(t.keyframe_ids.begin(), t.keyframe_ids.end(), keyframe_ids);
+  return 0;
+}
+
 int dba_render_surfels(dba_handle* h, void* stream, int keyframe_id, const float view_camera[4], int width, int height,
                        const float global_T_frame[7], const bahip_render_options* options, float* depth, uint32_t* index, float* normal,
                        uint8_t* color, float frame_T_global_out[12]) {

@@ -583,6 +583,45 @@ void DirectBA::ComputeObservedCovisibility(hipStream_t stream, vector<uint32_t>*
   BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
 }
 
+void DirectBA::ComputeSurfelObservations(hipStream_t stream, SurfelObservations* out, bool with_residuals) {
+  BindScene(stream);
+  const bahip_surfels s = SurfelsStruct(/*with_active*/ false);
+  const size_t n = s.surfels_size;
+  out->keyframe_ids.assign(bound_ids_.begin(), bound_ids_.end());
+  out->first.assign(n + 1, 0u);
+  out->keyframes.clear(); out->depth_raw.clear(); out->descriptor_raw.clear();
+  CUDABuffer<uint32_t> first(1, (int)(n + 1));
+  bahip_observations dev{};
+  dev.surfel_first = first.ToCUDA().address();
+  uint64_t pairs = 0;
+  BAHIP_CHECKED_CALL(bahip_surfel_observations(ctx_, &s, &dev, &pairs));   // the count: sizes the planes
+  if (pairs > 0) {
+    // one device block for the planes: the words of the payload first, the 16-bit indices last
+    const size_t payload_words = with_residuals ? 3 * pairs : 0;
+    if (payload_words + (pairs + 1) / 2 > (size_t)0x7fffffff) LOG(FATAL) << "ComputeSurfelObservations: " << pairs << " pairs are too many for one buffer";
+    CUDABuffer<uint32_t> planes(1, (int)(payload_words + (pairs + 1) / 2));
+    uint32_t* base = planes.ToCUDA().address();
+    if (with_residuals) {
+      dev.descriptor_raw = reinterpret_cast<float*>(base);
+      dev.depth_raw = reinterpret_cast<float*>(base) + 2 * pairs;
+    }
+    dev.keyframes = reinterpret_cast<uint16_t*>(base + payload_words);
+    dev.capacity = pairs;
+    uint64_t filled = 0;
+    BAHIP_CHECKED_CALL(bahip_surfel_observations(ctx_, &s, &dev, &filled));
+    if (filled != pairs) LOG(FATAL) << "ComputeSurfelObservations: the pairs changed between the count and the fill";
+    out->keyframes.resize(pairs);
+    BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->keyframes.data(), dev.keyframes, sizeof(uint16_t) * pairs, 2));
+    if (with_residuals) {
+      out->depth_raw.resize(pairs); out->descriptor_raw.resize(2 * pairs);
+      BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->depth_raw.data(), dev.depth_raw, sizeof(float) * pairs, 2));
+      BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->descriptor_raw.data(), dev.descriptor_raw, sizeof(float) * 2 * pairs, 2));
+    }
+  }
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->first.data(), dev.surfel_first, sizeof(uint32_t) * (n + 1), 2));
+  BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
+}
+
 void DirectBA::RenderSurfels(hipStream_t stream, const PinholeCamera4f& view, const SE3f& global_T_frame, const RenderOptions& options,
                              RenderedView* out) {
   BAHIP_CHECKED_CALL(bahip_context_set_stream(ctx_, stream));

@@ -71,6 +71,20 @@ class DirectBA {
   // the values: the co-visibility lists of the keyframes stay the frustum test's.  Surfel sharding with an all-reduce installed: every
   // rank gets the unsharded matrix; keyframe sharding: refused.  Waits for the stream.
   void ComputeObservedCovisibility(hipStream_t stream, vector<uint32_t>* counts, vector<int>* keyframe_ids);
+  // Observation lists (bahip_surfel_observations; DESIGN.md section 3, "Observation lists"): the associated (surfel, keyframe) pairs in
+  // compressed rows by surfel.  first: surfels_size + 1 offsets, first.back() = the number of pairs; keyframes[first[s] .. first[s + 1]):
+  // the keyframes paired with surfel s as indices into keyframe_ids, ascending; keyframe_ids[k] = the id of bound index k (deleted
+  // keyframes are not bound, as with ComputeCost).  with_residuals: entry for entry depth_raw (the pair's raw depth residual) and
+  // descriptor_raw (two words per entry; NaN twice where the pair's colour pixel is not valid); otherwise both stay empty.  A count
+  // call sizes the buffers, a second call fills them.  Surfel sharding: this rank's shard; keyframe sharding: refused.  Waits for the
+  // stream.
+  struct SurfelObservations {
+    vector<uint32_t> first;
+    vector<uint16_t> keyframes;
+    vector<int> keyframe_ids;
+    vector<float> depth_raw, descriptor_raw;
+  };
+  void ComputeSurfelObservations(hipStream_t stream, SurfelObservations* out, bool with_residuals = false);
   // The surfel map seen from a camera (bahip_render_surfels; DESIGN.md section 3, "Rendered views of the map"): per pixel of `view` at
   // pose global_T_frame the nearest surfel's depth, buffer index, normal in the view's frame and colour, row-major.  Empty pixels hold
   // depth 0, index 0xFFFFFFFF, normal (0, 0, 0), colour 0.  Binds nothing; under surfel sharding the view of this rank's shard.  Waits

@@ -877,6 +877,59 @@ class Scene:
         capi.check(self.lib.bahip_debug_covisibility_census(self.ctx.handle, out))
         return [int(v) for v in out]
 
+    OBSERVATION_PLANES = (("keyframes", np.uint16, 1), ("depth_raw", np.float32, 1), ("descriptor_raw", np.float32, 2))
+
+    def surfel_observations(self, size=None, capacity=None, prefill=None, residuals=("depth_raw", "descriptor_raw"), keyframes=True):
+        """The observation lists of the first `size` surfels (default: all) over the bound keyframes (bahip_surfel_observations): a
+        dict with `pairs` (P), `surfel_first` (size + 1 uint32) and the device planes asked for, WHOLE -- `keyframes` (capacity uint16),
+        `depth_raw` (capacity float32), `descriptor_raw` (capacity x 2 float32) -- of which the call fills the first P entries when
+        P <= capacity.  capacity None: a count-only call sizes the planes (capacity = P).  keyframes False: the keyframes plane is
+        passed as NULL (with residuals (): the count-only call).  residuals: the payload planes to ask for.  prefill: a byte value
+        every device plane, surfel_first included, is filled with before the call (tests: a word the call did not write shows; after a
+        refused call the planes are the exception's `arrays` attribute).  Call bind_keyframes first."""
+        s = self.surfels_struct(size)
+        n = int(s.surfels_size)
+        pairs = C.c_uint64(0)
+        first = DeviceBuffer2D(self.ctx, 1, n + 1, np.uint32)
+        bufs = {}
+        try:
+            if capacity is None:
+                out = capi.Observations(first.ptr, None, None, None, 0)
+                capi.check(self.lib.bahip_surfel_observations(self.ctx.handle, C.byref(s), C.byref(out), C.byref(pairs)))
+                capacity = int(pairs.value)
+            cap = int(capacity)
+            wanted = (["keyframes"] if keyframes else []) + list(residuals)
+            for name, dtype, channels in self.OBSERVATION_PLANES:
+                if name in wanted:
+                    bufs[name] = DeviceBuffer2D(self.ctx, 1, max(1, cap) * channels, dtype)
+            if prefill is not None:
+                first.clear(prefill)
+                for b in bufs.values():
+                    b.clear(prefill)
+
+            def planes():
+                self.ctx.synchronize()
+                res = {"surfel_first": first.download()[0].copy()}
+                for name, dtype, channels in self.OBSERVATION_PLANES:
+                    if name in bufs:
+                        a = bufs[name].download()[0, :cap * channels]
+                        res[name] = (a.reshape(cap, channels) if channels > 1 else a).copy()
+                return res
+
+            out = capi.Observations(first.ptr, *[bufs[name].ptr if name in bufs else None for name, _, _ in self.OBSERVATION_PLANES], cap)
+            try:
+                capi.check(self.lib.bahip_surfel_observations(self.ctx.handle, C.byref(s), C.byref(out), C.byref(pairs)))
+            except capi.BackendError as e:
+                e.arrays = planes()
+                raise
+            res = planes()
+            res["pairs"] = int(pairs.value)
+            return res
+        finally:
+            first.free()
+            for b in bufs.values():
+                b.free()
+
     def exact_sum(self, values, mode=0):
         """Exactly rounded binary64 sum of binary32 values through the device's exact accumulators (test hook)."""
         v = np.ascontiguousarray(values, np.float32)

@@ -75,6 +75,15 @@ int dba_compute_surfel_costs(dba_handle* h, void* hip_stream, uint32_t capacity,
  * triangles, the diagonal a keyframe's own pair count.  Returns non-zero, with *num_rows_out set and nothing else written, when
  * capacity_rows < K.  Surfel sharding with an all-reduce installed: the unsharded matrix on every rank; keyframe sharding: refused. */
 int dba_observed_covisibility(dba_handle* h, void* hip_stream, int capacity_rows, uint32_t* counts, int* keyframe_ids, int* num_rows_out);
+/* DirectBA::ComputeSurfelObservations (ours): the observation lists (bahip_surfel_observations) into host arrays -- first
+ * (surfels_size + 1 offsets, the last one the number of pairs P), keyframes (P indices into keyframe_ids, ascending within a list),
+ * depth_raw (P words) and descriptor_raw (2 P words), either or both may be NULL, and keyframe_ids (the id of each bound index, may be
+ * NULL; deleted ids are not bound).  *pairs_out = P and *num_keyframes_out = K are always set.  Returns non-zero, with nothing else
+ * written, when capacity_surfels < surfels_size, capacity_pairs < P, capacity_keyframes < K or first or keyframes is NULL: call with
+ * zero capacities to size the arrays.  Surfel sharding: this rank's shard; keyframe sharding: refused. */
+int dba_surfel_observations(dba_handle* h, void* hip_stream, uint32_t capacity_surfels, uint64_t capacity_pairs, int capacity_keyframes,
+                            uint32_t* first, uint16_t* keyframes, float* depth_raw, float* descriptor_raw, int* keyframe_ids, uint64_t* pairs_out,
+                            int* num_keyframes_out);
 /* DirectBA::RenderSurfels / RenderKeyframeView (ours): the surfel map seen from a camera (bahip_render_surfels), row-major host planes
  * of width * height pixels, any may be NULL: depth, index, normal (3 floats per pixel), color (4 bytes per pixel).  keyframe_id >= 0:
  * the depth camera at that keyframe's pose (view_camera, width, height and global_T_frame are ignored; the planes have the depth

@@ -777,6 +777,49 @@ int bahip_debug_set_covisibility_stages(int stages);
  * non-zero mask, out[1] = atomic adds issued into counts, out[2] = tiles that took the overflow path. */
 int bahip_debug_covisibility_census(bahip_context* ctx, uint64_t out[3]);
 
+/* ---- observation lists (kernels_observations.hip; DESIGN.md section 3, "Observation lists") -----------------------------------------
+ * The sparse object every form of the objective reduces: the associated (surfel, keyframe) pairs themselves, in compressed rows by
+ * surfel.  A pair (s, k), s < surfels_size, k a bound keyframe, is in the table when it is in the pair population of
+ * bahip_evaluate_cost with the depth term on: the production association rule, a finite position, activation flags of surfels and
+ * keyframes ignored -- the matrix A of bahip_observed_covisibility.  All pointers are device memory, borrowed for the call:
+ *   surfel_first    surfels_size + 1 words: surfel_first[0] = 0, surfel_first[s + 1] - surfel_first[s] = the keyframes paired with s,
+ *                   surfel_first[surfels_size] = P, the number of pairs
+ *   keyframes       entries [surfel_first[s], surfel_first[s + 1]): the bound-order indices of s's keyframes, ascending
+ *   depth_raw       entry for entry with keyframes: the pair's raw depth residual, the word bahip_debug_evaluate_pairs reports
+ *   descriptor_raw  two words per entry: r1, r2 of the pair; both 0x7fc00000 where the pair's colour pixel is not valid
+ * A deleted surfel (NaN position) and a surfel no keyframe sees have an empty list.  Nothing depends on the launch shape, the tile
+ * order or the staging; the surfel order moves lists with their surfels.  The kernels exist once, in the exact arithmetic flavour: a
+ * context set to BAHIP_ARITHMETIC_FAST launches the same code and gets the exact flavour's association and residual bits.
+ * Every successful call writes all of surfel_first, stores P (summed in 64 bits) in *pairs and waits for the stream.  The entry planes
+ * are filled only when keyframes is not NULL and P <= capacity (capacity entries per plane, 2 * capacity words of descriptor_raw);
+ * otherwise not a word of them is touched and the call still returns 0: compare *pairs with the capacity, allocate, call again.
+ * keyframes NULL with both payload planes NULL is a count-only call.  Words of a plane beyond P are never touched.  No bound keyframe:
+ * an all-zero surfel_first and P = 0.
+ * The call is refused -- error text, nothing written, nothing launched, the context still usable -- when ctx, surfels, out,
+ * out->surfel_first or pairs is NULL, a payload plane is given without keyframes, no intrinsics are set, 65 536 or more keyframes are
+ * bound, or the context is keyframe-sharded (a rank holds the images of its own keyframes only: use surfel sharding).  A P above the pair
+ * limit (2^32 - 1) fails the call after the count and before a word of surfel_first or of a plane is written.
+ * Surfel sharding: the call covers the shard it is given and exchanges nothing. */
+typedef struct bahip_observations {
+  uint32_t* surfel_first;   /* surfels_size + 1 words, required */
+  uint16_t* keyframes;      /* capacity entries, or NULL: count only */
+  float* depth_raw;         /* capacity entries or NULL */
+  float* descriptor_raw;    /* 2 * capacity entries or NULL */
+  uint64_t capacity;
+} bahip_observations;
+int bahip_surfel_observations(bahip_context* ctx, const bahip_surfels* surfels, const bahip_observations* out, uint64_t* pairs);
+/* Launch shape (test hook; results never depend on it): wavefronts per workgroup 1 .. 8, workgroups >= 1; stage_entries selects the
+ * fill: -1 = direct (each lane stores into its own list), n > 0 = staged (of the entries of a 64-surfel tile, one contiguous range of
+ * every plane, the first n are assembled in LDS per wavefront and written with coalesced stores, the entries beyond are stored at once;
+ * waves * n * bytes per entry (2 + 4 + 8 for the planes asked for) is held to 64 KB by a smaller n), -2 = staged with the default
+ * window; tile_order 0 = buffer order, 1 = the sweeps' heavy-first order when there is one; pair_limit = the largest P a call
+ * accepts (at most 2^32 - 1).  0 (tile_order: -1) = the default. */
+int bahip_debug_set_observations_shape(int waves, int workgroups, int stage_entries, int tile_order, uint64_t pair_limit);
+/* What bahip_surfel_observations launches (scripts/surfel_observations_eval.py takes the stages' times by difference): 1 = the count
+ * alone, 3 = count and scan, 7 or 0 = all (the scan needs the count, the fill needs both).  With a stage missing the words are not the
+ * table; *pairs is still P. */
+int bahip_debug_set_observations_stages(int stages);
+
 /* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
  * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
  * e = 1e-8 + prior(u) as before and t = lambda * M[u] (one binary32 product), the preconditioner divides by ((M[u] + 1e-8) + prior(u))
