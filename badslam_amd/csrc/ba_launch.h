@@ -64,10 +64,32 @@ void launch_activation(hipStream_t stream, const Intrinsics& in, const KfEntry* 
                        uint32_t surfels_size);
 void launch_assign_colors(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s);
 void launch_normals(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s);
-void launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs,
+// The per-tile words of the geometry step's fused route (kernels_surfel.hip: geometry_fused_kernel), written by every tile of a launch:
+// the lanes left to the fix-up launch behind it, and the route the tile took (0 held, 1 position pass run again, 2 deferred lanes).
+struct GeometryFused {
+  unsigned long long* deferred = nullptr;
+  uint8_t* route = nullptr;
+  uint32_t tiles = 0;   // entries of either array: at least geometry_fused_tiles(surfels) for a launch over `surfels`
+  int threshold = 0;    // (filled in by the launcher)
+  bool settled = false; // host side: the step is not among the first kGeometryFusedAfter of its BundleAdjustment call
+};
+// The first geometry steps after a disturbance -- a new keyframe, a loop closure, new poses: what a call of BundleAdjustment follows --
+// move nearly every normal, and a walk whose sums are thrown away costs more than the normals pass it stands for (bench scene: 0.95 ms
+// against 0.73 in the first step, level from the sixth on, 0.52 against 0.61 once settled; profiles/geometry_fused_ab.txt).  Nothing on
+// the device announces a disturbance, so the host goes by the iteration's number in its call: the device-driven loop takes the classic
+// kernel for its first kGeometryFusedAfter iterations and the fused route from then on; the single-step entry points, which do not
+// know their place in a call, keep the classic kernel.  Forced shape 6 takes the fused route everywhere.
+constexpr int kGeometryFusedAfter = 5;
+// true: the step took the fused route (it does where `fused` has the room, descriptor residuals are in use, and either shape 6 is
+// forced or no shape is, the step is settled and there are enough tiles for one wavefront per tile); false: the classic kernels
+bool launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs,
                      int num_kfs, const SurfelsView& s, long long activate_count = -1,
                      const uint32_t* sched = nullptr /* heavy work first (wave_cull.h: scheduled_tile) */,
-                     const int* stop = nullptr /* device word: non-zero = the launch does nothing (device-driven BA loop) */);
+                     const int* stop = nullptr /* device word: non-zero = the launch does nothing (device-driven BA loop) */,
+                     const GeometryFused* fused = nullptr);
+bool geometry_takes_fused_route(uint32_t surfels, bool use_desc, bool settled);
+uint32_t geometry_fused_tiles(uint32_t surfels);   // tiles of the (padded) grid of a geometry step over `surfels`
+void set_geometry_fused(int threshold, int window);   // 0 = default; threshold 1 .. 65, window >= 1 tiles (bahip_debug_set_geometry_fused)
 
 // keyframe sharding (kernels_surfel.hip: geometry_step, kPhase): one phase of the geometry step over this rank's keyframe classes
 int geometry_normals_sums(bool activate);     // sums per class and surfel of the normals pass (cpn) ...
@@ -383,8 +405,10 @@ hipError_t launch_compact(hipStream_t st, const SurfelsView& s, uint32_t* invali
   /* kernels_surfel.hip */                                                                                                                    \
   void launch_activation(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s, uint32_t surfels_size); \
   void launch_normals(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s);                       \
-  void launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs, int num_kfs,              \
-                       const SurfelsView& s, long long activate_count, const uint32_t* sched, const int* stop);                              \
+  bool launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs, int num_kfs,              \
+                       const SurfelsView& s, long long activate_count, const uint32_t* sched, const int* stop, const GeometryFused* fused);   \
+  void set_geometry_fused(int threshold, int window);                                                                                         \
+  bool geometry_takes_fused_route(uint32_t surfels, bool use_desc, bool settled);                                                             \
   void launch_geometry_phase(hipStream_t stream, int phase, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs,          \
                              int num_kfs, const SurfelsView& s, long long activate_count, const ClassPartials& cpn, const ClassPartials& cpp); \
   void launch_activation_hits(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,                \

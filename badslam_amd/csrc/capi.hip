@@ -175,6 +175,29 @@ int ensure_tile_bounds(bahip_context* ctx, uint32_t surfels) {
   return ctx->dev_tile_bounds.reserve(need, need / 4, "the tile bounds of the pose sweep");
 }
 
+// The per-tile buffers of the geometry step's fused route for a step over these surfels (ba_launch.h: GeometryFused), allocated for the
+// cloud's capacity the first time a step would take the route; left empty (the classic kernels) where it would not.  `settled`: the
+// step, or a later step of the call that asks, is past the first kGeometryFusedAfter of its call.
+int geometry_fused_for(bahip_context* ctx, const bahip_surfels* surfels, bool use_desc, bool settled, GeometryFused* out) {
+  *out = GeometryFused{};
+  if (!geometry_takes_fused_route(surfels->surfels_size, use_desc, settled)) return 0;
+  const size_t tiles = geometry_fused_tiles(std::max(surfels->surfels_size, surfels->capacity));
+  if (tiles > ctx->dev_fused_deferred.size() || tiles > ctx->dev_fused_route.size()) {
+    DeviceBuffer<unsigned long long> deferred; DeviceBuffer<uint8_t> route;
+    if (deferred.reserve(tiles, 0, "the deferred lanes of the geometry step") || route.reserve(tiles, 0, "the tile routes of the geometry step"))
+      return fail("allocation of the geometry step's per-tile words failed", __FILE__, __LINE__);
+    // (a launch behind a raised stop word writes neither array: bahip_debug_geometry_fused_stats then reads these zeros, or what the
+    // launch before left)
+    if (hipMemsetAsync(route, 0, tiles, ctx->stream) != hipSuccess || hipMemsetAsync(deferred, 0, sizeof(unsigned long long) * tiles, ctx->stream) != hipSuccess)
+      return fail("clearing the geometry step's per-tile words failed", __FILE__, __LINE__);
+    ctx->dev_fused_deferred = std::move(deferred); ctx->dev_fused_route = std::move(route);
+    ctx->fused_launch_tiles = 0;
+  }
+  out->deferred = ctx->dev_fused_deferred; out->route = ctx->dev_fused_route; out->tiles = (uint32_t)ctx->dev_fused_deferred.size();
+  out->settled = settled;
+  return 0;
+}
+
 int g_tile_order_enabled = bahip_env_int("BAHIP_TILE_ORDER", 1);
 int ensure_tile_schedule(bahip_context* ctx, uint32_t padded_tiles) {
   if (padded_tiles <= ctx->tile_schedule_capacity) return 0;

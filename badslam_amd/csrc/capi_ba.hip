@@ -248,8 +248,11 @@ int bahip_optimize_geometry_iteration(bahip_context* ctx, int use_depth, int use
   if (kf_sharded(ctx)) {
     if (geometry_keyframe_sharded(ctx, use_depth != 0, use_desc != 0, make_view(surfels), -1)) return 1;
   } else {
-    launch_geometry(ctx->stream, use_depth != 0, use_desc != 0, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels), -1,
-                    tile_order_for(ctx, surfels->surfels_size));
+    GeometryFused fused;
+    if (geometry_fused_for(ctx, surfels, use_desc != 0, /*settled*/ false, &fused)) return 1;   // (a single step does not know its place in a call)
+    if (launch_geometry(ctx->stream, use_depth != 0, use_desc != 0, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels), -1,
+                        tile_order_for(ctx, surfels->surfels_size), nullptr, &fused))
+      ctx->fused_launch_tiles = surfel_tiles(surfels->surfels_size);
   }
   timer_end(ctx, 1);
   CHECK_LAUNCH();
@@ -267,8 +270,11 @@ int bahip_update_activation_and_optimize_geometry(bahip_context* ctx, int use_de
   if (kf_sharded(ctx)) {
     if (geometry_keyframe_sharded(ctx, use_depth != 0, use_desc != 0, make_view(surfels), (long long)activation_surfels_size)) return 1;
   } else {
-    launch_geometry(ctx->stream, use_depth != 0, use_desc != 0, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels),
-                    (long long)activation_surfels_size, tile_order_for(ctx, surfels->surfels_size));
+    GeometryFused fused;
+    if (geometry_fused_for(ctx, surfels, use_desc != 0, /*settled*/ false, &fused)) return 1;   // (a single step does not know its place in a call)
+    if (launch_geometry(ctx->stream, use_depth != 0, use_desc != 0, ctx->in, ctx->dev_kfs, ctx->num_kfs, make_view(surfels),
+                        (long long)activation_surfels_size, tile_order_for(ctx, surfels->surfels_size), nullptr, &fused))
+      ctx->fused_launch_tiles = surfel_tiles(surfels->surfels_size);
   }
   timer_end(ctx, 1);
   CHECK_LAUNCH();
@@ -438,6 +444,8 @@ int bahip_alternating_iterations(bahip_context* ctx, const bahip_alternating_opt
   const SurfelsView sv = make_view(surfels);
   if (ensure_tile_bounds(ctx, sv.size)) return 1;
   const bool use_depth = opt->use_depth_residuals != 0, use_desc = opt->use_descriptor_residuals != 0;
+  GeometryFused fused;   // (allocated here, in front of the loop, where later geometry steps of the call take the fused route)
+  if (geometry_fused_for(ctx, surfels, use_desc, opt->max_iterations > kGeometryFusedAfter, &fused)) return 1;
   hipStream_t st = ctx->stream;
   HIP_TRY(hipMemsetAsync(ctx->dev_loop_ctl, 0, sizeof(int) * kLoopWords, st));
   memset(ctx->host_loop_ctl, 0, sizeof(int) * kLoopWords);
@@ -490,8 +498,10 @@ int bahip_alternating_iterations(bahip_context* ctx, const bahip_alternating_opt
         else if (begin_mode == 2) launch_propagate_covisible(st, ctx->dev_kfs, K, csr, csr + K + 1, stop);
       }
       timer_begin(ctx, 1, true);
-      launch_geometry(st, use_depth, use_desc, ctx->in, ctx->dev_kfs, K, sv, opt->activate_in_geometry ? (long long)opt->activation_surfels_size : -1,
-                      tile_order_for(ctx, sv.size), stop);
+      fused.settled = i >= kGeometryFusedAfter;
+      if (launch_geometry(st, use_depth, use_desc, ctx->in, ctx->dev_kfs, K, sv, opt->activate_in_geometry ? (long long)opt->activation_surfels_size : -1,
+                          tile_order_for(ctx, sv.size), stop, &fused))
+        ctx->fused_launch_tiles = surfel_tiles(sv.size);
       timer_end(ctx, 1);
       if (!begun) launch_pose_init_from_keyframes(st, ctx->dev_kfs, K, ctx->dev_work, ctx->dev_Hb, ctx->pinned_work, 0, 1, stop);
       CHECK_LAUNCH();

@@ -137,7 +137,8 @@ int bahip_debug_set_pose_form(int form) {
 }
 
 int bahip_debug_set_launch_shapes(int tile_waves, int pose_parts) {
-  REQUIRE(tile_waves == 0 || tile_waves == 1 || tile_waves == 4 || tile_waves == 5, "tile_waves must be 0 (automatic), 1, 4 or 5 (the geometry step's hybrid shape)");
+  REQUIRE(tile_waves == 0 || tile_waves == 1 || tile_waves == 4 || tile_waves == 5 || tile_waves == 6,
+          "tile_waves must be 0 (automatic), 1, 4, 5 (the geometry step's hybrid shape) or 6 (its fused route)");
   REQUIRE(pose_parts == 0 || pose_parts == 1 || pose_parts == 2 || pose_parts == 4 || pose_parts == 8, "pose_parts must be 0, 1, 2, 4 or 8");
   set_tile_waves(tile_waves);
   set_pose_parts(pose_parts);
@@ -145,6 +146,32 @@ int bahip_debug_set_launch_shapes(int tile_waves, int pose_parts) {
 }
 
 int bahip_debug_geometry_hybrid_launches(long long* launches_out) { if (launches_out) *launches_out = geometry_hybrid_launches(); return 0; }
+
+int bahip_debug_set_geometry_fused(int threshold, int window) {
+  REQUIRE(threshold >= 0 && threshold <= 65, "bahip_debug_set_geometry_fused: threshold must be 0 (default) or 1 .. 65");
+  REQUIRE(window >= 0 && window <= 65536, "bahip_debug_set_geometry_fused: window must be 0 (default) or 1 .. 65536 tiles");
+  set_geometry_fused(threshold, window);
+  return 0;
+}
+
+int bahip_debug_geometry_fused_stats(bahip_context* ctx, long long out[4]) {
+  REQUIRE(ctx != nullptr && out != nullptr, "bahip_debug_geometry_fused_stats: NULL argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  const size_t tiles = ctx->fused_launch_tiles;
+  if (tiles == 0) return 0;
+  std::vector<unsigned long long> deferred(tiles);
+  std::vector<uint8_t> route(tiles);
+  HIP_TRY(hipMemcpyAsync(deferred.data(), ctx->dev_fused_deferred, sizeof(unsigned long long) * tiles, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(route.data(), ctx->dev_fused_route, tiles, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (size_t t = 0; t < tiles; ++t) {
+    const int taken = route[t];
+    REQUIRE(taken <= 2 && (taken == 2) == (deferred[t] != 0), "bahip_debug_geometry_fused_stats: a tile's route and its deferred lanes disagree");
+    out[taken] += 1;
+    out[3] += __builtin_popcountll(deferred[t]);
+  }
+  return 0;
+}
 
 int bahip_debug_jacobian(bahip_context* ctx, int kind, const float* in, int n_in, float* out, int n_out) {
   REQUIRE(kind >= 0 && kind <= 4 && n_in > 0 && n_in <= 16 && n_out > 0 && n_out <= 8, "bahip_debug_jacobian: bad arguments");

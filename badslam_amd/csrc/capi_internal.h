@@ -163,6 +163,12 @@ struct bahip_context {
   int phases_since_schedule = 0;       // the schedule is rebuilt when the grid changes and every kSchedulePhases-th phase
   uint32_t tile_order_unavailable_tiles = 0;   // a grid the order kernel cannot schedule (too many runs): no census for it again
   bool tile_order_unavailable_for(uint32_t padded_tiles) const { return padded_tiles != 0 && tile_order_unavailable_tiles == padded_tiles; }
+  // the geometry step's fused route (ba_launch.h: GeometryFused): per tile the word of deferred lanes and the route byte, sized with the
+  // surfel capacity when the route is first taken; fused_launch_tiles: tiles of the last launch ENQUEUED on it (bahip_debug_geometry_fused_stats;
+  // a launch behind a raised stop word writes nothing, the arrays then hold what the launch before it left)
+  DeviceBuffer<unsigned long long> dev_fused_deferred;
+  DeviceBuffer<uint8_t> dev_fused_route;
+  uint32_t fused_launch_tiles = 0;
   DeviceBuffer<int> dev_loop_ctl;  // device-driven BA loop (bahip_alternating_iterations): kLoopWords control words ...
   PinnedBuffer<int> host_loop_ctl{kHostVisible};   // ... their mapped host copy, followed by kLoopLogSlots words of per-round log
   int rounds_hint_table = 1, rounds_hint_frame = 1;   // Gauss-Newton rounds the previous pose phase took (keyframe table / single frame)
@@ -276,6 +282,8 @@ void timer_begin(bahip_context* ctx, int stage, bool first, int units = 1);
 void timer_end(bahip_context* ctx, int stage);
 inline bool kf_sharded(const bahip_context* ctx) { return ctx->kf_world > 1; }
 int ensure_tile_bounds(bahip_context* ctx, uint32_t surfels);
+int geometry_fused_for(bahip_context* ctx, const bahip_surfels* surfels, bool use_desc, bool settled, GeometryFused* out);
+inline uint32_t surfel_tiles(uint32_t surfels) { return (surfels + 63u) / 64u; }
 extern int g_tile_order_enabled;
 int ensure_tile_schedule(bahip_context* ctx, uint32_t padded_tiles);
 const uint32_t* tile_order_for(const bahip_context* ctx, uint32_t surfels);

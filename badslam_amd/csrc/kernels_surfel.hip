@@ -68,9 +68,14 @@ enum ParkSlot {
   kParkNormal = 20,   // 3: the surfel's normal, read once per candidate (the association test) and by the final update
   kParkSlots = 23
 };
+// The fused kernel (geometry_fused_kernel) keeps the tile's bounding sphere in SGPRs and parks the sums of the normals instead: per class
+// x, y, z, count where the classic kernel parks the sphere and the count over kActive keyframes behind it, then their five totals.
+enum FusedSlot { kFusedNormalSums = kParkBounds, kFusedActiveSum = kParkSlots, kFusedNormalTotals = kParkSlots + 1, kFusedSlots = kParkSlots + 6 };
+constexpr int fused_sum_slot(int q) { return q < 4 ? kFusedNormalSums + q : kFusedActiveSum; }
 constexpr int kMaskChunks = 4;   // (normals_pass: the candidate masks the position pass replays)
 // the block and the candidate masks of BAHIP_GEOMETRY_WAVES workgroups per SIMD fit the compute unit's 160 KiB
 static_assert((kParkSlots * 64 * 4 + kMaxSumClasses * kMaskChunks * 8) * 4 * BAHIP_GEOMETRY_WAVES <= 160 * 1024, "parked state: LDS per workgroup");
+static_assert(kFusedSlots * 64 * 4 + kMaxSumClasses * kMaskChunks * 8 <= 160 * 1024 / (4 * BAHIP_GEOMETRY_WAVES), "fused kernel: LDS per workgroup");
 typedef __attribute__((address_space(3))) float ParkedFloat;
 __device__ __forceinline__ ParkedFloat* park_lane(float* block) { return (ParkedFloat*)block + (threadIdx.x & 63); }
 // In front of a group of reads: the compiler must take the column for memory it knows nothing about, or it forwards the stored values to
@@ -178,6 +183,41 @@ __device__ __forceinline__ void tile_sums_parked(float (&tot)[kCount], ParkedFlo
   park_reopen(park);
 #pragma unroll
   for (int q = 0; q < kCount; ++q) tot[q] = park_get(park, slot + q);
+}
+
+// One walk for both sets of sums (geometry_fused_kernel): tile_sums_parked<8> for the position pass's sums, and in the same class loops
+// tile_sums<1, kNormals> for the sums of the normals, whose per-class accumulators the visit keeps in the block (fused_sum_slot) -- the
+// additions and their order are those of the two separate walks.
+template <int kNormals, typename Visit>
+__device__ __forceinline__ void tile_sums_fused(float (&tot)[8], float (&ntot)[kNormals], ParkedFloat*& park, Visit visit, int classes) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) park_put(park, kParkTotals + q, 0.f);
+#pragma unroll
+  for (int q = 0; q < kNormals; ++q) park_put(park, kFusedNormalTotals + q, 0.f);
+#pragma nounroll
+  for (int c = 0; c < classes; ++c) {
+    float acc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+#pragma unroll
+    for (int q = 0; q < kNormals; ++q) park_put(park, fused_sum_slot(q), 0.f);
+    visit(acc, c);
+    park_reopen(park);
+    float t[8], n[kNormals];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) t[q] = park_get(park, kParkTotals + q);
+#pragma unroll
+    for (int q = 0; q < kNormals; ++q) n[q] = park_get(park, kFusedNormalTotals + q) + park_get(park, fused_sum_slot(q));
+#pragma unroll
+    for (int q = 0; q < 8; ++q) park_put(park, kParkTotals + q, t[q] + acc[q]);
+#pragma unroll
+    for (int q = 0; q < kNormals; ++q) park_put(park, kFusedNormalTotals + q, n[q]);
+  }
+  park_reopen(park);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) tot[q] = park_get(park, kParkTotals + q);
+#pragma unroll
+  for (int q = 0; q < kNormals; ++q) ntot[q] = park_get(park, kFusedNormalTotals + q);
 }
 
 // B/kernel_surfel_activation.cu:38-94
@@ -307,17 +347,31 @@ normals_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, Surf
 // kPark (the one-wavefront kernel only): what the candidate loops of the joint solve's position pass do not touch lives in `park_block`
 // (ParkSlot) instead of registers -- parked after the early return and the normals pass, so nothing before them depends on the block;
 // the values, the operations on them and their order are those of kPark == false.
-template <bool kUseDepth, bool kUseDesc, int kWaves, bool kActivate, int kPhase, bool kPark = false>
+//
+// kFused (geometry_fused_kernel; parked, joint or descriptor-only solve): ONE walk over the candidates with the old normal.  The walk is
+// the position pass, and from the same associations it also takes the sums of the normals pass (tile_sums_fused).  The new normal is a
+// 10-bit-per-component word: where it equals the stored word, the position pass of the classic kernel would have computed, bit for bit,
+// what the walk computed, so such a surfel is solved from the walk's sums.  Per tile, with c = the live lanes whose word changed:
+//   c == 0          every lane solves and updates (kFusedHeld);
+//   c >= threshold  the position pass is run again with the new normals, replaying the walk's candidate masks (kFusedRerun);
+//   otherwise       the unchanged lanes solve and update, the changed ones write their normal only and are left to
+//                   geometry_fixup_kernel, which finds them in fused.deferred[tile] (kFusedDeferred).
+// kPhase 4 (geometry_fixup_kernel): the position pass and the solve alone, for the surfel whose index the lane gets in place of `tile`
+// (kInvalidIndex: none), with the normal and the activation flag as stored and every non-inactive keyframe tested.
+enum FusedRoute : uint8_t { kFusedHeld = 0, kFusedRerun = 1, kFusedDeferred = 2 };
+template <bool kUseDepth, bool kUseDesc, int kWaves, bool kActivate, int kPhase, bool kPark = false, bool kFused = false>
 __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView& s,
                                               uint32_t activate_count, float* lds, const ClassPartials& cpn, const ClassPartials& cpp,
                                               uint32_t tile /* workgroup-uniform (kWaves > 1) or wave-uniform */, unsigned long long* replay_masks,
-                                              float* park_block = nullptr) {
+                                              float* park_block = nullptr, const GeometryFused& fused = GeometryFused{}) {
   static_assert(!kPark || (kWaves == 1 && kPhase == 0), "state is parked by the one-wavefront kernel of the whole step only");
+  static_assert(!kFused || (kPark && kUseDesc), "the fused walk is the parked position pass of the joint / descriptor-only solve");
+  static_assert(kPhase != 4 || !kActivate, "the fix-up takes the flags as the fused kernel left them");
   constexpr int kNormalsMode = kPhase == 1 ? kSumsProduce : kPhase == 2 ? kSumsConsume : kSumsFused;
   constexpr int kPositionMode = kPhase == 2 ? kSumsProduce : kPhase == 3 ? kSumsConsume : kSumsFused;
   const int lane = threadIdx.x & 63;
   const bool writer = kWaves == 1 || (threadIdx.x >> 6) == 0;
-  const uint32_t i = tile * kSurfelBlock + lane;
+  const uint32_t i = kPhase == 4 ? tile : tile * kSurfelBlock + lane;
   const bool in_range = i < s.size;
   const uint32_t ii = in_range ? i : 0;
   // (phase 3: the flags were decided by phase 2)
@@ -328,31 +382,42 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
   const WaveBounds wb = wave_bounds(gp, live && position_valid(gp));
   if (wb.r < 0.f) {   // workgroup-uniform (all wavefronts of the tile hold the same surfels): nothing a keyframe could see
     if (decide && writer && kPhase != 1) s.active[ii] = s.active[ii] & (uint8_t)~kSurfelActiveFlag;   // (deleted surfels: never active)
+    if constexpr (kFused) {
+      if (lane == 0) { fused.deferred[tile] = 0; fused.route[tile] = kFusedHeld; }
+    }
     return;
   }
   // one wavefront per tile, the whole step in one launch: the position pass replays the candidate masks of the normals pass
   constexpr bool kReplayMasks = kWaves == 1 && kPhase == 0;   // (measured: geometry sweep 0.749 -> 0.731 ms at the bench size, profiles/r5_ab_*.txt)
   unsigned long long* masks = kReplayMasks ? replay_masks : nullptr;   // kMaxSumClasses * kMaskChunks words of LDS per wavefront, owned by the kernel
-  if (kPhase != 3) normals_pass<kWaves, kActivate, kNormalsMode>(in, kfs, num_kfs, wb, s, ii, &live, decide, gp, &gn, lds, cpn, in_range, masks);
+  if (kPhase != 3 && kPhase != 4 && !kFused) normals_pass<kWaves, kActivate, kNormalsMode>(in, kfs, num_kfs, wb, s, ii, &live, decide, gp, &gn, lds, cpn, in_range, masks);
   if (kPhase == 1) return;
 
   // (the depth-only solve runs at 59 VGPRs: nothing to park)
   constexpr bool kParked = kPark && kUseDesc;
   ParkedFloat* park = nullptr;
+  WaveBounds wbs = wb;   // (kFused) wave_all leaves the same value in every lane: the sphere lives in SGPRs, not in the block
   if constexpr (kParked) {
     park = park_lane(park_block);
-    park_put(park, kParkBounds + 0, wb.cx); park_put(park, kParkBounds + 1, wb.cy);
-    park_put(park, kParkBounds + 2, wb.cz); park_put(park, kParkBounds + 3, wb.r);
+    if constexpr (kFused) {
+      wbs.cx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wb.cx))); wbs.cy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wb.cy)));
+      wbs.cz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wb.cz))); wbs.r = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wb.r)));
+    } else {
+      park_put(park, kParkBounds + 0, wb.cx); park_put(park, kParkBounds + 1, wb.cy);
+      park_put(park, kParkBounds + 2, wb.cz); park_put(park, kParkBounds + 3, wb.r);
+    }
   }
   auto cand = [&](int k) {
     float f[12];
     int32_t activation;
     load_candidate(kfs[k].pose.F, &kfs[k].activation, f, &activation);
     if constexpr (kParked) {
-      park_reopen(park);
-      WaveBounds b;
-      b.cx = park_get(park, kParkBounds + 0); b.cy = park_get(park, kParkBounds + 1);
-      b.cz = park_get(park, kParkBounds + 2); b.r = park_get(park, kParkBounds + 3);
+      WaveBounds b = wbs;
+      if constexpr (!kFused) {
+        park_reopen(park);
+        b.cx = park_get(park, kParkBounds + 0); b.cy = park_get(park, kParkBounds + 1);
+        b.cz = park_get(park, kParkBounds + 2); b.r = park_get(park, kParkBounds + 3);
+      }
       // the norms of the frustum planes depend on the intrinsics alone: left to the compiler they are computed once per launch and held
       // in six VGPRs across the candidate loops, for a test that runs once per 64 keyframes beyond the replayed masks
       // (an opaque copy of what the test reads makes them part of the test again)
@@ -432,6 +497,14 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
     }
   };
   float tot[8];   // a0 a1 a2 a3 a5 a6 a7 a8 of B/kernel_opt_geometry.cu:119-230 (a4 = H12 is exactly 0)
+  // (kFused) the lane's surfel index built again behind a candidate loop, the lane count started from a copy of the tile's first index
+  // that the compiler cannot see through: left to it, the index or the lane number is computed once in front of the walk and spilled
+  [[maybe_unused]] auto rebuilt_index = [&]() {
+    uint32_t first = tile * kSurfelBlock;
+    asm volatile("" : "+s"(first));
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, first));
+  };
+  [[maybe_unused]] bool walking = true;   // (kFused) wave-uniform: the one walk, as against the position pass run again behind it
   auto position_visit = [&](float (&acc)[8], int cls) {
     float &a0 = acc[0], &a1 = acc[1], &a2 = acc[2], &a3 = acc[3], &a5 = acc[4], &a6 = acc[5], &a7 = acc[6], &a8 = acc[7];
     // Two-stage candidate loop for the pixel word (wave_cull.h: for_each_candidate_pipelined): candidate k + 1 is projected and its
@@ -461,6 +534,17 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
       gathers_arrived(pix, dw);   // measured: -9 % on this pass (the footprint gathers of pairs that fail the association cost more than the second round trip saves here)
 #endif
       if (!associated) return;
+      if constexpr (kFused) {
+        if (walking) {   // wave-uniform.  What normals_pass adds for this association, to the class's sums in the block
+          const Vec3 g = mul33(kfs[k].pose.GR, unpack_normal8(r.normal_bits));
+          park_reopen(park);
+          const float nx = park_get(park, fused_sum_slot(0)), ny = park_get(park, fused_sum_slot(1)), nz = park_get(park, fused_sum_slot(2));
+          const float nc = park_get(park, fused_sum_slot(3));
+          park_put(park, fused_sum_slot(0), nx + g.x); park_put(park, fused_sum_slot(1), ny + g.y); park_put(park, fused_sum_slot(2), nz + g.z);
+          park_put(park, fused_sum_slot(3), nc + 1.f);
+          if (kActivate) park_put(park, fused_sum_slot(4), park_get(park, fused_sum_slot(4)) + ((kfs[k].activation == BAHIP_KF_ACTIVE) ? 1.f : 0.f));
+        }
+      }
       if (kUseDepth) {
         const float inv_std = assoc_inv_std(in, r);
         const float jac = -inv_std;
@@ -495,13 +579,51 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
     };
     if (kWaves == 1)
       for_each_candidate_pipelined<StartedPair>(num_kfs, cand, start_pair, finish_pair, in.sum_classes, cls, masks ? masks + cls * kMaskChunks : nullptr,
-                                                masks ? kMaskChunks : 0, masks != nullptr);
+                                                masks ? kMaskChunks : 0, kFused ? !walking : masks != nullptr);   // (the fused walk records the masks)
     else
       for_each_candidate_cached(num_kfs, cand, [&](int k) { finish_pair(k, start_pair(k)); }, in.sum_classes, cls,
                                 masks ? masks + cls * kMaskChunks : nullptr, masks ? kMaskChunks : 0, masks != nullptr);
   };
-  if constexpr (kParked) tile_sums_parked<8>(tot, park, kParkTotals, position_visit, in.sum_classes);
-  else tile_sums<kWaves, 8, kPositionMode>(tot, lds, position_visit, in.sum_classes, cpp, ii, in_range);
+  if constexpr (kFused) {
+    constexpr int kNormals = kActivate ? 5 : 4;   // (normals_pass: x, y, z, count [, count over kActive keyframes])
+    float ntot[kNormals];
+    tile_sums_fused<kNormals>(tot, ntot, park, position_visit, in.sum_classes);
+    // what normals_pass does behind its sums: the activation flag, then the normal -- written only where its word changes
+    const uint32_t iu = rebuilt_index();
+    if (kActivate && iu < s.size && iu < activate_count) {
+      live = live && ntot[kNormals - 1] >= 1.f;
+      s.active[iu] = (s.active[iu] & (uint8_t)~kSurfelActiveFlag) | (live ? kSurfelActiveFlag : 0);
+    }
+    uint32_t* words = reinterpret_cast<uint32_t*>(s.row(kSurfelNormal));
+    const uint32_t iw = iu < s.size ? iu : 0;   // (a lane past the end computes on surfel 0, as everywhere)
+    uint32_t word = words[iw];
+    bool changed = false;
+    if (live) {
+      if (ntot[3] >= 1) {
+        const uint32_t packed = pack_normal10((1.f / ntot[3]) * mk3(ntot[0], ntot[1], ntot[2]));
+        changed = packed != word;
+        if (changed) { words[iu] = packed; word = packed; }
+      }
+    }
+    const unsigned long long changed_lanes = __ballot(changed);
+    const int c = __popcll(changed_lanes);
+    const uint8_t route = c == 0 ? kFusedHeld : c >= fused.threshold ? kFusedRerun : kFusedDeferred;   // wave-uniform
+    if ((iu & 63u) == 0) { fused.deferred[tile] = route == kFusedDeferred ? changed_lanes : 0ull; fused.route[tile] = route; }
+    if (route == kFusedRerun) {   // the classic position pass: new normals, hence new tangent points; the masks of the walk
+      const Vec3 gn_new = unpack_normal10(word);
+      const TangentPoints tn = surfel_tangent_points(gp, gn_new, s.row(kSurfelRadiusSquared)[iw]);
+      park_put(park, kParkTangents + 0, tn.q1.x); park_put(park, kParkTangents + 1, tn.q1.y); park_put(park, kParkTangents + 2, tn.q1.z);
+      park_put(park, kParkTangents + 3, tn.q2.x); park_put(park, kParkTangents + 4, tn.q2.y); park_put(park, kParkTangents + 5, tn.q2.z);
+      park_put(park, kParkNormal + 0, gn_new.x); park_put(park, kParkNormal + 1, gn_new.y); park_put(park, kParkNormal + 2, gn_new.z);
+      walking = false;
+      tile_sums_parked<8>(tot, park, kParkTotals, position_visit, in.sum_classes);
+    }
+    if (route == kFusedDeferred && changed) return;
+  } else if constexpr (kParked) {
+    tile_sums_parked<8>(tot, park, kParkTotals, position_visit, in.sum_classes);
+  } else {
+    tile_sums<kWaves, 8, kPositionMode>(tot, lds, position_visit, in.sum_classes, cpp, ii, in_range);
+  }
   if (kPhase == 2 || !live || !writer) return;
   const float a0 = tot[0], a1 = tot[1], a2 = tot[2], a3 = tot[3], a5 = tot[4], a6 = tot[5], a7 = tot[6], a8 = tot[7];
 
@@ -522,7 +644,7 @@ __device__ __forceinline__ void geometry_step(const Intrinsics& in, const KfEntr
   // what the updates read: (kParked) the index rebuilt from the tile and the lane number, not held in a register across the passes
   uint32_t iu = i;
   if constexpr (kParked) {
-    iu = tile * kSurfelBlock + __lane_id();
+    iu = kFused ? rebuilt_index() : tile * kSurfelBlock + __lane_id();
     park_reopen(park);
   }
   Vec3 gn_back;
@@ -557,6 +679,60 @@ geometry_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, Sur
 #ifdef BAHIP_RECORD_GEOMETRY_TIMELINE
   if (threadIdx.x == 0 && blockIdx.x < 65536) { g_geometry_timeline[blockIdx.x][0] = t0; g_geometry_timeline[blockIdx.x][1] = wall_clock64(); }
 #endif
+}
+
+// The one-wavefront kernel with ONE candidate walk per class (geometry_step: kFused), followed in the stream by geometry_fixup_kernel.
+// Every tile of the grid stores its route and its word of deferred lanes, the tiles that return early included: no shared counter.
+template <bool kUseDepth, bool kUseDesc, bool kActivate>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BAHIP_GEOMETRY_WAVES)))
+geometry_fused_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s, uint32_t activate_count,
+                      const uint32_t* __restrict__ sched, const int* __restrict__ stop, GeometryFused fused) {
+  __shared__ unsigned long long candidate_masks[kMaxSumClasses * kMaskChunks];
+  __shared__ float parked[kFusedSlots * 64];
+  if (stop && load_global(stop) != 0) return;
+  uint32_t tile;
+  if (!scheduled_tile(blockIdx.x, gridDim.x - (sched ? kHeavySlots : 0u), sched, &tile)) return;
+  geometry_step<kUseDepth, kUseDesc, 1, kActivate, 0, true, true>(in, kfs, num_kfs, s, activate_count, nullptr, ClassPartials{}, ClassPartials{}, tile,
+                                                                  candidate_masks, parked, fused);
+}
+
+// The surfels the fused kernel left behind (geometry_step: kFusedDeferred): a workgroup takes a window of `window` consecutive tiles --
+// buffer order is Morton order, so a window is spatially compact -- gathers the set bits of its deferred words 64 at a time, one surfel
+// per lane, and runs the classic position pass and the solve on them with the normals the fused kernel wrote (geometry_step: kPhase 4),
+// a keyframe class per wavefront (the four-wavefront shape: a window's few groups are the whole launch, so the longest one bounds it; the
+// one-wavefront form also needs scratch at 128 VGPRs).  A surfel's sums are its own, per class in ascending keyframe
+// order, and the cull is conservative: the result does not depend on which surfels share a wavefront.
+// gridDim.y workgroups share a window: each forms every group (a scan of the window's words) and works on every gridDim.y-th one, so
+// that a window with several groups -- the first iterations after a change, when many normals still move -- is not one serial chain.
+template <bool kUseDepth>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+geometry_fixup_kernel(Intrinsics in, const KfEntry* __restrict__ kfs, int num_kfs, SurfelsView s, const unsigned long long* __restrict__ deferred,
+                      uint32_t tiles, uint32_t window, const int* __restrict__ stop) {
+  __shared__ float lds[kMaxSumClasses * 8 * 64];
+  __shared__ uint32_t list[128];   // surfel indices: the group being filled, and what the last word put beyond it
+  if (stop && load_global(stop) != 0) return;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t end = min(blockIdx.x * window + window, tiles);
+  uint32_t next = blockIdx.x * window, filled = 0;   // workgroup-uniform; every wavefront writes the same list
+  for (uint32_t group = 0;; ++group) {
+    while (next < end && filled < 64) {
+      const unsigned long long word = load_global(deferred + next);
+      if ((word >> lane) & 1ull) list[filled + __popcll(word & ((1ull << lane) - 1ull))] = next * kSurfelBlock + lane;
+      filled += (uint32_t)__popcll(word);
+      ++next;
+    }
+    if (filled == 0) break;
+    __syncthreads();
+    const uint32_t taken = min(filled, 64u);
+    const uint32_t index = lane < taken ? list[lane] : kInvalidIndex;
+    const uint32_t beyond = list[64 + lane];
+    __syncthreads();
+    list[lane] = beyond;
+    filled -= taken;
+    __syncthreads();   // (the next group's entries go behind the ones just moved)
+    if (group % gridDim.y == blockIdx.y)
+      geometry_step<kUseDepth, true, 4, false, 4>(in, kfs, num_kfs, s, 0u, lds, ClassPartials{}, ClassPartials{}, index, nullptr);
+  }
 }
 
 // The HYBRID shape (round 6), for clouds whose tiles do not fill the chip several times over (a shard of a multi-GPU run): workgroups
@@ -656,6 +832,7 @@ void set_tile_waves(int waves) { g_forced_tile_waves = waves; }
 static int tile_waves(uint32_t surfels) {
   const int forced = g_forced_tile_waves;
   if (forced == 1 || forced == 4) return forced;
+  if (forced == 6) return 1;   // (the fused route is a one-wavefront shape; where it does not exist -- depth only -- the classic one)
   // measured on MI355X (geometry pass, ms): 11.7 k tiles: 0.90 with one wavefront per tile, 0.95 with four;
   // 5.9 k tiles: 0.65 vs 0.51
   return grid_for(surfels) >= 8192 ? 1 : 4;
@@ -689,12 +866,49 @@ static void launch_geometry_hybrid(hipStream_t stream, bool use_depth, bool use_
   else hipLaunchKernelGGL((geometry_hybrid_kernel<false, true, kActivate>), grid, block, 0, stream, in, kfs, num_kfs, s, activate_count, sched, padded, stop);
 }
 
+// The fused route (geometry_fused_kernel + geometry_fixup_kernel): threshold of changed lanes from which a tile runs its position pass
+// again in the kernel (1: every changed tile, nothing is deferred and no fix-up is launched; 65: never), tiles per fix-up window.
+// bahip_debug_set_geometry_fused; defaults chosen on the bench scene (profiles/geometry_fused_ab.txt).
+constexpr int kFusedThresholdDefault = 16, kFusedWindowDefault = 64;
+constexpr int kFixupShare = 4;   // workgroups per fix-up window (geometry_fixup_kernel)
+static int g_fused_threshold = kFusedThresholdDefault, g_fused_window = kFusedWindowDefault;
+void set_geometry_fused(int threshold, int window) {
+  g_fused_threshold = threshold ? threshold : kFusedThresholdDefault;
+  g_fused_window = window ? window : kFusedWindowDefault;
+}
+// Does a geometry step over `surfels` surfels take the fused route, given the buffers?  Descriptor residuals in use, and either shape 6
+// is forced, or nothing is forced, the step is a settled one (ba_launch.h: kGeometryFusedAfter) and there are enough tiles to fill
+// the chip with one wavefront per tile -- where the classic one-wavefront kernel runs.
+bool geometry_takes_fused_route(uint32_t surfels, bool use_desc, bool settled) {
+  return use_desc && surfels != 0 && (g_forced_tile_waves == 6 || (g_forced_tile_waves == 0 && settled && grid_for(surfels) >= 8192));
+}
+
+template <bool kActivate>
+static void launch_geometry_fused(hipStream_t stream, bool use_depth, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,
+                                  uint32_t activate_count, const uint32_t* sched, const int* stop, GeometryFused fused) {
+  fused.threshold = g_fused_threshold;
+  const dim3 grid(sched_positions(grid_for(s.size), sched));
+  if (use_depth) hipLaunchKernelGGL((geometry_fused_kernel<true, true, kActivate>), grid, dim3(64), 0, stream, in, kfs, num_kfs, s, activate_count, sched, stop, fused);
+  else hipLaunchKernelGGL((geometry_fused_kernel<false, true, kActivate>), grid, dim3(64), 0, stream, in, kfs, num_kfs, s, activate_count, sched, stop, fused);
+  if (fused.threshold <= 1) return;   // every changed tile ran again in the kernel
+  const uint32_t tiles = (s.size + kSurfelBlock - 1) / kSurfelBlock, window = (uint32_t)g_fused_window;
+  const dim3 windows((tiles + window - 1) / window, kFixupShare);
+  if (use_depth) hipLaunchKernelGGL((geometry_fixup_kernel<true>), windows, dim3(256), 0, stream, in, kfs, num_kfs, s, fused.deferred, tiles, window, stop);
+  else hipLaunchKernelGGL((geometry_fixup_kernel<false>), windows, dim3(256), 0, stream, in, kfs, num_kfs, s, fused.deferred, tiles, window, stop);
+}
+
 // activate_count < 0: the activation flags are taken as they are; >= 0: surfels [0, activate_count) are (re)activated first.
 // `sched`: the schedule of a grid of grid_for(s.size) tiles (wave_cull.h: scheduled_tile), or NULL.
-void launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs,
-                     int num_kfs, const SurfelsView& s, long long activate_count, const uint32_t* sched, const int* stop) {
-  if (s.size == 0) return;
+// `fused`: the per-tile buffers of the fused route, or NULL (the classic kernels); true = the fused route was taken.
+bool launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs,
+                     int num_kfs, const SurfelsView& s, long long activate_count, const uint32_t* sched, const int* stop, const GeometryFused* fused) {
+  if (s.size == 0) return false;
   const uint32_t n = activate_count < 0 ? 0u : (uint32_t)activate_count;
+  if (fused && fused->deferred && fused->route && fused->tiles >= grid_for(s.size) && geometry_takes_fused_route(s.size, use_desc, fused->settled)) {
+    if (activate_count < 0) launch_geometry_fused<false>(stream, use_depth, in, kfs, num_kfs, s, n, sched, stop, *fused);
+    else launch_geometry_fused<true>(stream, use_depth, in, kfs, num_kfs, s, n, sched, stop, *fused);
+    return true;
+  }
   // few tiles and a schedule (its heavy list): the hybrid shape; BAHIP_TILE_WAVES / bahip_debug_set_launch_shapes: 5 forces it (where a
   // schedule exists), 1 / 4 the uniform shapes
   const bool hybrid = sched != nullptr && (g_forced_tile_waves == 5 || (g_forced_tile_waves == 0 && grid_for(s.size) < 8192));
@@ -709,6 +923,7 @@ void launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const In
     if (activate_count < 0) launch_geometry_shape<4, false>(stream, use_depth, use_desc, in, kfs, num_kfs, s, n, sched, stop);
     else launch_geometry_shape<4, true>(stream, use_depth, use_desc, in, kfs, num_kfs, s, n, sched, stop);
   }
+  return false;
 }
 
 // ---- keyframe sharding ------------------------------------------------------------------------------------------------
@@ -848,9 +1063,10 @@ void launch_activation(hipStream_t stream, const Intrinsics& in, const KfEntry* 
 void launch_normals(hipStream_t stream, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s) {
   BAHIP_PICK(in, launch_normals(stream, in, kfs, num_kfs, s));
 }
-void launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,
-                     long long activate_count, const uint32_t* sched, const int* stop) {
-  BAHIP_PICK(in, launch_geometry(stream, use_depth, use_desc, in, kfs, num_kfs, s, activate_count, sched, stop));
+bool launch_geometry(hipStream_t stream, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs, int num_kfs, const SurfelsView& s,
+                     long long activate_count, const uint32_t* sched, const int* stop, const GeometryFused* fused) {
+  return in.fast_math ? fast::launch_geometry(stream, use_depth, use_desc, in, kfs, num_kfs, s, activate_count, sched, stop, fused)
+                      : exact::launch_geometry(stream, use_depth, use_desc, in, kfs, num_kfs, s, activate_count, sched, stop, fused);
 }
 void launch_geometry_phase(hipStream_t stream, int phase, bool use_depth, bool use_desc, const Intrinsics& in, const KfEntry* kfs, int num_kfs,
                            const SurfelsView& s, long long activate_count, const ClassPartials& cpn, const ClassPartials& cpp) {
@@ -864,6 +1080,9 @@ void launch_activation_hits(hipStream_t stream, const Intrinsics& in, const KfEn
   BAHIP_PICK(in, launch_activation_hits(stream, in, kfs, num_kfs, s, surfels_size, kf_rank, kf_world, hits));
 }
 void set_tile_waves(int waves) { exact::set_tile_waves(waves); fast::set_tile_waves(waves); }
+void set_geometry_fused(int threshold, int window) { exact::set_geometry_fused(threshold, window); fast::set_geometry_fused(threshold, window); }
+bool geometry_takes_fused_route(uint32_t surfels, bool use_desc, bool settled) { return exact::geometry_takes_fused_route(surfels, use_desc, settled); }
+uint32_t geometry_fused_tiles(uint32_t surfels) { return xcd_padded_tiles((surfels + kSurfelBlock - 1) / kSurfelBlock); }
 long long geometry_hybrid_launches() { return exact::geometry_hybrid_launches() + fast::geometry_hybrid_launches(); }
 }  // namespace bahip
 

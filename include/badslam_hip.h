@@ -1045,6 +1045,17 @@ int bahip_debug_exact_sum(bahip_context* ctx, const float* values, size_t count,
  * bahip_debug_geometry_hybrid_launches: how many geometry steps have run in that shape so far. */
 int bahip_debug_set_launch_shapes(int tile_waves, int pose_parts);
 int bahip_debug_geometry_hybrid_launches(long long* launches_out);
+/* tile_waves = 6: the geometry step's FUSED route at any size (the default from the sixth iteration of a bahip_alternating_iterations
+ * call on, where the one-wavefront shape runs: no forcing, >= 8192 tiles, descriptor residuals in use -- the first five iterations of a
+ * call, in which nearly every normal moves, and the single-step entry points keep the classic kernel, as does the depth-only step): one walk over a tile's candidates with the old
+ * normals gives the sums of the normals AND of the position pass; a surfel whose packed normal does not change is solved from them.
+ * Per tile, with c changed live surfels: c = 0 held; c >= threshold: the position pass runs again in the kernel; otherwise the changed
+ * surfels are left to a fix-up launch, which takes them from windows of `window` consecutive tiles, 64 at a time.  Same bits as the
+ * classic shapes.  threshold 1 .. 65 (1: nothing is deferred, no fix-up launch; 65: everything is), window >= 1; 0 = the default.
+ * bahip_debug_geometry_fused_stats: out = tiles held, tiles run again, tiles with deferred surfels, deferred surfels, of the context's
+ * last geometry step that took the route (zeros if none did); synchronises. */
+int bahip_debug_set_geometry_fused(int threshold, int window);
+int bahip_debug_geometry_fused_stats(bahip_context* ctx, long long out[4]);
 /* Form of the pose sweep, process-wide; results are bit-identical for all of them.  0 = chosen from the sizes (default);
  * 1 = one wavefront per surfel tile, tile totals added to the normal equations with global 64-bit integer atomics (the only form
  * for shards and for more work items than fit the table); 2 = persistent workgroups, one per compute unit, that keep the normal

@@ -32,7 +32,10 @@ def counters_of(d, sub):
 
 
 POSE_KERNELS = ("pose_accumulate_lds_kernel", "pose_accumulate_kernel")
-GEOMETRY_KERNELS = ("geometry_kernel",)
+# one launch per geometry step: the classic kernel, or the fused one -- whose fix-up launch (when there is one) follows it in the stream
+# and belongs to the same step
+GEOMETRY_KERNELS = ("geometry_kernel", "geometry_fused_kernel")
+GEOMETRY_FOLLOWERS = ("geometry_fixup_kernel",)
 
 
 def bench_line(path):
@@ -44,13 +47,30 @@ def bench_line(path):
         return None
 
 
-def window_rows(rows, kernels, before, count):
+def kernel_of(row):
+    return short(row.get("Kernel_Name", row.get("Name", "")))
+
+
+def window_rows(rows, kernels, before, count, followers=()):
     """The rows (one per dispatch and counter / one per dispatch of a kernel trace) of `kernels` in dispatch order, cut to the
-    dispatches [before, before + count) of those kernels: the timed region of the bench run that produced them."""
-    mine = [r for r in rows if short(r.get("Kernel_Name", r.get("Name", ""))).startswith(kernels)]
+    dispatches [before, before + count) of those kernels: the timed region of the bench run that produced them.  Dispatches of
+    `followers` between a kept dispatch and the next one of `kernels` come with it and are not counted."""
+    mine = [r for r in rows if kernel_of(r).startswith(kernels)]
     ids = sorted({int(r["Dispatch_Id"]) for r in mine})
     keep = set(ids[before:before + count])
-    return [r for r in mine if int(r["Dispatch_Id"]) in keep], len(keep)
+    sel = [r for r in mine if int(r["Dispatch_Id"]) in keep]
+    if followers and keep:
+        end = ids[before + count] if before + count < len(ids) else float("inf")
+        sel += [r for r in rows if kernel_of(r).startswith(followers) and min(keep) < int(r["Dispatch_Id"]) < end]
+    return sel, len(keep)
+
+
+def kernels_in(rows):
+    """kernel name (up to its template arguments) -> dispatches among `rows`"""
+    seen = collections.defaultdict(set)
+    for r in rows:
+        seen[kernel_of(r).split("<")[0]].add(int(r["Dispatch_Id"]))
+    return {name: len(ids) for name, ids in sorted(seen.items())}
 
 
 def timed_window(d):
@@ -75,9 +95,9 @@ def timed_window(d):
         for path in glob.glob(os.path.join(d, sub, "**", "*kernel_trace.csv"), recursive=True):
             with open(path) as f:
                 trace += list(csv.DictReader(f))
-        for name, kernels, before, count in (("pose", POSE_KERNELS, w["pose_dispatches_before"], w["pose_dispatches_timed"]),
-                                             ("geometry", GEOMETRY_KERNELS, w["geometry_dispatches_before"], w["geometry_dispatches_timed"])):
-            sel, n = window_rows(rows, kernels, before, count)
+        for name, kernels, before, count, followers in (("pose", POSE_KERNELS, w["pose_dispatches_before"], w["pose_dispatches_timed"], ()),
+                                                        ("geometry", GEOMETRY_KERNELS, w["geometry_dispatches_before"], w["geometry_dispatches_timed"], GEOMETRY_FOLLOWERS)):
+            sel, n = window_rows(rows, kernels, before, count, followers)
             e = out.setdefault(name, {"passes": {}})
             sums = collections.defaultdict(float)
             for r in sel:
@@ -85,9 +105,10 @@ def timed_window(d):
             e["passes"][sub] = {"dispatches": n, "iterations": w["iterations_timed"], "sums": dict(sums),
                                 "launches_with_work": w["pose_launches_with_work_timed"] if name == "pose" else n,
                                 "keyframes_visited": w["keyframes_visited_timed"] if name == "pose" else None, "surfels": w["surfels"]}
-            tsel, _ = window_rows(trace, kernels, before, count)
+            tsel, _ = window_rows(trace, kernels, before, count, followers)
             if tsel:   # kernel time of the same dispatches in this (counter) pass
                 e["passes"][sub]["duration_ns"] = sum(float(r["End_Timestamp"]) - float(r["Start_Timestamp"]) for r in tsel)
+                e["passes"][sub]["kernels"] = kernels_in(tsel)
     # kernel time of the same dispatches in the stats pass (its own bench line)
     stats_line = bench_line(os.path.join(d, "bench_stats.json"))
     if stats_line and "launch_window" in stats_line:
@@ -96,12 +117,12 @@ def timed_window(d):
         for path in glob.glob(os.path.join(d, "stats", "**", "*kernel_trace.csv"), recursive=True):
             with open(path) as f:
                 rows += list(csv.DictReader(f))
-        for name, kernels, before, count in (("pose", POSE_KERNELS, w["pose_dispatches_before"], w["pose_dispatches_timed"]),
-                                             ("geometry", GEOMETRY_KERNELS, w["geometry_dispatches_before"], w["geometry_dispatches_timed"])):
-            sel, n = window_rows(rows, kernels, before, count)
+        for name, kernels, before, count, followers in (("pose", POSE_KERNELS, w["pose_dispatches_before"], w["pose_dispatches_timed"], ()),
+                                                        ("geometry", GEOMETRY_KERNELS, w["geometry_dispatches_before"], w["geometry_dispatches_timed"], GEOMETRY_FOLLOWERS)):
+            sel, n = window_rows(rows, kernels, before, count, followers)
             if sel:
                 e = out.setdefault(name, {"passes": {}})
-                e["passes"]["stats"] = {"dispatches": n, "iterations": w["iterations_timed"],
+                e["passes"]["stats"] = {"dispatches": n, "iterations": w["iterations_timed"], "kernels": kernels_in(sel),
                                         "duration_ns": sum(float(r["End_Timestamp"]) - float(r["Start_Timestamp"]) for r in sel)}
     return out, stats_line
 
