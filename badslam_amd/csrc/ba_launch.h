@@ -697,6 +697,27 @@ void launch_observations_count(hipStream_t stream, const Intrinsics& in, const K
 void launch_observations_fill(hipStream_t stream, const Intrinsics& in, const KfEntry* frames, int num_kfs, const SurfelsView& s,
                               const uint32_t* sched, const ObsShape& shape, const uint32_t* first, const ObsPlanes& planes);
 
+// kernels_redundancy.hip: keyframe redundancy, per keyframe its surfels by the number of other keyframes that observe them (exists
+// once: the exact flavour's association under either flavour).  hist: device, num_kfs rows of `pitch` words, `bins` of them written;
+// launch shape: `waves` wavefronts per workgroup, at most `workgroups` of them, `list_capacity` (keyframe, mask) entries per wavefront
+// in LDS before a tile is traversed a second time.  A wavefront's LDS: list_capacity + 64 entries of 12 bytes (the list, and one
+// (bin, mask) entry per bin present in the tile).
+constexpr int kRedundancyMaxBins = 64, kRedundancyMaxWaves = 8, kRedundancyMaxListCapacity = 448, kRedundancyEntryBytes = 12;   // 48 KB at most
+constexpr int kRedundancyDefaultWaves = 8, kRedundancyWorkgroupsPerUnit = 4, kRedundancyDefaultListCapacity = 128;
+struct RedundancyShape {
+  int waves, workgroups, list_capacity;
+};
+void launch_redundancy_clear(hipStream_t stream, uint32_t* hist, int num_kfs, int bins, uint32_t pitch);
+// hist[k][min(o, bins - 1)] += the surfels of s associated with keyframe k that o other keyframes are associated with; attribute false:
+// the traversal, the counts and the lists only, no atomic (timing);
+// census: NULL or three zeroed words ((tile, keyframe) entries, atomic adds issued, tiles traversed a second time)
+void launch_redundancy_sweep(hipStream_t stream, const Intrinsics& in, const KfEntry* frames, int num_kfs, const SurfelsView& s,
+                             const uint32_t* sched, const RedundancyShape& shape, bool attribute, int bins, uint32_t* hist, uint32_t pitch,
+                             unsigned long long* census);
+// the compact num_kfs x bins words as int64 (what the ranks of a surfel partition sum), and the summed words into pitched rows
+void launch_redundancy_widen(hipStream_t stream, const uint32_t* compact, uint32_t words, long long* wide);
+void launch_redundancy_narrow(hipStream_t stream, const long long* wide, int num_kfs, int bins, uint32_t* hist, uint32_t pitch);
+
 // kernels_ingest.hip: a frame brought to the BA's pyramid level (exists once: integer rules and one correctly rounded division, the same
 // under either flavour).  The callers have checked sizes and pitches; the downscale's blocks are at most kIngestMaxBlock on a side.
 constexpr int kIngestMaxBlock = 9, kIngestMaxLevels = 3;

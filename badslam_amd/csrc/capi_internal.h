@@ -12,6 +12,7 @@
 //   capi_residual_image.hip a frame's residuals per pixel (bahip_frame_residual_image)
 //   capi_covisibility.hip the surfels every pair of keyframes shares (bahip_observed_covisibility)
 //   capi_observations.hip the keyframes paired with each surfel, in compressed rows (bahip_surfel_observations)
+//   capi_redundancy.hip per keyframe its surfels by the number of other observers (bahip_keyframe_observer_histogram)
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
 //   capi_geometry_trial.hip step control of the geometry phase of the alternating scheme
@@ -237,6 +238,10 @@ struct bahip_context {
   DeviceBuffer<uint32_t> obs_counts;
   DeviceBuffer<unsigned long long> obs_total;
   DeviceBuffer<void> obs_scan_temp;
+  // bahip_keyframe_observer_histogram: the three census words of the last call, and, with a transport installed, the words of a shard
+  // ([K x bins int64 | K x bins uint32]) that are summed over the ranks (kernels_redundancy.hip)
+  DeviceBuffer<unsigned long long> redundancy_census;
+  DeviceBuffer<long long> redundancy_stage;
   // dealing the lifecycle under surfel sharding (bahip_context_set_lifecycle_dealing): the switch, and the surfel partition of the
   // whole-cloud phase in progress -- set by bahip_gather_surfel_shards, cleared by bahip_extract_surfel_shard (deal_world 1: none) --
   // with the gathered cloud it belongs to: lifecycle calls on any other buffer are not dealt

@@ -57,6 +57,12 @@ def _load():
         if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_surfel_observations"):
             L.dba_surfel_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int] + [C.c_void_p] * 4 + \
                 [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_keyframe_redundancy"):
+            L.dba_keyframe_redundancy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.dba_find_redundant_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                       C.POINTER(C.c_int)]
+            L.dba_cull_redundant_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dba_surfel_count.restype = C.c_uint32
         L.dba_surfel_count.argtypes = [C.c_void_p]
         L.dba_surfels_size.restype = C.c_uint32
@@ -303,6 +309,39 @@ class DirectBA:
         if residuals:
             out.update(depth_raw=depth, descriptor_raw=desc)
         return out
+
+    def keyframe_redundancy(self, bins=16):
+        """DirectBA::ComputeKeyframeRedundancy: (ids, hist) -- the ids of the existing keyframes in order and the (K, bins) uint32
+        table: hist[i, j] = the surfels paired with keyframe ids[i] that min(o, bins - 1) = j other keyframes are paired with too.
+        Under surfel sharding with an all-reduce installed every rank gets the unsharded table."""
+        cap = max(1, self.keyframe_count())
+        hist = np.zeros(cap * bins, np.uint32)
+        ids = (C.c_int * cap)()
+        rows = C.c_int()
+        assert self.L.dba_keyframe_redundancy(self.h, self.stream, int(bins), cap, hist.ctypes.data, ids, C.byref(rows)) == 0
+        K = rows.value
+        return [int(v) for v in ids[:K]], hist[:K * bins].reshape(K, bins).copy()
+
+    def find_redundant_keyframes(self, min_other_observers, min_fraction, bins=16):
+        """DirectBA::FindRedundantKeyframes: the ids of the keyframes of whose surfels at least min_fraction have min_other_observers
+        other observers or more, most redundant first, ties to the lower id.  Deletes nothing."""
+        cap = max(1, self.keyframe_count())
+        ids = (C.c_int * cap)()
+        n = C.c_int()
+        assert self.L.dba_find_redundant_keyframes(self.h, self.stream, int(min_other_observers), float(min_fraction), int(bins), cap, ids,
+                                                   C.byref(n)) == 0
+        return [int(v) for v in ids[:n.value]]
+
+    def cull_redundant_keyframes(self, min_other_observers, min_fraction, max_deletions, protect_newest=0):
+        """DirectBA::CullRedundantKeyframes: deletes, one by one and with the table computed again after each deletion, the most
+        redundant qualifying keyframe that is neither the first existing one nor among the protect_newest last ones; returns the
+        deleted ids in order.  Nothing calls it unless asked."""
+        cap = max(1, self.keyframe_count())
+        ids = (C.c_int * cap)()
+        n = C.c_int()
+        assert self.L.dba_cull_redundant_keyframes(self.h, self.stream, int(min_other_observers), float(min_fraction), int(max_deletions),
+                                                   int(protect_newest), cap, ids, C.byref(n)) == 0
+        return [int(v) for v in ids[:n.value]]
 
     def render_surfels(self, keyframe=None, view_camera=None, width=None, height=None, global_T_frame=None, options=None):
         """DirectBA::RenderKeyframeView (keyframe: an id -- the depth camera at that keyframe's pose) or DirectBA::RenderSurfels (the

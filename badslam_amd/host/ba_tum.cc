@@ -15,6 +15,7 @@
 //          [--pcg_step_control] [--pose_step_control] [--geometry_step_control] [--intrinsics_step_control]
 //          [--render_dir DIR [--render_mode point|disc] [--render_max_radius N] [--render_radius_factor F]]
 //          [--residual_dir DIR [--residual_select best|worst]] [--covisibility_file F] [--observations_file F]
+//          [--redundancy_file F [--redundancy_bins B]] [--cull_redundant_keyframes M,FRACTION]
 //          [--pyramid_level_for_depth N] [--pyramid_level_for_color N] [--median_filter_and_densify_iterations N]
 //
 // --pyramid_level_for_depth N / --pyramid_level_for_color N (0 .. 3): the BA runs on depth / colour images of 2^-N the dataset's size, with
@@ -42,6 +43,12 @@
 // surfel the keyframes the association rule pairs it with) as a text file, one line per surfel with at least one pair: surfel_index count
 // id ... (the keyframe ids ascending), and one summary line on the output: the number of pairs, the histogram of the list lengths and
 // the surfels whose list is shorter than min_observation_count (what the next deletion pass would remove).  Nothing acts on the lists.
+// --redundancy_file F [--redundancy_bins B]: after the observation lists, the keyframe redundancy of the final state
+// (DirectBA::ComputeKeyframeRedundancy with B bins, 1 .. 64, default 16) as a text file, one line per keyframe in id order: id total
+// and the B words -- word j the keyframe's surfels that min(o, B - 1) = j other keyframes observe as well, total their sum.
+// --cull_redundant_keyframes M,FRACTION: before the final BA call (not with --incremental), DirectBA::CullRedundantKeyframes deletes,
+// one by one, the keyframes of whose surfels at least FRACTION have M (0 .. 15) or more other observers -- never the first keyframe nor
+// the newest -- and the deleted ids are printed.  Off unless given: nothing else deletes a keyframe by this rule.
 // --report_cost: prints the value of the BA objective (DirectBA::ComputeCost: total and the depth / descriptor sums and counts) before
 // the first and after the last BA call.
 // --pose_step_control: without --pcg, damped pose steps kept per keyframe only if its cost falls (DirectBA::SetPoseStepControl, its defaults)
@@ -200,7 +207,9 @@ int main(int argc, char** argv) {
   bool row_major_creation = false, report_cost = false, pcg_step_control = false, pose_step_control = false, geometry_step_control = false;
   bool intrinsics_step_control = false;
   bool use_pcg = false, intrinsics = false, incremental = false, parallel_ba = false;
-  std::string save_state, load_state, render_dir, residual_dir, covisibility_file, observations_file;
+  std::string save_state, load_state, render_dir, residual_dir, covisibility_file, observations_file, redundancy_file;
+  int redundancy_bins = 16, cull_min_other_observers = -1;
+  double cull_min_fraction = 0.0;
   DirectBA::RenderOptions render_options;
   DirectBA::ResidualImageOptions residual_options;
   PreprocessConfig config;
@@ -237,6 +246,17 @@ int main(int argc, char** argv) {
     else if (a == "--residual_select" && i + 1 < argc && (!strcmp(argv[i + 1], "best") || !strcmp(argv[i + 1], "worst"))) residual_options.worst = !strcmp(argv[++i], "worst");
     else if (a == "--covisibility_file" && i + 1 < argc) covisibility_file = argv[++i];
     else if (a == "--observations_file" && i + 1 < argc) observations_file = argv[++i];
+    else if (a == "--redundancy_file" && i + 1 < argc) redundancy_file = argv[++i];
+    else if (a == "--redundancy_bins" && i + 1 < argc) redundancy_bins = atoi(argv[++i]);
+    else if (a == "--cull_redundant_keyframes" && i + 1 < argc) {
+      char* rest = nullptr;
+      cull_min_other_observers = (int)strtol(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest != ',' || cull_min_other_observers < 0 || cull_min_other_observers > 15) {
+        fprintf(stderr, "--cull_redundant_keyframes takes M,FRACTION with M in 0 .. 15\n");
+        return 2;
+      }
+      cull_min_fraction = atof(rest + 1);
+    }
     else if (a == "--pyramid_level_for_depth" && i + 1 < argc) config.pyramid_level_for_depth = atoi(argv[++i]);
     else if (a == "--pyramid_level_for_color" && i + 1 < argc) config.pyramid_level_for_color = atoi(argv[++i]);
     else if (a == "--median_filter_and_densify_iterations" && i + 1 < argc) config.median_filter_and_densify_iterations = atoi(argv[++i]);
@@ -244,6 +264,14 @@ int main(int argc, char** argv) {
   }
   if (intrinsics_step_control && (!intrinsics || use_pcg)) {
     fprintf(stderr, "--intrinsics_step_control needs --intrinsics and the alternating scheme (no --pcg)\n");
+    return 2;
+  }
+  if (redundancy_bins < 1 || redundancy_bins > 64) {
+    fprintf(stderr, "--redundancy_bins takes 1 .. 64\n");
+    return 2;
+  }
+  if (cull_min_other_observers >= 0 && incremental) {
+    fprintf(stderr, "--cull_redundant_keyframes runs before the final BA call of the batch mode: not with --incremental or --parallel_ba\n");
     return 2;
   }
   if (render_options.max_radius_px < 0 || render_options.max_radius_px > 16 || !(render_options.radius_factor > 0.f)) {
@@ -343,7 +371,18 @@ int main(int argc, char** argv) {
       printf("%zu keyframes\n", ba.keyframes().size());
       RememberKeyframePoses(&ba, &original_keyframe_T_global);   // B/bad_slam.cc:1230 (before the BA that moves them)
       print_cost("before the first BA call");
+      auto cull = [&]() {
+        vector<int> deleted;
+        ba.CullRedundantKeyframes(stream, cull_min_other_observers, cull_min_fraction, /*max_deletions*/ (int)ba.keyframes().size(), /*protect_newest*/ 1,
+                                  &deleted);
+        printf("culled %zu redundant keyframe(s) (at least %g of the surfels with %d or more other observers):", deleted.size(), cull_min_fraction,
+               cull_min_other_observers);
+        for (int id : deleted) printf(" %d", id);
+        printf("\n");
+      };
+      if (cull_min_other_observers >= 0 && iterations <= 0) cull();
       for (int i = 0; i < iterations; ++i) {
+        if (cull_min_other_observers >= 0 && i == iterations - 1) cull();
         int done = 0;
         bool converged = false;
         ba.BundleAdjustment(stream, /*optimize_depth_intrinsics*/ intrinsics, /*optimize_color_intrinsics*/ intrinsics, /*do_surfel_updates*/ true,
@@ -455,6 +494,22 @@ int main(int argc, char** argv) {
              table.keyframes.size());
       for (size_t c = 0; c < histogram.size(); ++c) printf(" %zu:%zu", c, histogram[c]);
       printf(", %zu observed surfel(s) below min_observation_count %d\n", below, kMinObservationCount);
+    }
+    if (!redundancy_file.empty()) {
+      vector<uint32_t> hist;
+      vector<int> ids;
+      ba.ComputeKeyframeRedundancy(stream, redundancy_bins, &hist, &ids);
+      FILE* file = fopen(redundancy_file.c_str(), "w");
+      if (!file) { fprintf(stderr, "cannot write the keyframe redundancy to %s\n", redundancy_file.c_str()); return 1; }
+      for (size_t i = 0; i < ids.size(); ++i) {
+        unsigned long long total = 0;
+        for (int j = 0; j < redundancy_bins; ++j) total += hist[i * (size_t)redundancy_bins + j];
+        fprintf(file, "%d %llu", ids[i], total);
+        for (int j = 0; j < redundancy_bins; ++j) fprintf(file, " %u", hist[i * (size_t)redundancy_bins + j]);
+        fprintf(file, "\n");
+      }
+      if (fclose(file) != 0) { fprintf(stderr, "cannot write the keyframe redundancy to %s\n", redundancy_file.c_str()); return 1; }
+      printf("wrote the keyframe redundancy of %zu keyframe(s) (%d bins) to %s\n", ids.size(), redundancy_bins, redundancy_file.c_str());
     }
   }
   bahip_stream_destroy(stream);

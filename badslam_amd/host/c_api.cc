@@ -202,6 +202,43 @@ int dba_surfel_observations(dba_handle* h, void* stream, uint32_t capacity_surfe
   return 0;
 }
 
+int dba_keyframe_redundancy(dba_handle* h, void* stream, int bins, int capacity_rows, uint32_t* hist, int* keyframe_ids, int* num_rows_out) {
+  int rows = 0;
+  for (int id = 0; id < (int)h->ba->keyframes().size(); ++id)
+    if (h->ba->keyframes()[id]) ++rows;
+  if (num_rows_out) *num_rows_out = rows;
+  if (capacity_rows < rows || !hist || bins < 1 || bins > 64) return 1;
+  std::vector<uint32_t> words;
+  std::vector<int> ids;
+  h->ba->ComputeKeyframeRedundancy(static_cast<hipStream_t>(stream), bins, &words, &ids);
+  std::copy(words.begin(), words.end(), hist);
+  if (keyframe_ids) std::copy(ids.begin(), ids.end(), keyframe_ids);
+  return 0;
+}
+
+int dba_find_redundant_keyframes(dba_handle* h, void* stream, int min_other_observers, double min_fraction, int bins, int capacity, int* keyframe_ids,
+                                 int* num_out) {
+  if (bins < 1 || bins > 64 || min_other_observers < 0 || min_other_observers > bins - 1 || !keyframe_ids || !num_out) return 1;
+  std::vector<int> ids;
+  h->ba->FindRedundantKeyframes(static_cast<hipStream_t>(stream), min_other_observers, min_fraction, &ids, bins);
+  *num_out = (int)ids.size();
+  if (capacity < (int)ids.size()) return 1;
+  std::copy(ids.begin(), ids.end(), keyframe_ids);
+  return 0;
+}
+
+int dba_cull_redundant_keyframes(dba_handle* h, void* stream, int min_other_observers, double min_fraction, int max_deletions, int protect_newest,
+                                 int capacity, int* deleted_ids, int* num_deleted_out) {
+  // (the default table of FindRedundantKeyframes has 16 bins)
+  if (min_other_observers < 0 || min_other_observers > 15 || !deleted_ids || !num_deleted_out) return 1;
+  std::vector<int> ids;
+  h->ba->CullRedundantKeyframes(static_cast<hipStream_t>(stream), min_other_observers, min_fraction, std::min(max_deletions, capacity), protect_newest,
+                                &ids);
+  *num_deleted_out = (int)ids.size();
+  std::copy(ids.begin(), ids.end(), deleted_ids);
+  return 0;
+}
+
 int dba_render_surfels(dba_handle* h, void* stream, int keyframe_id, const float view_camera[4], int width, int height,
                        const float global_T_frame[7], const bahip_render_options* options, float* depth, uint32_t* index, float* normal,
                        uint8_t* color, float frame_T_global_out[12]) {

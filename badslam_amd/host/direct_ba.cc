@@ -622,6 +622,69 @@ void DirectBA::ComputeSurfelObservations(hipStream_t stream, SurfelObservations*
   BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
 }
 
+void DirectBA::ComputeKeyframeRedundancy(hipStream_t stream, int bins, vector<uint32_t>* hist, vector<int>* keyframe_ids) {
+  CHECK(bins >= 1 && bins <= 64) << "ComputeKeyframeRedundancy: bins outside 1 .. 64";
+  BindScene(stream);
+  const bahip_surfels s = SurfelsStruct(/*with_active*/ false);
+  const size_t K = bound_ids_.size();
+  hist->assign(K * (size_t)bins, 0u);
+  if (keyframe_ids) keyframe_ids->assign(bound_ids_.begin(), bound_ids_.end());
+  if (K == 0) return;
+  CUDABuffer<uint32_t> words(1, (int)(K * (size_t)bins));
+  uint32_t* dev = words.ToCUDA().address();
+  BAHIP_CHECKED_CALL(bahip_keyframe_observer_histogram(ctx_, &s, bins, dev, bins));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, hist->data(), dev, sizeof(uint32_t) * K * (size_t)bins, 2));
+  BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
+}
+
+void DirectBA::FindRedundantKeyframes(hipStream_t stream, int min_other_observers, double min_fraction, vector<int>* keyframe_ids, int bins) {
+  CHECK(min_other_observers >= 0 && min_other_observers <= bins - 1) << "FindRedundantKeyframes: min_other_observers outside 0 .. bins - 1";
+  vector<uint32_t> hist;
+  vector<int> ids;
+  ComputeKeyframeRedundancy(stream, bins, &hist, &ids);
+  struct Row {
+    int id;
+    uint64_t covered, total;
+  };
+  vector<Row> rows;
+  for (size_t i = 0; i < ids.size(); ++i) {
+    uint64_t total = 0, covered = 0;
+    for (int j = 0; j < bins; ++j) {
+      total += hist[i * (size_t)bins + j];
+      if (j >= min_other_observers) covered += hist[i * (size_t)bins + j];
+    }
+    if (total > 0 && (double)covered >= min_fraction * (double)total) rows.push_back(Row{ids[i], covered, total});
+  }
+  // covered and total are below 2^32 each (a row's words count distinct surfels): the cross products are exact in 64 bits
+  std::stable_sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) {
+    const uint64_t ab = a.covered * b.total, ba = b.covered * a.total;
+    return ab != ba ? ab > ba : a.id < b.id;
+  });
+  keyframe_ids->clear();
+  for (const Row& r : rows) keyframe_ids->push_back(r.id);
+}
+
+void DirectBA::CullRedundantKeyframes(hipStream_t stream, int min_other_observers, double min_fraction, int max_deletions, int protect_newest,
+                                      vector<int>* deleted_ids) {
+  deleted_ids->clear();
+  while ((int)deleted_ids->size() < max_deletions) {
+    vector<int> candidates;
+    FindRedundantKeyframes(stream, min_other_observers, min_fraction, &candidates);
+    // (FindRedundantKeyframes bound the scene: bound_ids_ holds the existing keyframes in order)
+    const int existing = (int)bound_ids_.size();
+    int chosen = -1;
+    for (int id : candidates) {
+      const int position = (int)(std::find(bound_ids_.begin(), bound_ids_.end(), id) - bound_ids_.begin());
+      if (position == 0 || position >= existing - std::max(0, protect_newest)) continue;
+      chosen = id;
+      break;
+    }
+    if (chosen < 0) break;
+    DeleteKeyframe(chosen);
+    deleted_ids->push_back(chosen);
+  }
+}
+
 void DirectBA::RenderSurfels(hipStream_t stream, const PinholeCamera4f& view, const SE3f& global_T_frame, const RenderOptions& options,
                              RenderedView* out) {
   BAHIP_CHECKED_CALL(bahip_context_set_stream(ctx_, stream));

@@ -85,6 +85,23 @@ class DirectBA {
     vector<float> depth_raw, descriptor_raw;
   };
   void ComputeSurfelObservations(hipStream_t stream, SurfelObservations* out, bool with_residuals = false);
+  // Keyframe redundancy (bahip_keyframe_observer_histogram; DESIGN.md section 3, "Keyframe redundancy"): hist[i * bins + j] = the
+  // surfels the association rule pairs with the i-th existing keyframe that min(o, bins - 1) = j OTHER keyframes are paired with as
+  // well, K x bins row-major, 1 <= bins <= 64; keyframe_ids[i] = the id of row i (deleted keyframes are not rows, as with
+  // ComputeObservedCovisibility).  Surfel sharding with an all-reduce installed: every rank gets the unsharded table; keyframe
+  // sharding: refused.  Waits for the stream.
+  void ComputeKeyframeRedundancy(hipStream_t stream, int bins, vector<uint32_t>* hist, vector<int>* keyframe_ids);
+  // The keyframes the map does without: with total = a row's sum and covered = its sum over the bins j >= min_other_observers
+  // (<= bins - 1), a keyframe qualifies when total > 0 and (double)covered >= min_fraction * (double)total.  keyframe_ids: the ids of
+  // the qualifying keyframes, most redundant first (covered / total compared by the 64-bit cross products covered_a * total_b and
+  // covered_b * total_a), ties to the lower id.  Deletes nothing.
+  void FindRedundantKeyframes(hipStream_t stream, int min_other_observers, double min_fraction, vector<int>* keyframe_ids, int bins = 16);
+  // Greedy culling by that rule: in each round the table is computed again (a deletion lowers the observer counts of the deleted
+  // keyframe's surfels) and DeleteKeyframe is called on the first keyframe of FindRedundantKeyframes that is neither the first existing
+  // keyframe nor among the protect_newest last ones; stops when none qualifies or max_deletions keyframes are deleted.  deleted_ids: the
+  // ids in the order of deletion.  Nothing in the library calls it.
+  void CullRedundantKeyframes(hipStream_t stream, int min_other_observers, double min_fraction, int max_deletions, int protect_newest,
+                              vector<int>* deleted_ids);
   // The surfel map seen from a camera (bahip_render_surfels; DESIGN.md section 3, "Rendered views of the map"): per pixel of `view` at
   // pose global_T_frame the nearest surfel's depth, buffer index, normal in the view's frame and colour, row-major.  Empty pixels hold
   // depth 0, index 0xFFFFFFFF, normal (0, 0, 0), colour 0.  Binds nothing; under surfel sharding the view of this rank's shard.  Waits

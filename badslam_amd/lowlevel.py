@@ -877,6 +877,36 @@ class Scene:
         capi.check(self.lib.bahip_debug_covisibility_census(self.ctx.handle, out))
         return [int(v) for v in out]
 
+    def keyframe_observer_histogram(self, bins, prefill=None, size=None, pitch=None):
+        """Per bound keyframe its surfels by the number of other keyframes that observe them (bahip_keyframe_observer_histogram) over
+        the first `size` surfels (default: all): a (K, bins) uint32 array in bound order, column j the surfels with min(o, bins - 1) = j
+        other observers.  pitch: words per row of the device buffer (default bins; the call refuses less) -- the result is then the
+        whole (K, pitch) buffer; prefill: a byte value the buffer is filled with before the call (tests: a word the call did not write
+        shows; after a refused call the buffer is the exception's `arrays` attribute).  Call bind_keyframes first."""
+        K = len(self.keyframes)
+        p = int(bins) if pitch is None else int(pitch)
+        buf = DeviceBuffer2D(self.ctx, 1, max(1, K * max(p, 1)), np.uint32)
+        try:
+            buf.clear(0 if prefill is None else prefill)
+            s = self.surfels_struct(size)
+            try:
+                capi.check(self.lib.bahip_keyframe_observer_histogram(self.ctx.handle, C.byref(s), int(bins), buf.ptr, p))
+            except capi.BackendError as e:
+                self.ctx.synchronize()
+                e.arrays = buf.download()[0].copy()
+                raise
+            self.ctx.synchronize()
+            return buf.download()[0, :K * p].reshape(K, p).copy()
+        finally:
+            buf.free()
+
+    def redundancy_census(self):
+        """Of the last keyframe_observer_histogram: [(tile, keyframe) entries with a non-zero mask, atomic adds issued, tiles that took
+        a second traversal] (bahip_debug_redundancy_census)."""
+        out = (C.c_uint64 * 3)()
+        capi.check(self.lib.bahip_debug_redundancy_census(self.ctx.handle, out))
+        return [int(v) for v in out]
+
     OBSERVATION_PLANES = (("keyframes", np.uint16, 1), ("depth_raw", np.float32, 1), ("descriptor_raw", np.float32, 2))
 
     def surfel_observations(self, size=None, capacity=None, prefill=None, residuals=("depth_raw", "descriptor_raw"), keyframes=True):

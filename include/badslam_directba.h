@@ -84,6 +84,22 @@ int dba_observed_covisibility(dba_handle* h, void* hip_stream, int capacity_rows
 int dba_surfel_observations(dba_handle* h, void* hip_stream, uint32_t capacity_surfels, uint64_t capacity_pairs, int capacity_keyframes,
                             uint32_t* first, uint16_t* keyframes, float* depth_raw, float* descriptor_raw, int* keyframe_ids, uint64_t* pairs_out,
                             int* num_keyframes_out);
+/* DirectBA::ComputeKeyframeRedundancy (ours): per existing keyframe, in id order (deleted ids are not rows), its surfels by the number
+ * of other keyframes the association rule pairs them with (bahip_keyframe_observer_histogram), 1 <= bins <= 64.  *num_rows_out = K;
+ * when capacity_rows >= K: keyframe_ids[0 .. K) = the id of each row (may be NULL) and hist[i * bins + j], K x bins row-major.  Returns
+ * non-zero, with *num_rows_out set and nothing else written, when capacity_rows < K or bins is out of range.  Surfel sharding with an
+ * all-reduce installed: the unsharded table on every rank; keyframe sharding: refused. */
+int dba_keyframe_redundancy(dba_handle* h, void* hip_stream, int bins, int capacity_rows, uint32_t* hist, int* keyframe_ids, int* num_rows_out);
+/* DirectBA::FindRedundantKeyframes (ours): the ids of the keyframes with total > 0 and covered >= min_fraction * total -- total a row's
+ * sum, covered its sum over the bins j >= min_other_observers (0 .. bins - 1) -- most redundant first, ties to the lower id.
+ * *num_out = their number; non-zero, with nothing but *num_out written, when capacity is smaller.  Deletes nothing. */
+int dba_find_redundant_keyframes(dba_handle* h, void* hip_stream, int min_other_observers, double min_fraction, int bins, int capacity,
+                                 int* keyframe_ids, int* num_out);
+/* DirectBA::CullRedundantKeyframes (ours): greedy deletion by that rule with a table of 16 bins (min_other_observers 0 .. 15), the table
+ * computed again after each deletion; never the first existing keyframe nor one of the protect_newest last ones; at most
+ * min(max_deletions, capacity) deletions.  deleted_ids[0 .. *num_deleted_out) = the ids in the order of deletion. */
+int dba_cull_redundant_keyframes(dba_handle* h, void* hip_stream, int min_other_observers, double min_fraction, int max_deletions,
+                                 int protect_newest, int capacity, int* deleted_ids, int* num_deleted_out);
 /* DirectBA::RenderSurfels / RenderKeyframeView (ours): the surfel map seen from a camera (bahip_render_surfels), row-major host planes
  * of width * height pixels, any may be NULL: depth, index, normal (3 floats per pixel), color (4 bytes per pixel).  keyframe_id >= 0:
  * the depth camera at that keyframe's pose (view_camera, width, height and global_T_frame are ignored; the planes have the depth

@@ -820,6 +820,39 @@ int bahip_debug_set_observations_shape(int waves, int workgroups, int stage_entr
  * table; *pairs is still P. */
 int bahip_debug_set_observations_stages(int stages);
 
+/* ---- keyframe redundancy (kernels_redundancy.hip; DESIGN.md section 3, "Keyframe redundancy") ---------------------------------------
+ * What a front end culls redundant keyframes by: per bound keyframe, its surfels by the number of OTHER keyframes that observe them.
+ * With A the matrix of the observed co-visibility (A[k][s] = 1 when (surfel s, bound keyframe k) is in the pair population of
+ * bahip_evaluate_cost with the depth term on: the production association rule, a finite position, activation flags of surfels and
+ * keyframes ignored), c_s = sum over k of A[k][s] for s < surfels_size, and o = c_s - 1 the other observers of a surfel with
+ * A[k][s] = 1:  hist[k * pitch_words + j] = the number of s with A[k][s] = 1 and min(o, bins - 1) = j, for j < bins, 1 <= bins <= 64.
+ * hist: device memory, borrowed for the call, K rows in bound order of pitch_words >= bins words; the words [bins, pitch_words) of a
+ * row are never touched.  K = 0 succeeds and writes nothing; surfels_size = 0 writes zeros.  A row's sum is the keyframe's own pair
+ * count (per_keyframe[k].depth_residuals of bahip_evaluate_cost(use_depth = 1), the diagonal of bahip_observed_covisibility); for
+ * j < bins - 1 column j sums to (j + 1) times the number of surfels with j + 1 observers; hist[k][0] counts the surfels only k sees.
+ * Sums of integers: nothing depends on the launch shape, the tile order, the surfel order, the list capacity or the order in which
+ * atomics arrive.  The kernels exist once, in the exact arithmetic flavour: a context set to BAHIP_ARITHMETIC_FAST launches the same code.
+ * The call is refused -- error text, nothing written, nothing launched, the context still usable -- when ctx, surfels or hist is NULL,
+ * bins is outside 1 .. 64, pitch_words < bins, no intrinsics are set, or the context is keyframe-sharded: a rank then holds the masks of
+ * its own keyframes only, so c_s is known on no rank (use surfel sharding).
+ * Waits for the context's stream.  Surfel sharding: a surfel lives in one shard with all its observers, so the table of a shard is
+ * exact for that shard; with an all-reduce hook or an RCCL communicator installed the K x bins words are summed over the ranks as int64
+ * (one exchange; a rank with an empty shard takes part too; the hook's waits apply) and every rank ends with the unsharded table;
+ * without one the shards' tables are summed by the caller.  A failing exchange fails the call, writes nothing into hist and leaves
+ * the context usable. */
+int bahip_keyframe_observer_histogram(bahip_context* ctx, const bahip_surfels* surfels, int bins, uint32_t* hist, int pitch_words);
+/* Launch shape of the sweep (test hook; results never depend on it): wavefronts per workgroup 1 .. 8, workgroups >= 1, list_capacity
+ * 1 .. 448 = the (keyframe, mask) entries a wavefront keeps in LDS before a tile is traversed a second time (the overflow path),
+ * tile_order 0 = buffer order, 1 = the sweeps' heavy-first order when there is one; 0 / -1 = the default. */
+int bahip_debug_set_redundancy_shape(int waves, int workgroups, int list_capacity, int tile_order);
+/* What bahip_keyframe_observer_histogram launches (scripts/keyframe_redundancy_eval.py takes the stages' times by difference): 1 clear,
+ * 2 traversal (the counts and the lists are built), 4 attribution (the atomics and the second traversals; needs 2), or-ed; 0 = all.
+ * With a stage missing the words are not the table. */
+int bahip_debug_set_redundancy_stages(int stages);
+/* Of the last bahip_keyframe_observer_histogram of this context (this rank's shard): out[0] = (tile, keyframe) entries with a non-zero
+ * mask, out[1] = atomic adds issued into hist, out[2] = tiles that took a second traversal. */
+int bahip_debug_redundancy_census(bahip_context* ctx, uint64_t out[3]);
+
 /* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
  * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
  * e = 1e-8 + prior(u) as before and t = lambda * M[u] (one binary32 product), the preconditioner divides by ((M[u] + 1e-8) + prior(u))
