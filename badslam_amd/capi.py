@@ -306,6 +306,11 @@ SIGNATURES = {
     "bahip_debug_set_redundancy_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bahip_debug_set_redundancy_stages": (C.c_int, [C.c_int]),
     "bahip_debug_redundancy_census": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bahip_debug_set_observed_structure_route": (C.c_int, [C.c_int]),
+    "bahip_debug_set_tile_mask_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]),
+    "bahip_debug_set_tile_mask_stages": (C.c_int, [C.c_int]),
+    "bahip_debug_read_tile_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "bahip_debug_tile_mask_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "bahip_debug_evaluate_pairs": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(Surfels),
                                              C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_float)]),
     "bahip_debug_read_pcg_vector": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)]),

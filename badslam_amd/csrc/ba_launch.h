@@ -718,6 +718,65 @@ void launch_redundancy_sweep(hipStream_t stream, const Intrinsics& in, const KfE
 void launch_redundancy_widen(hipStream_t stream, const uint32_t* compact, uint32_t words, long long* wide);
 void launch_redundancy_narrow(hipStream_t stream, const long long* wide, int num_kfs, int bins, uint32_t* hist, uint32_t pitch);
 
+// kernels_tile_masks.hip: the tile mask table -- per tile of 64 surfels the (keyframe, 64-bit ballot) entries with a non-zero ballot,
+// ascending by keyframe -- built over a keyframe partition, and the observed co-visibility, the keyframe redundancy and the
+// observation lists computed from it (exists once: the exact flavour's association under either flavour).  Launch shape: `waves`
+// wavefronts per workgroup, at most `workgroups` of them.
+constexpr int kTileMaskMaxWaves = 8, kTileMaskBinBytes = 12;   // LDS of the redundancy reduction: 64 (bin, mask) entries per wavefront
+constexpr int kTileMaskDefaultWaves = 4, kTileMaskWorkgroupsPerUnit = 4;   // the observation sweeps' shape: the same traversal
+struct TileMaskShape {
+  int waves, workgroups;
+};
+struct TileMaskTable {   // device
+  const uint32_t* tile_first;          // tiles + 1 words
+  const uint32_t* keyframes;           // entries
+  const unsigned long long* masks;     // entries
+  uint32_t tiles, entries;
+};
+// the entries of the keyframes k with (k & owner_mask) == owner_rank per tile: counts[t] (zeroed) and this rank's 16-bit field of
+// plane[t * plane_words + owner_rank / 4] (zeroed); *listed (zeroed) += their number
+void launch_tile_mask_count(hipStream_t stream, const Intrinsics& in, const KfEntry* frames, int num_kfs, uint32_t owner_mask, uint32_t owner_rank,
+                            const SurfelsView& s, const uint32_t* sched, const TileMaskShape& shape, uint32_t* counts, long long* plane,
+                            uint32_t plane_words, unsigned long long* listed);
+// from the summed plane: totals[t] (tiles + 1 words, the last zero: the input of the scan into tile_first) and the entries of the
+// ranks below `rank` per tile
+void launch_tile_mask_offsets(hipStream_t stream, const long long* plane, uint32_t plane_words, uint32_t tiles, uint32_t rank, uint32_t world,
+                              uint32_t* totals, uint32_t* rank_offset);
+// this rank's entries at tile_first[t] + rank_offset[t] + the running index of zero-filled planes of `entries` entries
+void launch_tile_mask_fill(hipStream_t stream, const Intrinsics& in, const KfEntry* frames, int num_kfs, uint32_t owner_mask, uint32_t owner_rank,
+                           const SurfelsView& s, const uint32_t* sched, const TileMaskShape& shape, const uint32_t* counts,
+                           const uint32_t* tile_first, const uint32_t* rank_offset, uint32_t entries, uint32_t* keyframes,
+                           unsigned long long* masks);
+// the entries [begin, begin + count) as count + ceil(count / 4) int64 words (masks, then keyframe indices four to a word), and back
+inline size_t tile_mask_slice_words(size_t count) { return count + (count + 3) / 4; }
+void launch_tile_mask_pack(hipStream_t stream, const uint32_t* keyframes, const unsigned long long* masks, uint32_t begin, uint32_t count,
+                           long long* stage);
+void launch_tile_mask_unpack(hipStream_t stream, const long long* stage, uint32_t begin, uint32_t count, uint32_t* keyframes,
+                             unsigned long long* masks);
+// per tile the runs of the ranks merged into one run ascending in k
+void launch_tile_mask_merge(hipStream_t stream, const TileMaskShape& shape, const uint32_t* tile_first, uint32_t tiles, uint32_t entries,
+                            const uint32_t* in_kf, const unsigned long long* in_mask, uint32_t* out_kf, unsigned long long* out_mask);
+// the reductions over the tiles t with t % world == rank; *adds += the atomic adds issued.  counts: the lower triangle, as
+// launch_covisibility_sweep; hist: as launch_redundancy_sweep
+void launch_tile_mask_covisibility(hipStream_t stream, const TileMaskShape& shape, const TileMaskTable& table, uint32_t rank, uint32_t world,
+                                   int num_kfs, uint32_t* counts, uint32_t pitch, unsigned long long* adds);
+void launch_tile_mask_redundancy(hipStream_t stream, const TileMaskShape& shape, const TileMaskTable& table, uint32_t rank, uint32_t world,
+                                 int num_kfs, int bins, uint32_t* hist, uint32_t pitch, unsigned long long* adds);
+// counts[s] for s < surfels and *total (zeroed) += their sum; the keyframes plane from the scan of the counts; the payload of this
+// rank's keyframes into zero-filled planes (either may be NULL), *words += the payload words written
+void launch_tile_mask_observation_counts(hipStream_t stream, const TileMaskShape& shape, const TileMaskTable& table, uint32_t surfels,
+                                         uint32_t* counts, unsigned long long* total);
+void launch_tile_mask_observation_keyframes(hipStream_t stream, const TileMaskShape& shape, const TileMaskTable& table, uint32_t surfels,
+                                            const uint32_t* first, uint16_t* keyframes);
+void launch_tile_mask_payload(hipStream_t stream, const Intrinsics& in, const KfEntry* frames, int num_kfs, uint32_t owner_mask, uint32_t owner_rank,
+                              const SurfelsView& s, const uint32_t* sched, const TileMaskShape& shape, const TileMaskTable& table,
+                              const uint32_t* first, float* depth_plane, float* desc_plane, unsigned long long* words);
+// the 32-bit words [begin, begin + count) of a plane as ceil(count / 2) int64 words, and back
+void launch_tile_mask_words_pack(hipStream_t stream, const uint32_t* plane, size_t begin, uint32_t count, long long* stage);
+void launch_tile_mask_words_unpack(hipStream_t stream, const long long* stage, size_t begin, uint32_t count, uint32_t* plane);
+// census[0 .. 3) = (entries, *adds, 0)
+void launch_tile_mask_census(hipStream_t stream, unsigned long long entries, const unsigned long long* adds, unsigned long long* census);
+
 // kernels_ingest.hip: a frame brought to the BA's pyramid level (exists once: integer rules and one correctly rounded division, the same
 // under either flavour).  The callers have checked sizes and pitches; the downscale's blocks are at most kIngestMaxBlock on a side.
 constexpr int kIngestMaxBlock = 9, kIngestMaxLevels = 3;

@@ -32,12 +32,12 @@ int bahip_observed_covisibility(bahip_context* ctx, const bahip_surfels* surfels
   const int K = ctx->num_kfs;
   REQUIRE(pitch_words >= K, "bahip_observed_covisibility: pitch_words is smaller than the number of bound keyframes");
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
-  REQUIRE(!kf_sharded(ctx),
-          "bahip_observed_covisibility is not available under keyframe sharding (a rank holds the masks of its own keyframes only): use "
-          "surfel sharding");
+  REQUIRE(!kf_sharded(ctx) || is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator");
   REQUIRE(K < 65536, "bahip_observed_covisibility: more than 65 535 bound keyframes");
   REQUIRE(surfels->surfels_size == 0 || surfels->data != nullptr, "bahip_observed_covisibility: no surfel data");
   if (K == 0) return 0;
+  if (observed_structure_by_table(ctx)) return tile_mask_covisibility(ctx, surfels, counts, pitch_words);   // (capi_tile_masks.hip)
+  ctx->tile_mask_valid = false;   // (this call builds no table)
   if (ctx->covis_census.reserve(3, 0, "the co-visibility census")) return 1;
   const bool exchange = is_sharded(ctx);   // (an empty surfel shard must still join the exchange of the others)
   const size_t words = (size_t)K * (size_t)K;

@@ -13,6 +13,7 @@
 //   capi_covisibility.hip the surfels every pair of keyframes shares (bahip_observed_covisibility)
 //   capi_observations.hip the keyframes paired with each surfel, in compressed rows (bahip_surfel_observations)
 //   capi_redundancy.hip per keyframe its surfels by the number of other observers (bahip_keyframe_observer_histogram)
+//   capi_tile_masks.hip the tile mask table: those three calls under keyframe sharding, and on route 1 elsewhere
 //   capi_pcg_trial.hip  step control of the PCG scheme
 //   capi_pose_trial.hip step control of the pose phase of the alternating scheme
 //   capi_geometry_trial.hip step control of the geometry phase of the alternating scheme
@@ -242,6 +243,20 @@ struct bahip_context {
   // ([K x bins int64 | K x bins uint32]) that are summed over the ranks (kernels_redundancy.hip)
   DeviceBuffer<unsigned long long> redundancy_census;
   DeviceBuffer<long long> redundancy_stage;
+  // the tile mask table of the last call that built one (capi_tile_masks.hip, kernels_tile_masks.hip): per-tile words ([own counts
+  // T + 1 | totals T + 1 | entries of the lower ranks T | tile_first T + 1]), the count plane the ranks sum, the entries in the
+  // rank-major layout and merged, one slice of staging for the sums over the ranks, four counters (entries this rank listed, atomic
+  // adds, payload words, the pair total) and the scan's storage; what the last call left (bahip_debug_read_tile_masks, _stats)
+  DeviceBuffer<uint32_t> tile_mask_words;
+  DeviceBuffer<long long> tile_mask_plane;
+  DeviceBuffer<uint32_t> tile_mask_raw_keyframes, tile_mask_keyframes;
+  DeviceBuffer<unsigned long long> tile_mask_raw_masks, tile_mask_masks;
+  DeviceBuffer<long long> tile_mask_stage;
+  DeviceBuffer<unsigned long long> tile_mask_counters;
+  DeviceBuffer<void> tile_mask_scan_temp;
+  uint32_t tile_mask_tiles = 0, tile_mask_entries = 0;
+  bool tile_mask_valid = false;
+  long long tile_mask_exchanges = 0, tile_mask_consumer_tiles = 0;
   // dealing the lifecycle under surfel sharding (bahip_context_set_lifecycle_dealing): the switch, and the surfel partition of the
   // whole-cloud phase in progress -- set by bahip_gather_surfel_shards, cleared by bahip_extract_surfel_shard (deal_world 1: none) --
   // with the gathered cloud it belongs to: lifecycle calls on any other buffer are not dealt
@@ -341,6 +356,14 @@ inline bool lifecycle_dealt(const bahip_context* ctx, const bahip_surfels* surfe
          surfels != nullptr && surfels->data != nullptr && surfels->data == ctx->deal_data;
 }
 inline bool deal_owned(const bahip_context* ctx, int k) { return (k & (ctx->deal_world - 1)) == ctx->deal_rank; }
+// ---- defined in capi_tile_masks.hip ---------------------------------------------------------------------------------------------
+// The observed structure by way of the tile mask table: under keyframe sharding always, elsewhere on route 1
+// (bahip_debug_set_observed_structure_route).  The three entry points hand over after their refusals, with K > 0.
+bool observed_structure_by_table(const bahip_context* ctx);
+int tile_mask_covisibility(bahip_context* ctx, const bahip_surfels* surfels, uint32_t* counts, int pitch_words);
+int tile_mask_histogram(bahip_context* ctx, const bahip_surfels* surfels, int bins, uint32_t* hist, int pitch_words);
+int tile_mask_observations(bahip_context* ctx, const bahip_surfels* surfels, const bahip_observations* out, uint64_t pair_limit, uint64_t* pairs);
+
 #define REQUIRE_NO_KF_SHARDING(what) \
   REQUIRE(!kf_sharded(ctx), what " is not available under keyframe sharding (its per-surfel sums run over all keyframes in order): use surfel sharding")
 

@@ -39,9 +39,7 @@ int bahip_surfel_observations(bahip_context* ctx, const bahip_surfels* surfels, 
           "bahip_surfel_observations: a payload plane (depth_raw, descriptor_raw) without keyframes");
   const int K = ctx->num_kfs;
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
-  REQUIRE(!kf_sharded(ctx),
-          "bahip_surfel_observations is not available under keyframe sharding (a rank holds the masks of its own keyframes only): use "
-          "surfel sharding");
+  REQUIRE(!kf_sharded(ctx) || is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator");
   REQUIRE(K < 65536, "bahip_surfel_observations: more than 65 535 bound keyframes");
   REQUIRE(surfels->surfels_size == 0 || surfels->data != nullptr, "bahip_surfel_observations: no surfel data");
   const SurfelsView v = make_view(surfels);
@@ -53,6 +51,8 @@ int bahip_surfel_observations(bahip_context* ctx, const bahip_surfels* surfels, 
     *pairs = 0;
     return 0;
   }
+  if (observed_structure_by_table(ctx)) return tile_mask_observations(ctx, surfels, out, g_pair_limit, pairs);   // (capi_tile_masks.hip)
+  ctx->tile_mask_valid = false;   // (this call builds no table)
   if (ctx->obs_counts.reserve(words, words / 8, "the observation counts")) return 1;
   if (ctx->obs_total.reserve(1, 0, "the observation total")) return 1;
   if (ctx->obs_scan_temp.reserve(scan_temp_bytes(words), 0, "the scan of the observation counts")) return 1;

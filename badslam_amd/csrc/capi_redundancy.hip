@@ -32,12 +32,15 @@ int bahip_keyframe_observer_histogram(bahip_context* ctx, const bahip_surfels* s
   REQUIRE(bins >= 1 && bins <= kRedundancyMaxBins, "bahip_keyframe_observer_histogram: bins outside 1 .. 64");
   REQUIRE(pitch_words >= bins, "bahip_keyframe_observer_histogram: pitch_words is smaller than bins");
   REQUIRE(ctx->have_intrinsics, "bahip_set_intrinsics not called");
-  REQUIRE(!kf_sharded(ctx),
-          "bahip_keyframe_observer_histogram is not available under keyframe sharding (a rank holds the masks of its own keyframes only, so "
-          "no rank knows a surfel's observers): use surfel sharding");
+  REQUIRE(!kf_sharded(ctx) || is_sharded(ctx), "keyframe sharding needs an all-reduce hook or an RCCL communicator");
   REQUIRE(surfels->surfels_size == 0 || surfels->data != nullptr, "bahip_keyframe_observer_histogram: no surfel data");
   const int K = ctx->num_kfs;
   if (K == 0) return 0;
+  if (observed_structure_by_table(ctx)) {   // (capi_tile_masks.hip)
+    REQUIRE(K < 65536, "bahip_keyframe_observer_histogram: more than 65 535 bound keyframes for the tile mask table");
+    return tile_mask_histogram(ctx, surfels, bins, hist, pitch_words);
+  }
+  ctx->tile_mask_valid = false;   // (this call builds no table)
   if (ctx->redundancy_census.reserve(3, 0, "the keyframe redundancy census")) return 1;
   const bool exchange = is_sharded(ctx);   // (an empty surfel shard must still join the exchange of the others)
   const size_t words = (size_t)K * (size_t)bins;

@@ -280,7 +280,8 @@ class DirectBA:
     def observed_covisibility(self):
         """DirectBA::ComputeObservedCovisibility: (ids, counts) -- the ids of the existing keyframes in order and the (K, K) uint32
         matrix of the surfels the association rule pairs with both keyframes of a pair (both triangles; the diagonal a keyframe's own
-        pair count).  Under surfel sharding with an all-reduce installed every rank gets the unsharded matrix."""
+        pair count).  Under surfel sharding with an all-reduce installed, and under keyframe sharding, every rank gets the
+        unsharded matrix."""
         cap = max(1, self.keyframe_count())
         counts = np.zeros(cap * cap, np.uint32)
         ids = (C.c_int * cap)()
@@ -293,7 +294,7 @@ class DirectBA:
         """DirectBA::ComputeSurfelObservations: a dict -- keyframe_ids (the id of each bound index), first (surfels_size + 1 uint32
         offsets, the last one the number of pairs P), keyframes (P uint16 indices into keyframe_ids, ascending within a surfel's list)
         and, with residuals, depth_raw (P float32) and descriptor_raw ((P, 2) float32, NaN where the pair's colour pixel is not
-        valid).  Under surfel sharding this rank's shard."""
+        valid).  Under surfel sharding this rank's shard; under keyframe sharding the unsharded lists on every rank."""
         n, cap = self.surfels_size(), max(1, self.keyframe_count())
         pairs, K = C.c_uint64(), C.c_int()
         self.L.dba_surfel_observations(self.h, self.stream, 0, 0, 0, None, None, None, None, None, C.byref(pairs), C.byref(K))   # sizes the arrays
@@ -313,7 +314,7 @@ class DirectBA:
     def keyframe_redundancy(self, bins=16):
         """DirectBA::ComputeKeyframeRedundancy: (ids, hist) -- the ids of the existing keyframes in order and the (K, bins) uint32
         table: hist[i, j] = the surfels paired with keyframe ids[i] that min(o, bins - 1) = j other keyframes are paired with too.
-        Under surfel sharding with an all-reduce installed every rank gets the unsharded table."""
+        Under surfel sharding with an all-reduce installed, and under keyframe sharding, every rank gets the unsharded table."""
         cap = max(1, self.keyframe_count())
         hist = np.zeros(cap * bins, np.uint32)
         ids = (C.c_int * cap)()

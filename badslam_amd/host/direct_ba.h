@@ -69,15 +69,15 @@ class DirectBA {
   // the association rule pairs with both the i-th and the j-th existing keyframe, K x K row-major, both triangles, the diagonal a
   // keyframe's own pair count; keyframe_ids[i] = the id of row i (deleted keyframes are not rows, as with ComputeCost).  Nothing acts on
   // the values: the co-visibility lists of the keyframes stay the frustum test's.  Surfel sharding with an all-reduce installed: every
-  // rank gets the unsharded matrix; keyframe sharding: refused.  Waits for the stream.
+  // rank gets the unsharded matrix; keyframe sharding: the same, by way of the tile mask table.  Waits for the stream.
   void ComputeObservedCovisibility(hipStream_t stream, vector<uint32_t>* counts, vector<int>* keyframe_ids);
   // Observation lists (bahip_surfel_observations; DESIGN.md section 3, "Observation lists"): the associated (surfel, keyframe) pairs in
   // compressed rows by surfel.  first: surfels_size + 1 offsets, first.back() = the number of pairs; keyframes[first[s] .. first[s + 1]):
   // the keyframes paired with surfel s as indices into keyframe_ids, ascending; keyframe_ids[k] = the id of bound index k (deleted
   // keyframes are not bound, as with ComputeCost).  with_residuals: entry for entry depth_raw (the pair's raw depth residual) and
   // descriptor_raw (two words per entry; NaN twice where the pair's colour pixel is not valid); otherwise both stay empty.  A count
-  // call sizes the buffers, a second call fills them.  Surfel sharding: this rank's shard; keyframe sharding: refused.  Waits for the
-  // stream.
+  // call sizes the buffers, a second call fills them.  Surfel sharding: this rank's shard; keyframe sharding: the unsharded lists on
+  // every rank (every rank must ask for the same).  Waits for the stream.
   struct SurfelObservations {
     vector<uint32_t> first;
     vector<uint16_t> keyframes;
@@ -89,7 +89,8 @@ class DirectBA {
   // surfels the association rule pairs with the i-th existing keyframe that min(o, bins - 1) = j OTHER keyframes are paired with as
   // well, K x bins row-major, 1 <= bins <= 64; keyframe_ids[i] = the id of row i (deleted keyframes are not rows, as with
   // ComputeObservedCovisibility).  Surfel sharding with an all-reduce installed: every rank gets the unsharded table; keyframe
-  // sharding: refused.  Waits for the stream.
+  // sharding: the same, by way of the tile mask table (FindRedundantKeyframes and CullRedundantKeyframes with it: DeleteKeyframe moves
+  // the ownership of the later keyframes, whose images the object must hold).  Waits for the stream.
   void ComputeKeyframeRedundancy(hipStream_t stream, int bins, vector<uint32_t>* hist, vector<int>* keyframe_ids);
   // The keyframes the map does without: with total = a row's sum and covered = its sum over the bins j >= min_other_observers
   // (<= bins - 1), a keyframe qualifies when total > 0 and (double)covered >= min_fraction * (double)total.  keyframe_ids: the ids of

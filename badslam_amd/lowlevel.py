@@ -24,6 +24,20 @@ def live_allocations(lib=None):
     return int(count.value), int(nbytes.value)
 
 
+def set_observed_structure_route(route, lib=None):
+    """Which kernels the observed co-visibility, the keyframe redundancy and the observation lists run (process-wide test hook,
+    bahip_debug_set_observed_structure_route): 0 = their own wherever those are allowed (the default), 1 = the tile mask table on an
+    unsharded or surfel-sharded context too.  A keyframe-sharded context always takes the table."""
+    capi.check((lib or capi.load()).bahip_debug_set_observed_structure_route(int(route)))
+
+
+def set_tile_mask_shape(waves=0, workgroups=0, tile_order=-1, entry_slice=0, payload_slice=0, lib=None):
+    """Launch shape and exchange slices of the tile mask table (process-wide test hook, bahip_debug_set_tile_mask_shape); no argument:
+    the defaults."""
+    capi.check((lib or capi.load()).bahip_debug_set_tile_mask_shape(int(waves), int(workgroups), int(tile_order), int(entry_slice),
+                                                                    int(payload_slice)))
+
+
 def split_render_key(key):
     """A key plane of bahip_render_surfels (uint64: bits(depth) << 32 | index, all ones where empty) as (depth float32, index uint32) with
     the empty pixels as the call's own depth and index planes have them: +0.0 and 0xFFFFFFFF.  The elementwise minimum of the key planes
@@ -905,6 +919,28 @@ class Scene:
         a second traversal] (bahip_debug_redundancy_census)."""
         out = (C.c_uint64 * 3)()
         capi.check(self.lib.bahip_debug_redundancy_census(self.ctx.handle, out))
+        return [int(v) for v in out]
+
+    def tile_masks(self, size=None):
+        """The tile mask table the last observed_covisibility, keyframe_observer_histogram or surfel_observations of this scene built
+        (bahip_debug_read_tile_masks; under keyframe sharding, or on route 1 of set_observed_structure_route) over `size` surfels
+        (default: all; the size that call was given): (tile_first, keyframes, masks) -- tiles + 1 uint32, and per entry a uint32
+        keyframe index and a uint64 ballot, a tile's entries contiguous and ascending by keyframe."""
+        entries = C.c_uint64(0)
+        capi.check(self.lib.bahip_debug_read_tile_masks(self.ctx.handle, None, None, None, 0, C.byref(entries)))
+        E = int(entries.value)
+        first = np.zeros(((self.surfels_size if size is None else int(size)) + 63) // 64 + 1, np.uint32)
+        keyframes, masks = np.zeros(max(1, E), np.uint32), np.zeros(max(1, E), np.uint64)
+        capi.check(self.lib.bahip_debug_read_tile_masks(self.ctx.handle, first.ctypes.data, keyframes.ctypes.data, masks.ctypes.data, E,
+                                                        C.byref(entries)))
+        assert int(entries.value) == E and int(first[-1]) == E
+        return first, keyframes[:E], masks[:E]
+
+    def tile_mask_stats(self):
+        """Of the last call on the table route (bahip_debug_tile_mask_stats): [entries this rank listed, entries of the merged table,
+        exchanges, tiles whose reduction this rank ran, atomic adds, payload words written]."""
+        out = (C.c_uint64 * 6)()
+        capi.check(self.lib.bahip_debug_tile_mask_stats(self.ctx.handle, out))
         return [int(v) for v in out]
 
     OBSERVATION_PLANES = (("keyframes", np.uint16, 1), ("depth_raw", np.float32, 1), ("descriptor_raw", np.float32, 2))

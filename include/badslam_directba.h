@@ -73,14 +73,15 @@ int dba_compute_surfel_costs(dba_handle* h, void* hip_stream, uint32_t capacity,
  * (bahip_observed_covisibility), over the existing keyframes in id order (deleted ids are not rows).  *num_rows_out = K, the number of
  * rows; when capacity_rows >= K: keyframe_ids[0 .. K) = the id of each row (may be NULL) and counts[i * K + j], K x K row-major, both
  * triangles, the diagonal a keyframe's own pair count.  Returns non-zero, with *num_rows_out set and nothing else written, when
- * capacity_rows < K.  Surfel sharding with an all-reduce installed: the unsharded matrix on every rank; keyframe sharding: refused. */
+ * capacity_rows < K.  Surfel sharding with an all-reduce installed: the unsharded matrix on every rank; keyframe sharding: the same. */
 int dba_observed_covisibility(dba_handle* h, void* hip_stream, int capacity_rows, uint32_t* counts, int* keyframe_ids, int* num_rows_out);
 /* DirectBA::ComputeSurfelObservations (ours): the observation lists (bahip_surfel_observations) into host arrays -- first
  * (surfels_size + 1 offsets, the last one the number of pairs P), keyframes (P indices into keyframe_ids, ascending within a list),
  * depth_raw (P words) and descriptor_raw (2 P words), either or both may be NULL, and keyframe_ids (the id of each bound index, may be
  * NULL; deleted ids are not bound).  *pairs_out = P and *num_keyframes_out = K are always set.  Returns non-zero, with nothing else
  * written, when capacity_surfels < surfels_size, capacity_pairs < P, capacity_keyframes < K or first or keyframes is NULL: call with
- * zero capacities to size the arrays.  Surfel sharding: this rank's shard; keyframe sharding: refused. */
+ * zero capacities to size the arrays.  Surfel sharding: this rank's shard; keyframe sharding: the unsharded
+ * lists on every rank (every rank must ask for the same planes). */
 int dba_surfel_observations(dba_handle* h, void* hip_stream, uint32_t capacity_surfels, uint64_t capacity_pairs, int capacity_keyframes,
                             uint32_t* first, uint16_t* keyframes, float* depth_raw, float* descriptor_raw, int* keyframe_ids, uint64_t* pairs_out,
                             int* num_keyframes_out);
@@ -88,7 +89,7 @@ int dba_surfel_observations(dba_handle* h, void* hip_stream, uint32_t capacity_s
  * of other keyframes the association rule pairs them with (bahip_keyframe_observer_histogram), 1 <= bins <= 64.  *num_rows_out = K;
  * when capacity_rows >= K: keyframe_ids[0 .. K) = the id of each row (may be NULL) and hist[i * bins + j], K x bins row-major.  Returns
  * non-zero, with *num_rows_out set and nothing else written, when capacity_rows < K or bins is out of range.  Surfel sharding with an
- * all-reduce installed: the unsharded table on every rank; keyframe sharding: refused. */
+ * all-reduce installed: the unsharded table on every rank; keyframe sharding: the same. */
 int dba_keyframe_redundancy(dba_handle* h, void* hip_stream, int bins, int capacity_rows, uint32_t* hist, int* keyframe_ids, int* num_rows_out);
 /* DirectBA::FindRedundantKeyframes (ours): the ids of the keyframes with total > 0 and covered >= min_fraction * total -- total a row's
  * sum, covered its sum over the bins j >= min_other_observers (0 .. bins - 1) -- most redundant first, ties to the lower id.

@@ -143,6 +143,14 @@ int bahip_context_set_allreduce(bahip_context* ctx, bahip_allreduce_fn fn, void*
  *       bahip_delete_surfels_and_update_radii: per surfel the observation and violation counts and one minimum-radius word per rank
  *         ((2 + world) x 4 bytes);
  *     compaction and the spatial order read no image and run as they are;
+ *   - bahip_observed_covisibility, bahip_keyframe_observer_histogram and bahip_surfel_observations build the tile mask table (per
+ *     tile of 64 surfels the (keyframe, 64-bit ballot) entries with a non-zero ballot; DESIGN.md section 3, "The tile mask table")
+ *     from every rank's own keyframes with two integer sums of zero-filled partials -- the per-tile entry counts (T x ceil(world / 4)
+ *     int64 words, T = ceil(surfels / 64)) and the E entries (10 bytes each, in slices of at most 1 600 000 entries; none when
+ *     E = 0) -- and reduce it on every rank: the matrix and the histogram over the tiles t % world == rank, summed over the ranks (one
+ *     exchange of K x K or K x bins int64 words); the lists on every rank from the whole table, the payload planes from this rank's
+ *     keyframes, summed as bit patterns (4 bytes per depth_raw word, 8 per descriptor_raw pair, per plane in slices of at most
+ *     4 000 000 words).  Every argument of such a call, the capacity and the planes asked for included, is the same on every rank;
  *   - everything ends with the bits of the unsharded run (with the same class counts) on every rank.
  * The PCG stage entry points (bahip_pcg_begin ...), bahip_assign_colors and the one-keyframe lifecycle entry points
  * (bahip_create_surfels_for_keyframe, bahip_determine_supporting_surfels) and bahip_merge_surfels_for_keyframes (a frame does not
@@ -759,8 +767,12 @@ int bahip_debug_set_residual_image_stages(int stages);
  * the tile order, the surfel order or the order in which atomics arrive.  The kernels exist once, in the exact arithmetic flavour: a
  * context set to BAHIP_ARITHMETIC_FAST launches the same code, so the matrix is the exact flavour's association.
  * The call is refused -- error text, nothing written, nothing launched, the context still usable -- when ctx, surfels or counts is NULL,
- * pitch_words < K, no intrinsics are set, or the context is keyframe-sharded: a rank then holds the masks of its own keyframes only, and
- * a pair of keyframes on two ranks would need their mask tables exchanged, which is left for later (use surfel sharding).
+ * pitch_words < K, no intrinsics are set, 65 536 or more keyframes are bound, or the context is keyframe-sharded without a transport.
+ * Keyframe sharding (with an all-reduce hook or an RCCL communicator): the ranks build the tile mask table with 1 + ceil(E / 1 600 000)
+ * exchanges (bahip_context_set_keyframe_sharding), every rank sums the pairs of the tiles t % world == rank, and one exchange of K x K
+ * int64 words gives every rank the unsharded matrix; the call then waits for the stream.  A failing exchange fails the call with a
+ * message that names it ("tile mask counts", "tile mask entries", "co-visibility words"), writes nothing into counts and leaves the
+ * context usable.
  * Asynchronous on the context's stream.  Surfel sharding: the call covers the shard it is given; with an all-reduce hook or an RCCL
  * communicator installed the K x K words are summed over the ranks as int64 (one exchange of K x K words; a rank with an empty shard
  * takes part too; the hook's waits apply) and every rank ends with the unsharded matrix; without one the shards' matrices are summed by
@@ -797,9 +809,16 @@ int bahip_debug_covisibility_census(bahip_context* ctx, uint64_t out[3]);
  * an all-zero surfel_first and P = 0.
  * The call is refused -- error text, nothing written, nothing launched, the context still usable -- when ctx, surfels, out,
  * out->surfel_first or pairs is NULL, a payload plane is given without keyframes, no intrinsics are set, 65 536 or more keyframes are
- * bound, or the context is keyframe-sharded (a rank holds the images of its own keyframes only: use surfel sharding).  A P above the pair
+ * bound, or the context is keyframe-sharded without a transport.  A P above the pair
  * limit (2^32 - 1) fails the call after the count and before a word of surfel_first or of a plane is written.
- * Surfel sharding: the call covers the shard it is given and exchanges nothing. */
+ * Surfel sharding: the call covers the shard it is given and exchanges nothing.
+ * Keyframe sharding (with an all-reduce hook or an RCCL communicator): the ranks build the tile mask table with 1 + ceil(E / 1 600 000)
+ * exchanges; every rank computes P, surfel_first and keyframes from it without a further exchange; the payload planes asked for are
+ * zero-filled, written by every rank for the pairs of its own keyframes and summed over the ranks as bit patterns, per plane in slices
+ * of at most 4 000 000 words (P words of depth_raw, 2 P of descriptor_raw).  P is the same on every rank, and so is what the call does:
+ * out->capacity and the planes asked for MUST be the same on every rank, like every argument of a keyframe-sharded call.  A failing
+ * exchange ("tile mask counts", "tile mask entries", "observation payload") fails the call, leaves *pairs unwritten and the context
+ * usable. */
 typedef struct bahip_observations {
   uint32_t* surfel_first;   /* surfels_size + 1 words, required */
   uint16_t* keyframes;      /* capacity entries, or NULL: count only */
@@ -833,8 +852,11 @@ int bahip_debug_set_observations_stages(int stages);
  * Sums of integers: nothing depends on the launch shape, the tile order, the surfel order, the list capacity or the order in which
  * atomics arrive.  The kernels exist once, in the exact arithmetic flavour: a context set to BAHIP_ARITHMETIC_FAST launches the same code.
  * The call is refused -- error text, nothing written, nothing launched, the context still usable -- when ctx, surfels or hist is NULL,
- * bins is outside 1 .. 64, pitch_words < bins, no intrinsics are set, or the context is keyframe-sharded: a rank then holds the masks of
- * its own keyframes only, so c_s is known on no rank (use surfel sharding).
+ * bins is outside 1 .. 64, pitch_words < bins, no intrinsics are set, or the context is keyframe-sharded without a transport.
+ * Keyframe sharding (with an all-reduce hook or an RCCL communicator; fewer than 65 536 bound keyframes): the ranks build the tile mask
+ * table with 1 + ceil(E / 1 600 000) exchanges, so every rank knows every c_s; every rank attributes the tiles t % world == rank, and one
+ * exchange of K x bins int64 words gives every rank the unsharded table.  A failing exchange fails the call with a message that names
+ * it ("tile mask counts", "tile mask entries", "observer histogram words"), writes nothing into hist and leaves the context usable.
  * Waits for the context's stream.  Surfel sharding: a surfel lives in one shard with all its observers, so the table of a shard is
  * exact for that shard; with an all-reduce hook or an RCCL communicator installed the K x bins words are summed over the ranks as int64
  * (one exchange; a rank with an empty shard takes part too; the hook's waits apply) and every rank ends with the unsharded table;
@@ -852,6 +874,30 @@ int bahip_debug_set_redundancy_stages(int stages);
 /* Of the last bahip_keyframe_observer_histogram of this context (this rank's shard): out[0] = (tile, keyframe) entries with a non-zero
  * mask, out[1] = atomic adds issued into hist, out[2] = tiles that took a second traversal. */
 int bahip_debug_redundancy_census(bahip_context* ctx, uint64_t out[3]);
+
+/* ---- the tile mask table (kernels_tile_masks.hip; DESIGN.md section 3, "The tile mask table"): test hooks ---------------------------
+ * The route of the three calls above: 0 (default) = their own kernels wherever those are allowed, the table under keyframe sharding;
+ * 1 = the table on an unsharded or surfel-sharded context too: no owner filter, no exchange of the table, all tiles on this rank,
+ * then the surfel shards' sum as on route 0.  The words never depend on the route. */
+int bahip_debug_set_observed_structure_route(int route);
+/* Launch shape of the table's kernels (results never depend on it): wavefronts per workgroup 1 .. 8, workgroups >= 1, tile_order
+ * 0 = buffer order, 1 = the sweeps' heavy-first order when there is one; entry_slice = the entries, payload_slice = the 32-bit payload
+ * words one exchange carries at most.  0 (tile_order: -1) = the default. */
+int bahip_debug_set_tile_mask_shape(int waves, int workgroups, int tile_order, uint32_t entry_slice, uint32_t payload_slice);
+/* What a call on the table route launches (scripts/observed_structure_table_eval.py takes the stages' times by difference): 1 = the
+ * count sweep (with its exchange, the scan and the read-back of E), 3 = + the fill sweep (with its exchange), 7 = + the merge, 15 or
+ * 0 = all.  With a stage missing the words are not the results and no table can be read back. */
+int bahip_debug_set_tile_mask_stages(int stages);
+/* The table the last of the three calls of this context built (host memory): tile_first ceil(surfels / 64) + 1 words, and, when the
+ * E entries fit into `capacity`, keyframes and masks, E entries each, the entries of a tile contiguous and ascending by keyframe.
+ * *entries = E.  Any of the three pointers may be NULL.  Refused when that call built none (route 0 without keyframe sharding, no
+ * surfels, a failed exchange). */
+int bahip_debug_read_tile_masks(bahip_context* ctx, uint32_t* tile_first, uint32_t* keyframes, uint64_t* masks, uint64_t capacity, uint64_t* entries);
+/* Of the last call of this context on the table route: out[0] = entries this rank listed, out[1] = entries of the merged table,
+ * out[2] = exchanges the call made, out[3] = tiles whose reduction this rank ran, out[4] = atomic adds it issued, out[5] = payload
+ * words it wrote.  On that route the census hooks of the co-visibility and the redundancy report [0] the merged entries, [1] this
+ * rank's adds, [2] 0. */
+int bahip_debug_tile_mask_stats(bahip_context* ctx, uint64_t out[6]);
 
 /* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
  * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
