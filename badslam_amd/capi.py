@@ -299,6 +299,11 @@ SIGNATURES = {
     "bahip_debug_set_covisibility_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bahip_debug_set_covisibility_stages": (C.c_int, [C.c_int]),
     "bahip_debug_covisibility_census": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bahip_reduced_camera_system": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Surfels), C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bahip_debug_set_rcs_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bahip_debug_set_rcs_list_capacity": (C.c_int, [C.c_int]),
+    "bahip_debug_set_rcs_stages": (C.c_int, [C.c_int]),
     "bahip_surfel_observations": (C.c_int, [C.c_void_p, C.POINTER(Surfels), C.POINTER(Observations), C.POINTER(C.c_uint64)]),
     "bahip_debug_set_observations_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64]),
     "bahip_debug_set_observations_stages": (C.c_int, [C.c_int]),

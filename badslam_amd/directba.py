@@ -54,6 +54,11 @@ def _load():
                                                       C.POINTER(capi.ResidualImageOptions)] + [C.c_void_p] * 7 + [C.POINTER(C.c_float)]
         if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_observed_covisibility"):
             L.dba_observed_covisibility.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_reduced_camera_system"):
+            L.dba_reduced_camera_system.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + \
+                [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+            L.dba_pose_covariances.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                               C.POINTER(C.c_int), C.c_void_p, C.c_char_p, C.c_int]
         if not os.environ.get("BADSLAM_LIB_DIR") or hasattr(L, "dba_surfel_observations"):
             L.dba_surfel_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int] + [C.c_void_p] * 4 + \
                 [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
@@ -289,6 +294,42 @@ class DirectBA:
         assert self.L.dba_observed_covisibility(self.h, self.stream, cap, counts.ctypes.data, ids, C.byref(rows)) == 0
         K = rows.value
         return [int(v) for v in ids[:K]], counts[:K * K].reshape(K, K).copy()
+
+    RCS_STATS = ("list_entries", "pairs_visited", "atomics_issued", "degenerate_surfels", "overflow_tiles", "invalid")
+
+    def reduced_camera_system(self, marginalise=True):
+        """DirectBA::ComputeReducedCameraSystem: a dict -- keyframe_ids (the id of each block), S (6K, 6K) and g (6K,) in float64: the
+        Gauss-Newton system over the poses of the existing keyframes with every surfel eliminated (marginalise=False: the block
+        diagonal of the pose equations), A (K, 6, 6) and b (K, 6) the keyframes' own pose equations, stats (RCS_STATS).  No gauge is
+        removed.  Not available under keyframe sharding."""
+        cap = max(1, self.keyframe_count())
+        n = 6 * cap
+        S, g, A, b = np.zeros(n * n), np.zeros(n), np.zeros(36 * cap), np.zeros(n)
+        ids, rows, stats = (C.c_int * cap)(), C.c_int(), (C.c_uint64 * 6)()
+        assert self.L.dba_reduced_camera_system(self.h, self.stream, int(bool(marginalise)), cap, S.ctypes.data, g.ctypes.data, A.ctypes.data,
+                                                b.ctypes.data, ids, stats, C.byref(rows)) == 0
+        K = rows.value
+        return dict(keyframe_ids=[int(v) for v in ids[:K]], S=S[:36 * K * K].reshape(6 * K, 6 * K).copy(), g=g[:6 * K].copy(),
+                    A=A[:36 * K].reshape(K, 6, 6).copy(), b=b[:6 * K].reshape(K, 6).copy(), stats=dict(zip(self.RCS_STATS, (int(v) for v in stats))))
+
+    def pose_covariances(self, gauge_keyframe, pairs=()):
+        """DirectBA::ComputePoseCovariances: the gauge keyframe's rows and columns deleted from the reduced camera system, the rest
+        factored and inverted in float64.  Returns (ids, marginal, cross): the remaining keyframe ids, their (R, 6, 6) marginal pose
+        covariances, and the (len(pairs), 6, 6) covariance blocks between the keyframes of each pair of ids.  Raises ValueError with
+        the reason when the gauge keyframe does not exist, a pair names it or an unknown id, or a pivot is not positive."""
+        cap = max(1, self.keyframe_count())
+        pairs = [(int(i), int(j)) for i, j in pairs]
+        marginal, cross = np.zeros(36 * cap), np.zeros(36 * max(1, len(pairs)))
+        ids, rows = (C.c_int * cap)(), C.c_int()
+        flat = (C.c_int * max(1, 2 * len(pairs)))(*[v for p in pairs for v in p])
+        error = C.create_string_buffer(512)
+        rc = self.L.dba_pose_covariances(self.h, self.stream, int(gauge_keyframe), cap, marginal.ctypes.data, ids, C.byref(rows), len(pairs), flat,
+                                         cross.ctypes.data, error, len(error))
+        if rc == 2:
+            raise ValueError(error.value.decode())
+        assert rc == 0
+        R = rows.value
+        return [int(v) for v in ids[:R]], marginal[:36 * R].reshape(R, 6, 6).copy(), cross[:36 * len(pairs)].reshape(len(pairs), 6, 6).copy()
 
     def surfel_observations(self, residuals=False):
         """DirectBA::ComputeSurfelObservations: a dict -- keyframe_ids (the id of each bound index), first (surfels_size + 1 uint32

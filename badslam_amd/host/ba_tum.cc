@@ -17,7 +17,12 @@
 //          [--residual_dir DIR [--residual_select best|worst]] [--covisibility_file F] [--observations_file F]
 //          [--redundancy_file F [--redundancy_bins B]] [--cull_redundant_keyframes M,FRACTION]
 //          [--pyramid_level_for_depth N] [--pyramid_level_for_color N] [--median_filter_and_densify_iterations N]
+//          [--pose_information_file F [--pose_information_gauge ID]]
 //
+// --pose_information_file F [--pose_information_gauge ID]: after the keyframe redundancy, the reduced camera system of the final state
+// (DirectBA::ComputeReducedCameraSystem) as a text file: one line per keyframe but the gauge keyframe ID (default: the first existing
+// one), id and the six marginal standard deviations of its pose unknowns (DirectBA::PoseCovariancesOf; 17 digits), then one line per pair
+// of keyframes i < j in id order: id_i id_j and the Frobenius norm of the block S_ij.  Nothing acts on the values.
 // --pyramid_level_for_depth N / --pyramid_level_for_color N (0 .. 3): the BA runs on depth / colour images of 2^-N the dataset's size, with
 // the dataset's cameras Scaled(1 / 2^N) (B/main.cc:457-460); every frame's depth goes through the median downscale and its colour through
 // N halvings on the GPU (CreateKeyframeFromFrame).  --median_filter_and_densify_iterations N: that many rounds of the 3 x 3 median
@@ -208,6 +213,8 @@ int main(int argc, char** argv) {
   bool intrinsics_step_control = false;
   bool use_pcg = false, intrinsics = false, incremental = false, parallel_ba = false;
   std::string save_state, load_state, render_dir, residual_dir, covisibility_file, observations_file, redundancy_file;
+  std::string pose_information_file;
+  int pose_information_gauge = -1;
   int redundancy_bins = 16, cull_min_other_observers = -1;
   double cull_min_fraction = 0.0;
   DirectBA::RenderOptions render_options;
@@ -248,6 +255,8 @@ int main(int argc, char** argv) {
     else if (a == "--observations_file" && i + 1 < argc) observations_file = argv[++i];
     else if (a == "--redundancy_file" && i + 1 < argc) redundancy_file = argv[++i];
     else if (a == "--redundancy_bins" && i + 1 < argc) redundancy_bins = atoi(argv[++i]);
+    else if (a == "--pose_information_file" && i + 1 < argc) pose_information_file = argv[++i];
+    else if (a == "--pose_information_gauge" && i + 1 < argc) pose_information_gauge = atoi(argv[++i]);
     else if (a == "--cull_redundant_keyframes" && i + 1 < argc) {
       char* rest = nullptr;
       cull_min_other_observers = (int)strtol(argv[++i], &rest, 10);
@@ -510,6 +519,33 @@ int main(int argc, char** argv) {
       }
       if (fclose(file) != 0) { fprintf(stderr, "cannot write the keyframe redundancy to %s\n", redundancy_file.c_str()); return 1; }
       printf("wrote the keyframe redundancy of %zu keyframe(s) (%d bins) to %s\n", ids.size(), redundancy_bins, redundancy_file.c_str());
+    }
+    if (!pose_information_file.empty()) {
+      DirectBA::ReducedCameraSystem system;
+      ba.ComputeReducedCameraSystem(stream, &system);
+      const size_t K = system.keyframe_ids.size(), n = 6 * K;
+      const int gauge = pose_information_gauge >= 0 ? pose_information_gauge : (K ? system.keyframe_ids[0] : 0);
+      DirectBA::PoseCovariances covariances;
+      std::string why;
+      if (!DirectBA::PoseCovariancesOf(system, gauge, &covariances, nullptr, &why)) { fprintf(stderr, "%s\n", why.c_str()); return 1; }
+      FILE* file = fopen(pose_information_file.c_str(), "w");
+      if (!file) { fprintf(stderr, "cannot write the pose information to %s\n", pose_information_file.c_str()); return 1; }
+      for (size_t q = 0; q < covariances.keyframe_ids.size(); ++q) {
+        fprintf(file, "%d", covariances.keyframe_ids[q]);
+        for (int i = 0; i < 6; ++i) fprintf(file, " %.17g", sqrt(covariances.marginal[36 * q + 7 * i]));
+        fprintf(file, "\n");
+      }
+      for (size_t i = 0; i < K; ++i)
+        for (size_t j = i + 1; j < K; ++j) {
+          double squares = 0.0;
+          for (size_t r = 0; r < 6; ++r)
+            for (size_t c = 0; c < 6; ++c) squares += system.S[(6 * i + r) * n + 6 * j + c] * system.S[(6 * i + r) * n + 6 * j + c];
+          fprintf(file, "%d %d %.17g\n", system.keyframe_ids[i], system.keyframe_ids[j], sqrt(squares));
+        }
+      if (fclose(file) != 0) { fprintf(stderr, "cannot write the pose information to %s\n", pose_information_file.c_str()); return 1; }
+      printf("wrote the pose information of %zu keyframe(s) (gauge keyframe %d) to %s: %llu list entries, %llu pairs of entries, %llu degenerate surfel(s)\n", K,
+             gauge, pose_information_file.c_str(), (unsigned long long)system.list_entries, (unsigned long long)system.pairs_visited,
+             (unsigned long long)system.degenerate_surfels);
     }
   }
   bahip_stream_destroy(stream);

@@ -185,6 +185,49 @@ int dba_observed_covisibility(dba_handle* h, void* stream, int capacity_rows, ui
   return 0;
 }
 
+int dba_reduced_camera_system(dba_handle* h, void* stream, int marginalise, int capacity_rows, double* S, double* g, double* A_diag, double* b,
+                              int* keyframe_ids, uint64_t* stats, int* num_rows_out) {
+  int rows = 0;
+  for (int id = 0; id < (int)h->ba->keyframes().size(); ++id)
+    if (h->ba->keyframes()[id]) ++rows;
+  if (num_rows_out) *num_rows_out = rows;
+  if (capacity_rows < rows || !S || !g) return 1;
+  DirectBA::ReducedCameraSystem system;
+  h->ba->ComputeReducedCameraSystem(static_cast<hipStream_t>(stream), &system, marginalise != 0);
+  std::copy(system.S.begin(), system.S.end(), S);
+  std::copy(system.g.begin(), system.g.end(), g);
+  if (A_diag) std::copy(system.A_diag.begin(), system.A_diag.end(), A_diag);
+  if (b) std::copy(system.b.begin(), system.b.end(), b);
+  if (keyframe_ids) std::copy(system.keyframe_ids.begin(), system.keyframe_ids.end(), keyframe_ids);
+  if (stats) {
+    stats[0] = system.list_entries; stats[1] = system.pairs_visited; stats[2] = system.atomics_issued;
+    stats[3] = system.degenerate_surfels; stats[4] = system.overflow_tiles; stats[5] = system.invalid;
+  }
+  return 0;
+}
+
+int dba_pose_covariances(dba_handle* h, void* stream, int gauge_keyframe_id, int capacity_rows, double* marginal, int* keyframe_ids, int* num_rows_out,
+                         int num_pairs, const int* pair_ids, double* cross, char* error, int error_capacity) {
+  int rows = -1;   // the existing keyframes but the gauge one
+  for (int id = 0; id < (int)h->ba->keyframes().size(); ++id)
+    if (h->ba->keyframes()[id]) ++rows;
+  if (num_rows_out) *num_rows_out = std::max(rows, 0);
+  if (capacity_rows < rows || !marginal || (num_pairs > 0 && (!pair_ids || !cross))) return 1;
+  std::vector<std::pair<int, int>> pairs;
+  for (int q = 0; q < num_pairs; ++q) pairs.emplace_back(pair_ids[2 * q], pair_ids[2 * q + 1]);
+  DirectBA::PoseCovariances covariances;
+  std::string why;
+  if (!h->ba->ComputePoseCovariances(static_cast<hipStream_t>(stream), gauge_keyframe_id, &covariances, &pairs, &why)) {
+    if (error && error_capacity > 0) snprintf(error, (size_t)error_capacity, "%s", why.c_str());
+    return 2;
+  }
+  if (num_rows_out) *num_rows_out = (int)covariances.keyframe_ids.size();
+  std::copy(covariances.marginal.begin(), covariances.marginal.end(), marginal);
+  if (keyframe_ids) std::copy(covariances.keyframe_ids.begin(), covariances.keyframe_ids.end(), keyframe_ids);
+  if (cross) std::copy(covariances.cross.begin(), covariances.cross.end(), cross);
+  return 0;
+}
+
 int dba_surfel_observations(dba_handle* h, void* stream, uint32_t capacity_surfels, uint64_t capacity_pairs, int capacity_keyframes, uint32_t* first,
                             uint16_t* keyframes, float* depth_raw, float* descriptor_raw, int* keyframe_ids, uint64_t* pairs_out, int* num_keyframes_out) {
   DirectBA::SurfelObservations t;

@@ -583,6 +583,111 @@ void DirectBA::ComputeObservedCovisibility(hipStream_t stream, vector<uint32_t>*
   BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
 }
 
+void DirectBA::ComputeReducedCameraSystem(hipStream_t stream, ReducedCameraSystem* out, bool marginalise) {
+  BindScene(stream);
+  const bahip_surfels s = SurfelsStruct(/*with_active*/ false);
+  const size_t K = bound_ids_.size(), n = 6 * K;
+  *out = ReducedCameraSystem();
+  out->S.assign(n * n, 0.0); out->g.assign(n, 0.0); out->A_diag.assign(36 * K, 0.0); out->b.assign(n, 0.0);
+  out->keyframe_ids.assign(bound_ids_.begin(), bound_ids_.end());
+  if (K == 0) return;
+  // one device block for the four planes, in doubles: S, g, A_diag, b
+  const size_t doubles = n * n + n + 36 * K + n;
+  if (2 * doubles > (size_t)0x7fffffff) LOG(FATAL) << "ComputeReducedCameraSystem: " << K << " keyframes are too many for one buffer";
+  CUDABuffer<uint32_t> planes(1, (int)(2 * doubles));
+  double* dev_S = reinterpret_cast<double*>(planes.ToCUDA().address());
+  double* dev_g = dev_S + n * n;
+  double* dev_A = dev_g + n;
+  double* dev_b = dev_A + 36 * K;
+  bahip_rcs_stats stats{};
+  BAHIP_CHECKED_CALL(bahip_reduced_camera_system(ctx_, use_depth_residuals_ ? 1 : 0, use_descriptor_residuals_ ? 1 : 0, marginalise ? 1 : 0, &s, dev_S, n,
+                                                 dev_g, dev_A, dev_b, &stats));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->S.data(), dev_S, sizeof(double) * n * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->g.data(), dev_g, sizeof(double) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->A_diag.data(), dev_A, sizeof(double) * 36 * K, 2));
+  BAHIP_CHECKED_CALL(bahip_memcpy_async(stream, out->b.data(), dev_b, sizeof(double) * n, 2));
+  BAHIP_CHECKED_CALL(bahip_stream_synchronize(stream));
+  out->list_entries = stats.list_entries; out->pairs_visited = stats.pairs_visited; out->atomics_issued = stats.atomics_issued;
+  out->degenerate_surfels = stats.degenerate_surfels; out->overflow_tiles = stats.overflow_tiles; out->invalid = stats.invalid;
+}
+
+bool DirectBA::PoseCovariancesOf(const ReducedCameraSystem& system, int gauge_keyframe_id, PoseCovariances* out,
+                                 const vector<std::pair<int, int>>* pairs, std::string* error) {
+  auto refuse = [&](const std::string& why) { if (error) *error = why; return false; };
+  const size_t K = system.keyframe_ids.size();
+  vector<int> ids;           // the remaining keyframes
+  vector<size_t> blocks;     // ... and their blocks in the system
+  bool found = false;
+  for (size_t i = 0; i < K; ++i) {
+    if (system.keyframe_ids[i] == gauge_keyframe_id) { found = true; continue; }
+    ids.push_back(system.keyframe_ids[i]);
+    blocks.push_back(i);
+  }
+  if (!found) return refuse("pose covariances: the gauge keyframe " + std::to_string(gauge_keyframe_id) + " does not exist");
+  auto row_of = [&](int id) { for (size_t r = 0; r < ids.size(); ++r) if (ids[r] == id) return (long)r; return -1l; };
+  if (pairs)
+    for (const auto& p : *pairs)
+      if (row_of(p.first) < 0 || row_of(p.second) < 0)
+        return refuse("pose covariances: the pair (" + std::to_string(p.first) + ", " + std::to_string(p.second) + ") names the gauge keyframe or a keyframe that does not exist");
+  if (system.invalid) return refuse("pose covariances: the sums of the reduced camera system were invalid");
+  const size_t m = 6 * ids.size(), n = 6 * K;
+  // R = S without the gauge rows and columns; R = L D L^T in place (L unit lower in the strict lower triangle, D on the diagonal)
+  vector<double> R(m * m);
+  for (size_t r = 0; r < m; ++r)
+    for (size_t c = 0; c < m; ++c) R[r * m + c] = system.S[(6 * blocks[r / 6] + r % 6) * n + 6 * blocks[c / 6] + c % 6];
+  for (size_t j = 0; j < m; ++j) {
+    double d = R[j * m + j];
+    for (size_t k = 0; k < j; ++k) d -= R[j * m + k] * R[j * m + k] * R[k * m + k];
+    if (!(d > 0.0) || !std::isfinite(d))
+      return refuse("pose covariances: pivot " + std::to_string(j) + " (keyframe " + std::to_string(ids[j / 6]) + ", unknown " + std::to_string(j % 6) +
+                    ") is not positive: the poses are not determined");
+    R[j * m + j] = d;
+    for (size_t i = j + 1; i < m; ++i) {
+      double v = R[i * m + j];
+      for (size_t k = 0; k < j; ++k) v -= R[i * m + k] * R[j * m + k] * R[k * m + k];
+      R[i * m + j] = v / d;
+    }
+  }
+  // W = L^-1 (unit lower), then the inverse = W^T D^-1 W
+  vector<double> W(m * m, 0.0);
+  for (size_t c = 0; c < m; ++c) {
+    W[c * m + c] = 1.0;
+    for (size_t i = c + 1; i < m; ++i) {
+      double v = 0.0;
+      for (size_t k = c; k < i; ++k) v -= R[i * m + k] * W[k * m + c];
+      W[i * m + c] = v;
+    }
+  }
+  auto inverse = [&](size_t r, size_t c) {
+    double v = 0.0;
+    for (size_t k = std::max(r, c); k < m; ++k) v += W[k * m + r] * W[k * m + c] / R[k * m + k];
+    return v;
+  };
+  PoseCovariances result;
+  result.keyframe_ids = ids;
+  result.marginal.resize(36 * ids.size());
+  for (size_t q = 0; q < ids.size(); ++q)
+    for (int i = 0; i < 6; ++i)
+      for (int j = 0; j < 6; ++j) result.marginal[36 * q + 6 * i + j] = inverse(6 * q + std::min(i, j), 6 * q + std::max(i, j));
+  if (pairs) {
+    result.cross.resize(36 * pairs->size());
+    for (size_t q = 0; q < pairs->size(); ++q) {
+      const size_t a = (size_t)row_of((*pairs)[q].first), b = (size_t)row_of((*pairs)[q].second);
+      for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) result.cross[36 * q + 6 * i + j] = inverse(6 * a + i, 6 * b + j);
+    }
+  }
+  *out = std::move(result);
+  return true;
+}
+
+bool DirectBA::ComputePoseCovariances(hipStream_t stream, int gauge_keyframe_id, PoseCovariances* out, const vector<std::pair<int, int>>* pairs,
+                                      std::string* error) {
+  ReducedCameraSystem system;
+  ComputeReducedCameraSystem(stream, &system, /*marginalise*/ true);
+  return PoseCovariancesOf(system, gauge_keyframe_id, out, pairs, error);
+}
+
 void DirectBA::ComputeSurfelObservations(hipStream_t stream, SurfelObservations* out, bool with_residuals) {
   BindScene(stream);
   const bahip_surfels s = SurfelsStruct(/*with_active*/ false);

@@ -12,6 +12,8 @@
 #pragma once
 
 #include <limits>
+#include <string>
+#include <utility>
 
 #include "camera_frustum.h"
 #include "keyframe.h"
@@ -71,6 +73,33 @@ class DirectBA {
   // the values: the co-visibility lists of the keyframes stay the frustum test's.  Surfel sharding with an all-reduce installed: every
   // rank gets the unsharded matrix; keyframe sharding: the same, by way of the tile mask table.  Waits for the stream.
   void ComputeObservedCovisibility(hipStream_t stream, vector<uint32_t>* counts, vector<int>* keyframe_ids);
+  // The reduced camera system (bahip_reduced_camera_system; DESIGN.md section 3, "The reduced camera system") with this object's
+  // residual switches: S (6K x 6K row-major) and g (6K) -- the Gauss-Newton system over the poses of the K existing keyframes with every
+  // surfel eliminated, 6 unknowns per keyframe in the tangent convention of the pose phase, no gauge removed --, A_diag (K x 36) and b
+  // (K x 6) the keyframes' own pose equations; keyframe_ids[i] = the id of block i.  marginalise false: S = blockdiag(A), g = b.
+  // Nothing acts on the values.  Surfel sharding with an all-reduce installed: the unsharded system on every rank; not available under
+  // keyframe sharding.  Waits for the stream.
+  struct ReducedCameraSystem {
+    vector<double> S, g, A_diag, b;
+    vector<int> keyframe_ids;
+    uint64_t list_entries = 0, pairs_visited = 0, atomics_issued = 0, degenerate_surfels = 0, overflow_tiles = 0, invalid = 0;
+  };
+  void ComputeReducedCameraSystem(hipStream_t stream, ReducedCameraSystem* out, bool marginalise = true);
+  // Marginal pose covariances from the reduced camera system: the 6 rows and columns of gauge_keyframe_id are deleted, the rest is
+  // factored in binary64 (L D L^T in the order of the blocks, no pivoting) and inverted.  keyframe_ids: the remaining keyframes in
+  // order; marginal: their 6 x 6 covariance blocks (36 words each); for every pair (i, j) of ids in `pairs` the 6 x 6 block between
+  // them goes to cross (rows of i, columns of j).  Returns false with *error set and nothing else written when the gauge keyframe does
+  // not exist, a pair names it or an unknown id, or a pivot is not positive (the poses are not determined: too few observations, or
+  // the sums were invalid).
+  struct PoseCovariances {
+    vector<int> keyframe_ids;
+    vector<double> marginal, cross;
+  };
+  bool ComputePoseCovariances(hipStream_t stream, int gauge_keyframe_id, PoseCovariances* out, const vector<std::pair<int, int>>* pairs = nullptr,
+                              std::string* error = nullptr);
+  // The same from a system already computed (no GPU work).
+  static bool PoseCovariancesOf(const ReducedCameraSystem& system, int gauge_keyframe_id, PoseCovariances* out,
+                                const vector<std::pair<int, int>>* pairs, std::string* error);
   // Observation lists (bahip_surfel_observations; DESIGN.md section 3, "Observation lists"): the associated (surfel, keyframe) pairs in
   // compressed rows by surfel.  first: surfels_size + 1 offsets, first.back() = the number of pairs; keyframes[first[s] .. first[s + 1]):
   // the keyframes paired with surfel s as indices into keyframe_ids, ascending; keyframe_ids[k] = the id of bound index k (deleted

@@ -884,6 +884,43 @@ class Scene:
         finally:
             buf.free()
 
+    RCS_STATS = ("list_entries", "pairs_visited", "atomics_issued", "degenerate_surfels", "overflow_tiles", "invalid")
+
+    def reduced_camera_system(self, use_depth=True, use_desc=True, marginalise=True, size=None, pitch=None, prefill=None, planes=True):
+        """The reduced camera system of the bound keyframes (bahip_reduced_camera_system) over the first `size` surfels (default: all):
+        a dict with S (6K, 6K) and g (6K,) in binary64 -- the Gauss-Newton system over the poses with every surfel eliminated
+        (marginalise=False: the block-diagonal pose equations) --, A (K, 6, 6) and b (K, 6) (planes=False: not asked for, None) and
+        stats (RCS_STATS).  pitch: doubles per row of the device buffer of S (default 6K; the call refuses less) -- S is then the whole
+        (6K, pitch) buffer; prefill: a byte value every buffer is filled with before the call (after a refused call the buffers are
+        the exception's `arrays` attribute: S, g, A, b).  Call bind_keyframes first."""
+        K = len(self.keyframes)
+        n = 6 * K
+        p = n if pitch is None else int(pitch)
+        bufs = [DeviceBuffer2D(self.ctx, 1, max(1, n * max(p, 1)), np.float64), DeviceBuffer2D(self.ctx, 1, max(1, n), np.float64)]
+        if planes:
+            bufs += [DeviceBuffer2D(self.ctx, 1, max(1, 36 * K), np.float64), DeviceBuffer2D(self.ctx, 1, max(1, n), np.float64)]
+        try:
+            for buf in bufs:
+                buf.clear(0 if prefill is None else prefill)
+            s = self.surfels_struct(size)
+            stats = (C.c_uint64 * 6)()
+            try:
+                capi.check(self.lib.bahip_reduced_camera_system(self.ctx.handle, int(bool(use_depth)), int(bool(use_desc)), int(bool(marginalise)),
+                                                                C.byref(s), bufs[0].ptr, p, bufs[1].ptr, bufs[2].ptr if planes else None,
+                                                                bufs[3].ptr if planes else None, stats))
+            except capi.BackendError as e:
+                self.ctx.synchronize()
+                e.arrays = [buf.download()[0].copy() for buf in bufs]
+                raise
+            self.ctx.synchronize()
+            return dict(S=bufs[0].download()[0, :n * p].reshape(n, p).copy(), g=bufs[1].download()[0, :n].copy(),
+                        A=bufs[2].download()[0, :36 * K].reshape(K, 6, 6).copy() if planes else None,
+                        b=bufs[3].download()[0, :n].reshape(K, 6).copy() if planes else None,
+                        stats=dict(zip(self.RCS_STATS, (int(v) for v in stats))))
+        finally:
+            for buf in bufs:
+                buf.free()
+
     def covisibility_census(self):
         """Of the last observed_covisibility: [(tile, keyframe) entries with a non-zero mask, atomic adds issued, tiles that took the
         overflow path] (bahip_debug_covisibility_census)."""

@@ -75,6 +75,20 @@ int dba_compute_surfel_costs(dba_handle* h, void* hip_stream, uint32_t capacity,
  * triangles, the diagonal a keyframe's own pair count.  Returns non-zero, with *num_rows_out set and nothing else written, when
  * capacity_rows < K.  Surfel sharding with an all-reduce installed: the unsharded matrix on every rank; keyframe sharding: the same. */
 int dba_observed_covisibility(dba_handle* h, void* hip_stream, int capacity_rows, uint32_t* counts, int* keyframe_ids, int* num_rows_out);
+/* DirectBA::ComputeReducedCameraSystem (ours): the Gauss-Newton system over the poses of the K existing keyframes with every surfel
+ * eliminated (bahip_reduced_camera_system), blocks in id order (deleted ids are not blocks).  *num_rows_out = K; when capacity_rows >= K:
+ * S (6K x 6K row-major), g (6K), A_diag (K x 36) and b (K x 6) -- the last two may be NULL --, keyframe_ids[0 .. K) (may be NULL) and
+ * stats[0 .. 6) (may be NULL: list entries, pairs visited, atomics issued, degenerate surfels, overflow tiles, invalid).  marginalise 0:
+ * S = blockdiag(A), g = b.  Returns non-zero, with *num_rows_out set and nothing else written, when capacity_rows < K or S or g is NULL. */
+int dba_reduced_camera_system(dba_handle* h, void* hip_stream, int marginalise, int capacity_rows, double* S, double* g, double* A_diag, double* b,
+                              int* keyframe_ids, uint64_t* stats, int* num_rows_out);
+/* DirectBA::ComputePoseCovariances (ours): the gauge keyframe's rows and columns deleted from S, the rest factored (L D L^T, binary64)
+ * and inverted.  *num_rows_out = R, the remaining keyframes; when capacity_rows >= R: marginal (R x 36: each keyframe's 6 x 6 covariance),
+ * keyframe_ids[0 .. R) (may be NULL) and, for the num_pairs pairs of ids in pair_ids (two ids each), cross (num_pairs x 36: the block
+ * between them).  Returns 1 when a capacity or a pointer is missing; 2 with the reason in error (error_capacity bytes, may be NULL) and
+ * nothing else written when the gauge keyframe does not exist, a pair names it or an unknown id, or a pivot is not positive. */
+int dba_pose_covariances(dba_handle* h, void* hip_stream, int gauge_keyframe_id, int capacity_rows, double* marginal, int* keyframe_ids,
+                         int* num_rows_out, int num_pairs, const int* pair_ids, double* cross, char* error, int error_capacity);
 /* DirectBA::ComputeSurfelObservations (ours): the observation lists (bahip_surfel_observations) into host arrays -- first
  * (surfels_size + 1 offsets, the last one the number of pairs P), keyframes (P indices into keyframe_ids, ascending within a list),
  * depth_raw (P words) and descriptor_raw (2 P words), either or both may be NULL, and keyframe_ids (the id of each bound index, may be

@@ -899,6 +899,47 @@ int bahip_debug_read_tile_masks(bahip_context* ctx, uint32_t* tile_first, uint32
  * rank's adds, [2] 0. */
 int bahip_debug_tile_mask_stats(bahip_context* ctx, uint64_t out[6]);
 
+/* ---- the reduced camera system (kernels_rcs.hip; DESIGN.md section 3, "The reduced camera system") --------------------------------
+ * The second-order structure of the joint problem over the bound keyframes: the 6K x 6K matrix S and the vector g that remain of the
+ * Gauss-Newton system over poses and surfels when every surfel's unknowns are eliminated (the Schur complement on the poses).  The
+ * pairs are those of bahip_evaluate_cost with the same use_depth / use_desc, at the current state; nothing is written to the state,
+ * activation flags play no part.  6 unknowns per bound keyframe in bound order, in the tangent convention of the pose phase
+ * (T <- T exp(-x)); no gauge is removed.  Per surfel 3 unknowns with descriptors (offset along the normal, the two descriptors), 1
+ * without.  A surfel whose 3 x 3 factor is not finite or has a pivot that is not positive is degenerate: counted, held fixed.
+ * S_kl = delta_kl A_k - M_kl and g_k = b_k - v_k in binary64, where A_k, b_k are the keyframe's pose equations -- the fixed-point sums
+ * bahip_accumulate_pose_estimation_coeffs rounds to binary32, here as binary64 -- and M, v are sums over the surfels with the same
+ * definition (fixed tile tree, two-limb fixed point): no word depends on the launch shape, the tile order, the list capacity or the
+ * order atomics arrive in, and S equals its transpose bit for bit.
+ * S: device memory, 6K rows of pitch_doubles >= 6K doubles (the words [6K, pitch_doubles) of a row are never touched); g: device,
+ * 6K doubles; A_diag (K x 36, row-major 6 x 6 blocks) and b (K x 6): device, optional, a NULL plane is skipped.  marginalise = 0:
+ * S = blockdiag(A), g = b, the surfel stage does not run.  stats: host memory, optional.  invalid != 0: a tile total or a sum was
+ * beyond the fixed point's range and is missing from the words.  The call waits for the stream.
+ * Refused -- error text, nothing written -- when ctx, surfels, S or g is NULL, no keyframe is bound, neither term is selected,
+ * pitch_doubles < 6K, no intrinsics are set, or the context is keyframe-sharded (a rank lacks the other ranks' pairs).  Surfel
+ * sharding: the call covers the shard it is given; with an all-reduce hook or an RCCL communicator the integer sums are added over
+ * the ranks (one exchange) and every rank ends with the unsharded words and statistics; a failing exchange fails the call by name
+ * and writes nothing.  The kernels exist once, in the exact arithmetic flavour. */
+typedef struct {
+  uint64_t list_entries;        /* (tile, keyframe) entries with an associated surfel */
+  uint64_t pairs_visited;       /* pairs a <= b of a tile's entries that share a surfel */
+  uint64_t atomics_issued;      /* 64-bit limb adds due: 12 per entry, 72 per pair a < b, 42 per pair a = b */
+  uint64_t degenerate_surfels;
+  uint64_t overflow_tiles;      /* tiles with more entries than the list holds: walked in passes */
+  uint64_t invalid;
+} bahip_rcs_stats;
+int bahip_reduced_camera_system(bahip_context* ctx, int use_depth, int use_desc, int marginalise, const bahip_surfels* surfels, double* S,
+                                size_t pitch_doubles, double* g, double* A_diag, double* b, bahip_rcs_stats* stats);
+/* Launch shape of the sweep (test hooks; results never depend on it): wavefronts per workgroup 1 .. 4, workgroups >= 1, list_capacity
+ * 1 .. 32 = the entries (keyframe, mask, Y) a wavefront keeps in LDS before a tile is walked in passes, tile_order 0 = buffer order,
+ * 1 = the sweeps' heavy-first order when there is one; 0 / -1 = the default.  Refused when waves x list_capacity entries with
+ * descriptors (4 620 bytes each) exceed 160 KB. */
+int bahip_debug_set_rcs_shape(int waves, int workgroups, int list_capacity, int tile_order);
+int bahip_debug_set_rcs_list_capacity(int list_capacity);
+/* What bahip_reduced_camera_system launches (scripts/reduced_camera_system_eval.py takes the stages' times by difference): 1 the pose
+ * sums, 2 the factor traversal of the surfel stage, 4 its pair stage (needs 2), 8 the resolution into the caller's planes, or-ed;
+ * 0 = all.  With a stage missing the words are not the system. */
+int bahip_debug_set_rcs_stages(int stages);
+
 /* ---- step control for the PCG scheme (ours: the reference applies every update; kernels_pcg_trial.hip) --------
  * Damping.  A factor lambda >= 0 per context (default 0), Marquardt-scaled by the diagonal M the scheme assembles: for unknown u, with
  * e = 1e-8 + prior(u) as before and t = lambda * M[u] (one binary32 product), the preconditioner divides by ((M[u] + 1e-8) + prior(u))
